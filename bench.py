@@ -4,9 +4,18 @@ src/vertexcm.hxx:284-548) on BASELINE.json's workloads.
 
   python bench.py [--gpus N] [--steps K] [--warmup W]            headline: scene 1, VCM, 2048x2048, maxPathLength 10
   python bench.py --scene 3 --algo vcm --res 1024                any other built-in configuration (named in the line)
+  python bench.py ... --full                                     everything below besides the headline (minutes)
+  python bench.py ... --dump-outputs DIR                         the timed path's framebuffer as DIR/framebuffer.npy
 
 A "step" is one RunIteration = N light sub-paths + N camera sub-paths, N = res*res.
 Mpaths/s = 2*N*steps / seconds / 1e6 (BASELINE.md).
+
+A plain run sets up, warms up, times the K steps and prints the line: its roofline comes from the timed steps' own
+device stamps (and a counter recording in profiles/ made on the same kernel sources, if there is one).  Whatever takes
+runs of its own -- the rocprofv3 counter passes, `configs`, `cpu_baseline`, `dropin`, `host_cross_check`, and at N > 1
+the RCCL self-check and `hybrid_decomposition` -- runs only with --full (the --no-* / --cpu-baseline options narrow it).
+--dump-outputs DIR writes the framebuffer the timed steps accumulated (what vcm_farm_render returns: the mean over the
+renderers of their running sums, warm-up cleared) as float32 [res, res, 3]; the inputs are fixed by the arguments.
 
 STDOUT IS ONE SHORT JSON LINE (< 4 KB: the driver keeps a tail of stdout and parses its last line; round 4's 20 KB line did
 not survive that).  Everything else the run measured -- per-kernel blocks, counters, the config blocks, CPU samples --
@@ -557,6 +566,13 @@ def emit(full):
     print(json.dumps(line, allow_nan=False), flush=True)
 
 
+def dump_outputs(out_dir, image):
+    """--dump-outputs: the framebuffer the timed steps produced (float32, resy x resx x 3; 48 MB at 2048^2)"""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "framebuffer.npy"), np.ascontiguousarray(image, dtype=np.float32))
+
+
 def workload_name(scene, algo, res, replicas, first, last):
     if isinstance(scene, str):
         scene_txt = ("scene file %s (vcm_scene_load), BVH," % scene.split(":", 1)[1] if scene.startswith("file:")
@@ -592,7 +608,7 @@ def cpu_port(scene, algo, res, iteration, budget_rows=8):
     sys.path.insert(0, os.path.join(ROOT, "tests"))
     from oracle_lib import Oracle, oracle
     from smallvcm_amd.renderer import cornell_scene
-    cores = oracle().oracle_max_threads()
+    cores = min(oracle().oracle_max_threads(), usable_cores())
     o = Oracle(cornell_scene(scene, res, res), algo, threads=cores)
     n = res * res
     t0 = time.perf_counter()
@@ -636,6 +652,20 @@ def host_memory_GB():
         except Exception:
             continue
     return round(total, 1), round(avail, 1)
+
+
+def usable_cores():
+    """host threads this process may keep busy: the affinity mask, capped by OMP_NUM_THREADS where the host sets it (a
+    share of a larger machine: os.cpu_count() counts the whole machine, and a pool sized by it only slows itself down)"""
+    try:
+        n = len(os.sched_getaffinity(0))
+    except (AttributeError, OSError):
+        n = os.cpu_count() or 1
+    try:
+        omp = int(os.environ.get("OMP_NUM_THREADS", "0").split(",")[0])
+    except ValueError:
+        omp = 0
+    return max(1, min(n, omp) if omp > 0 else n)
 
 
 REF_GB_PER_RENDERER_2048 = 1.3   # one VertexCM of the reference at 2048^2: mLightVertices 8.9 M x 120 B + the hash grid + the framebuffer
@@ -797,7 +827,7 @@ def multi_gpu(args):
     shards = args.shards if args.shards > 0 else N
     inflight = args.inflight if args.inflight > 0 else 1
     # two real RCCL ranks against one GPU, both exchanges, before anything is timed (a few seconds; rank 0's subprocesses)
-    selftest = rccl_selftest() if (rank == 0 and args.collectives == "rccl") else None
+    selftest = rccl_selftest() if (args.full and rank == 0 and args.collectives == "rccl") else None
     main_run = run(shards, inflight)
     strong = None
     hybrid = run(2, 2) if (args.shards <= 0 and args.inflight <= 0 and N % 2 == 0 and not args.no_hybrid) else None
@@ -831,6 +861,8 @@ def multi_gpu(args):
                                                  "mergeAccepted", "connections", "lightSplats", "lightRays", "cameraRays", "shadowRays")},
             "image_mean": [round(float(x), 5) for x in main_run["image"].mean(axis=(0, 1))],
         }
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, main_run["image"])
         roof["scope"] = "world rank 0 (1 of %d shards of renderer 0), mean over its timed iterations" % shards
         out["roofline"] = finalize_roofline(roof)
         if selftest is not None:
@@ -865,7 +897,8 @@ def main():
     ap.add_argument("--collectives", default="rccl", choices=["rccl", "threads"],
                     help="threads: in-process stand-in for RCCL so that --gpus N ranks can share one GPU (tests)")
     ap.add_argument("--cpu-baseline", default="reference", choices=["reference", "port", "none"],
-                    help="reference: the unmodified reference in this run (minutes of host CPU at 2048^2) + the port; "
+                    help="with --full (a plain run has none): "
+                         "reference: the unmodified reference in this run (minutes of host CPU at 2048^2) + the port; "
                          "port: only the oracle restatement (seconds); none")
     ap.add_argument("--no-cpu-baseline", action="store_true", help="same as --cpu-baseline none")
     ap.add_argument("--cpu-threads", type=int, default=0, help="threads of the reference leg (default min(32, cores): "
@@ -881,10 +914,20 @@ def main():
     ap.add_argument("--no-cross-check", action="store_true", help="skip the second timing of the headline through the Python host")
     ap.add_argument("--record-counters", default="", metavar="TAG",
                     help="keep the live counter sets as profiles/TAG_counters_<config>.json (the fallback of runs without a profiler)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beyond the headline: live counter passes, the other configs, the drop-in "
+                         "leg, the Python-host cross-check, the CPU baselines; N > 1: the RCCL self-check and the hybrid decomposition")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps write their framebuffer (float32, res x res x 3) as DIR/framebuffer.npy")
     ap.add_argument("--child", action="store_true", help=argparse.SUPPRESS)   # inner run under rocprofv3: GPU loop only
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("bench.py: --steps must be >= 1 and --warmup >= 0")
     if args.no_cpu_baseline:
         args.cpu_baseline = "none"
+    if not args.full:   # a plain run: the headline alone
+        args.cpu_baseline = "none"
+        args.no_configs = args.no_dropin = args.no_cross_check = args.no_hybrid = True
     if args.scene_file:   # a scene the reference cannot load: no CPU leg, no per-kernel child runs by scene id
         args.scene = "file:" + args.scene_file
         args.cpu_baseline, args.no_traffic = "none", True
@@ -906,13 +949,20 @@ def main():
                       collectives="threads")
         return
 
-    import torch
-    if not torch.cuda.is_available():
-        raise SystemExit("bench.py needs a GPU (the product has no CPU path)")
-    torch.cuda.set_device(local_rank)
+    builtin = not isinstance(args.scene, str)
+    if builtin and not args.full:
+        # the headline alone: the C++ farm's loop over the C-ABI, as in --child, nothing in it needs torch
+        if load_library(require_gpu=False).vcm_device_count() <= 0:
+            raise SystemExit("bench.py needs a GPU (the product has no CPU path)")
+        sync = None
+    else:
+        import torch
+        if not torch.cuda.is_available():
+            raise SystemExit("bench.py needs a GPU (the product has no CPU path)")
+        torch.cuda.set_device(local_rank)
 
-    def sync():
-        torch.cuda.synchronize()
+        def sync():
+            torch.cuda.synchronize()
 
     def make_farm(scene, algo_name, res, shards, inflight):
         if isinstance(scene, str) and scene.startswith("file:"):   # a scene file: version-2 description, BVH
@@ -943,7 +993,6 @@ def main():
                            inflight=nfl, devices=[local_rank], warmup=warmup, same_window=True, collectives="threads")
         return rr["wall_s"], rr["stats"], rr["image"], rr["rank_iteration_ms"]
 
-    builtin = not isinstance(args.scene, str)
     cross = None
     if builtin:
         nfl0 = args.inflight if args.inflight > 0 else 1
@@ -972,6 +1021,8 @@ def main():
         inflight_used = farm.inflight
         farm.close()
         host = "Python (smallvcm_amd.renderer.RenderFarm over ctypes): scene files are not wired into the C++ farm"
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, fb)
 
     value = 2.0 * n_paths * args.steps * replicas / elapsed / 1e6
     dom, roof = roofline_block(st, n_local, n_paths)
@@ -1006,8 +1057,11 @@ def main():
             return None, "disabled (--no-traffic)"
         if isinstance(scene, str):
             return None, "scene files have no child runs"
-        ns = argparse.Namespace(res=r, scene=scene, algo=algo_name, steps=args.steps, warmup=args.warmup)
-        counters, src = live_counters(ns)
+        if args.full:
+            ns = argparse.Namespace(res=r, scene=scene, algo=algo_name, steps=args.steps, warmup=args.warmup)
+            counters, src = live_counters(ns)
+        else:
+            counters, src = None, "live counter passes run with --full only"
         if counters is not None:
             if args.record_counters:
                 try:
@@ -1085,7 +1139,7 @@ def main():
             port = {"error": repr(e)}
         if args.cpu_baseline == "reference":
             try:
-                cores = os.cpu_count() or 1
+                cores = usable_cores()
                 threads = args.cpu_threads if args.cpu_threads > 0 else min(32, cores)
                 base = cpu_reference(args.scene, args.algo, res, args.warmup, args.steps, threads)
                 base["host_cores"] = cores

@@ -8,7 +8,7 @@
 # steps
 #   pytest            the whole GPU suite                               -> <tag>_pytest.log
 #   pytest:<expr>     ... restricted with -k <expr>
-#   bench             python bench.py --steps 20 --warmup 5 (the driver's command; CPU legs included: minutes)
+#   bench             python bench.py --full --steps 20 --warmup 5 (CPU legs, other configs, counter passes: minutes)
 #   bench_nocpu       ... --cpu-baseline none
 #   bench_record      ... --cpu-baseline none --record-counters <tag>  (keeps profiles/<tag>_counters_<config>.json)
 #   collect           profiles/collect.sh <tag> on the headline (kernel stats, FETCH / WRITE, SQ passes)
@@ -32,9 +32,9 @@ for step in "$@"; do
   case "$step" in
     pytest)        timeout 1500 python -m pytest tests -m gpu -x -q > ${O}_pytest.log 2>&1; tail -3 ${O}_pytest.log ;;
     pytest:*)      timeout 1200 python -m pytest tests -m gpu -x -q -k "${step#pytest:}" > ${O}_pytest_k.log 2>&1; tail -3 ${O}_pytest_k.log ;;
-    bench)         timeout 1500 python bench.py --steps 20 --warmup 5 > ${O}_bench.log 2> ${O}_bench.err; tail -c 4200 ${O}_bench.log; cp -f bench_detail.json ${O}_bench_detail.json 2>/dev/null ;;
-    bench_nocpu)   timeout 900 python bench.py --steps 20 --warmup 5 --cpu-baseline none > ${O}_bench_nocpu.log 2> ${O}_bench_nocpu.err; tail -c 4200 ${O}_bench_nocpu.log; tail -5 ${O}_bench_nocpu.err; cp -f bench_detail.json ${O}_bench_nocpu_detail.json 2>/dev/null ;;
-    bench_record)  timeout 900 python bench.py --steps 20 --warmup 5 --cpu-baseline none --record-counters ${TAG} > ${O}_bench_record.log 2> ${O}_bench_record.err; tail -c 4200 ${O}_bench_record.log; cp -f bench_detail.json ${O}_bench_record_detail.json 2>/dev/null; cp -f profiles/${TAG}_counters_*.json gpurun_out/ 2>/dev/null ;;
+    bench)         timeout 1500 python bench.py --full --steps 20 --warmup 5 > ${O}_bench.log 2> ${O}_bench.err; tail -c 4200 ${O}_bench.log; cp -f bench_detail.json ${O}_bench_detail.json 2>/dev/null ;;
+    bench_nocpu)   timeout 900 python bench.py --full --steps 20 --warmup 5 --cpu-baseline none > ${O}_bench_nocpu.log 2> ${O}_bench_nocpu.err; tail -c 4200 ${O}_bench_nocpu.log; tail -5 ${O}_bench_nocpu.err; cp -f bench_detail.json ${O}_bench_nocpu_detail.json 2>/dev/null ;;
+    bench_record)  timeout 900 python bench.py --full --steps 20 --warmup 5 --cpu-baseline none --record-counters ${TAG} > ${O}_bench_record.log 2> ${O}_bench_record.err; tail -c 4200 ${O}_bench_record.log; cp -f bench_detail.json ${O}_bench_record_detail.json 2>/dev/null; cp -f profiles/${TAG}_counters_*.json "$(dirname ${O})/" 2>/dev/null ;;
     collect)       BENCH_ARGS="--steps 20 --warmup 5" timeout 900 bash profiles/collect.sh ${TAG} > ${O}_collect.log 2>&1; tail -3 ${O}_collect.log ;;
     collect:C1)    BENCH_ARGS="--steps 20 --warmup 5 --scene 1 --algo vcm --res 512" timeout 600 bash profiles/collect.sh ${TAG}_C1 > ${O}_collect_C1.log 2>&1; tail -2 ${O}_collect_C1.log ;;
     collect:C2)    BENCH_ARGS="--steps 20 --warmup 5 --scene 3 --algo vcm --res 1024" timeout 600 bash profiles/collect.sh ${TAG}_C2 > ${O}_collect_C2.log 2>&1; tail -2 ${O}_collect_C2.log ;;

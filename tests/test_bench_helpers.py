@@ -228,3 +228,11 @@ def test_a_kernel_launched_three_times_per_iteration_counts_three_times():
         grid = ["vcm::k_cell_", "vcm::k_radix_", "vcm::k_grid_", "vcm::k_bbox"]
         gb = (2 * bench._sum_over(k, grid, "FETCH_SIZE") + bench._sum_over(k, grid, "WRITE_SIZE")) * 1024 / 1e9
         assert 3.0 < gb < 4.6, gb
+
+
+def test_cpu_legs_are_sized_by_the_cores_this_process_may_use(monkeypatch):
+    """the CPU baselines run as many threads as the process may keep busy, not os.cpu_count() of a shared host"""
+    monkeypatch.setenv("OMP_NUM_THREADS", "3")
+    assert 1 <= bench.usable_cores() <= 3
+    monkeypatch.delenv("OMP_NUM_THREADS")
+    assert bench.usable_cores() == len(os.sched_getaffinity(0))

@@ -715,7 +715,7 @@ def test_bench_line_for_several_gpus_runs_as_typed():
     detail = os.path.join(ROOT, "gpurun_out", "test_bench_detail.json") if os.path.isdir(os.path.join(ROOT, "gpurun_out")) \
         else os.path.join("/tmp", "test_bench_detail.json")
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--collectives", "threads", "--res", "256",
-                        "--steps", "3", "--warmup", "1"], capture_output=True, text=True, timeout=900, cwd=ROOT,
+                        "--steps", "3", "--warmup", "1", "--full"], capture_output=True, text=True, timeout=900, cwd=ROOT,
                        env=dict(os.environ, SMALLVCM_AMD_BENCH_DETAIL=detail))
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     lines = [l for l in r.stdout.splitlines() if l.strip()]
