@@ -59,7 +59,8 @@ enum {
     VCM_LIGHT_AREA = 0,        /* src/lights.hxx:112 */
     VCM_LIGHT_DIRECTIONAL = 1, /* src/lights.hxx:236 */
     VCM_LIGHT_POINT = 2,       /* src/lights.hxx:320 */
-    VCM_LIGHT_BACKGROUND = 3   /* src/lights.hxx:401 */
+    VCM_LIGHT_BACKGROUND = 3,  /* src/lights.hxx:401 */
+    VCM_LIGHT_ENVMAP = 4       /* an image around the scene (vcm_scene_desc3; DESIGN.md "Environment map") */
 };
 
 /* Tagged union of the public light fields (src/lights.hxx:229-232, 314-315,
@@ -67,7 +68,8 @@ enum {
  *   area:        p0,e1,e2, frame (mX,mY,mZ), intensity, invArea
  *   directional: frame, intensity
  *   point:       p0 = mPosition, intensity
- *   background:  intensity = mBackgroundColor, scale = mScale            */
+ *   background:  intensity = mBackgroundColor, scale = mScale
+ *   envmap:      scale (the radiance is texel * scale; the image comes with vcm_scene_desc3) */
 typedef struct vcm_light {
     int   type;
     float p0[3];
@@ -128,6 +130,23 @@ typedef struct vcm_scene_desc2 {
     float               invSceneRadiusSqr;
     vcm_camera          camera;
 } vcm_scene_desc2;
+
+/* An environment map: width x height linear RGB texels (3 floats each), row 0 = the TOP of the sky.  Equirectangular
+ * with +z up (the reference scenes' up axis): theta = acos z from +z, phi = atan2(y, x) in [0, 2 pi), u = phi / 2 pi
+ * (column), v = theta / pi (row); nearest texel, radiance = texel * the light's scale.  1 <= width <= 8192,
+ * 1 <= height <= 4096; every texel finite and >= 0, not all black. */
+typedef struct vcm_envmap {
+    int          width, height;
+    const float *rgb;             /* width * height * 3 floats */
+} vcm_envmap;
+
+/* Scene description, version 3: a version-2 scene whose background may be an image.  With `envmap` set, the scene
+ * holds exactly one light of type VCM_LIGHT_ENVMAP (vcm_make_envmap_light) and it is the backgroundLight (no other
+ * background light); with `envmap` NULL and no such light it is the version-2 scene.  The map is copied. */
+typedef struct vcm_scene_desc3 {
+    vcm_scene_desc2   base;
+    const vcm_envmap *envmap;
+} vcm_scene_desc3;
 
 /* VertexCM::AlgorithmType (src/vertexcm.hxx:182-204) -- same values */
 enum {
@@ -205,6 +224,14 @@ vcm_ctx *vcm_create_sharded(const vcm_scene_desc *scene, int algorithm,
 vcm_ctx *vcm_create2(const vcm_scene_desc2 *scene, int algorithm,
                      float radiusFactor, float radiusAlpha, int seed);
 vcm_ctx *vcm_create_sharded2(const vcm_scene_desc2 *scene, int algorithm,
+                             float radiusFactor, float radiusAlpha, int seed,
+                             int device, int rank, int worldSize);
+
+/* The same for a version-3 scene description (environment map).  NULL with vcm_last_error() for a bad map (size,
+ * non-finite or negative texels, zero total luminance) or a map without its light / a light without its map. */
+vcm_ctx *vcm_create3(const vcm_scene_desc3 *scene, int algorithm,
+                     float radiusFactor, float radiusAlpha, int seed);
+vcm_ctx *vcm_create_sharded3(const vcm_scene_desc3 *scene, int algorithm,
                              float radiusFactor, float radiusAlpha, int seed,
                              int device, int rank, int worldSize);
 
@@ -410,6 +437,8 @@ void vcm_make_area_light(const float *p0, const float *p1, const float *p2, cons
 void vcm_make_directional_light(const float *direction, const float *intensity, vcm_light *out);
 void vcm_make_point_light(const float *position, const float *intensity, vcm_light *out);
 void vcm_make_background_light(float scale, vcm_light *out);
+/* the light of a vcm_scene_desc3's environment map (radiance = texel * scale); it must be the scene's backgroundLight */
+void vcm_make_envmap_light(float scale, vcm_light *out);
 void vcm_make_material(vcm_material *out);
 int  vcm_make_camera(const float *position, const float *forward, const float *up, float horizontalFovDeg, int resX, int resY,
                      vcm_camera *out);
@@ -428,6 +457,16 @@ vcm_scene_file *vcm_scene_load(const char *path, int resX, int resY);
 const vcm_scene_desc2 *vcm_scene_file_desc(const vcm_scene_file *scene);
 void vcm_scene_file_free(vcm_scene_file *scene);
 const char *vcm_scene_load_error(void);
+/* The scene as a version-3 description: envmap set when the file has a `light envmap <file> <scale>` directive, NULL
+ * otherwise.  Points into the handle, like vcm_scene_file_desc. */
+const vcm_scene_desc3 *vcm_scene_file_desc3(const vcm_scene_file *scene);
+
+/* Environment maps from files: Radiance RGBE (.hdr: "#?RADIANCE" / "#?RGBE", FORMAT=32-bit_rle_rgbe, "-Y H +X W", flat
+ * or new-style run-length scanlines) or PFM (.pfm: "PF", either byte order; its bottom-up rows are flipped), picked by
+ * the file's magic.  Rows come out top first, as vcm_envmap wants them.  NULL on failure, with the reason in
+ * vcm_scene_load_error(); vcm_envmap_free releases the map and its texels. */
+vcm_envmap *vcm_envmap_load(const char *path);
+void vcm_envmap_free(vcm_envmap *map);
 
 #ifdef __cplusplus
 }

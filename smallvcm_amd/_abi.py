@@ -12,6 +12,7 @@ VCM_MERGE_RECORD_FLOATS = 13
 
 PRIM_TRIANGLE, PRIM_SPHERE = 0, 1
 LIGHT_AREA, LIGHT_DIRECTIONAL, LIGHT_POINT, LIGHT_BACKGROUND = 0, 1, 2, 3
+LIGHT_ENVMAP = 4
 
 # VertexCM::AlgorithmType (reference src/vertexcm.hxx:182-204)
 ALGO_LIGHT_TRACE, ALGO_PPM, ALGO_BPM, ALGO_BPT, ALGO_VCM = 0, 1, 2, 3, 4
@@ -73,6 +74,21 @@ class SceneDesc2(C.Structure):
                 ("backgroundLight", C.c_int),
                 ("sceneCenter", f3), ("sceneRadius", C.c_float), ("invSceneRadiusSqr", C.c_float),
                 ("camera", Camera)]
+
+
+class EnvMap(C.Structure):
+    """vcm_envmap: width x height RGB float texels, row 0 = the top (equirectangular, +z up; include/smallvcm_amd.h)"""
+    _fields_ = [("width", C.c_int), ("height", C.c_int), ("rgb", C.POINTER(C.c_float))]
+
+
+class SceneDesc3(C.Structure):
+    """vcm_scene_desc3: a version-2 scene and an optional environment map (the light: vcm_make_envmap_light, which
+    must be the backgroundLight).  Like SceneDesc2 the arrays are owned by the Python object that built it."""
+    _fields_ = [("base", SceneDesc2), ("envmap", C.POINTER(EnvMap))]
+
+    @property
+    def camera(self):
+        return self.base.camera
 
 
 class Stats(C.Structure):

@@ -126,6 +126,42 @@ VCM_HD void dm_sincosf_cold(float y, float &s, float &c) { dm_sincosf(y, s, c); 
 VCM_HD float dm_sinf(float x) { float s, c; dm_sincosf(x, s, c); return s; }
 VCM_HD float dm_cosf(float x) { float s, c; dm_sincosf(x, s, c); return c; }
 
+/* ---- atan2f / acosf of the environment map's lookup (vcm_core.h env_lookup) ----
+ * Not glibc's: the reference has no image lookup to agree with, so these only have to be the SAME bits on the host and
+ * the device, which a fixed sequence of binary32 + - x / and sqrt is (correctly rounded on both builds).
+ *   atan2(y, x)   a = min(|x|, |y|) / max(|x|, |y|) in [0, 1]; above tan(pi/8) t = (a - 1) / (a + 1) and pi/4 is added
+ *                 back, so the polynomial sees |t| <= tan(pi/8): atan t = t + t s P(s), s = t^2, P of degree 4 (a Chebyshev
+ *                 fit of atan(sqrt s) / sqrt s on [0, tan^2(pi/8)]); then the octant and the quadrant.
+ *   acos(z)       atan2(sqrt((1 - z)(1 + z)), z), z clamped to [-1, 1].
+ * Measured against binary64 over dense sweeps (tests/test_envmap.py keeps them under test): |error| <= 2.74e-7 rad for
+ * atan2 (2^22 angles on circles of radius 1e-30 .. 1e30), <= 2.88e-7 rad for acos (2^22 points in [-1, 1]) -- a few
+ * units in the last place of pi.  dm_atan2f(0, 0) = 0; the result lies in [-pi, pi]. */
+VCM_HD float dm_atan2f(float y, float x)
+{
+    const float ax = fabsf(x), ay = fabsf(y);
+    const float mx = ax < ay ? ay : ax, mn = ax < ay ? ax : ay;
+    if (mx == 0.f) return 0.f;
+    const float a = mn / mx;
+    const bool big = a > 0.41421356f;
+    const float t = big ? (a - 1.f) / (a + 1.f) : a;
+    const float s = t * t;
+    float p = -0.060332417488098145f;
+    p = p * s + 0.1057281419634819f;
+    p = p * s + -0.1423998326063156f;
+    p = p * s + 0.19998210668563843f;
+    p = p * s + -0.3333330750465393f;
+    float r = t + (t * s) * p;
+    if (big) r = r + 0.78539816f;
+    if (ay > ax) r = 1.57079633f - r;
+    if (x < 0.f) r = 3.14159265f - r;
+    return y < 0.f ? -r : r;
+}
+VCM_HD float dm_acosf(float z)
+{
+    z = z < -1.f ? -1.f : (z > 1.f ? 1.f : z);
+    return dm_atan2f(sqrtf((1.f - z) * (1.f + z)), z);
+}
+
 /* ---- powf (glibc e_powf.c: log2_inline, exp2_inline; __powf_log2_data, __exp2f_data) ---- */
 #define VCM_DM_LOG2_WORDS 32   /* {invc, logc} x 16 */
 #define VCM_DM_EXP2_WORDS 32

@@ -399,6 +399,13 @@ extern "C" void vcm_make_background_light(float scale, vcm_light *out)
     put3(out->intensity, mk3(135, 206, 250) / sp3(255.f));
     out->scale = scale;
 }
+extern "C" void vcm_make_envmap_light(float scale, vcm_light *out)
+{   /* the image comes with vcm_scene_desc3; intensity is not used */
+    memset(out, 0, sizeof(*out));
+    out->type = VCM_LIGHT_ENVMAP;
+    put3(out->intensity, sp3(1.f));
+    out->scale = scale;
+}
 extern "C" void vcm_make_material(vcm_material *out)
 {   /* Material::Reset materials.hxx:44-51 */
     reset_material(*out);

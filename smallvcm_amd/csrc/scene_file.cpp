@@ -16,6 +16,8 @@
 //       light point px py pz  r g b                      PointLight (lights.hxx:324-328)
 //       light directional dx dy dz  r g b                DirectionalLight (lights.hxx:239-243)
 //       light background scale                           BackgroundLight (lights.hxx:404-408)
+//       light envmap <file.hdr|file.pfm> scale           an environment map as the background (vcm_scene_desc3,
+//                                                        vcm_scene_file_desc3; the image: vcm_envmap_load below)
 //   .obj        v, f (triangles; polygons are fanned around their first vertex; v, v/vt, v/vt/vn, v//vn; negative
 //               = relative indices), usemtl, mtllib; everything else is skipped
 //   .mtl        newmtl, Kd -> mDiffuseReflectance, Ks + Ns -> mPhongReflectance / mPhongExponent (materials.hxx:54-65),
@@ -24,7 +26,16 @@
 //               a primitive with a material of its own whose mat2light entry names the light, and no reflectance,
 //               as the reference's light box (scene.hxx:333-361)
 // A bare .obj loads too (default camera: in front of the bounding sphere, looking along +y, z up, 45 degrees).
+//
+// Environment maps (vcm_envmap_load): Radiance RGBE -- header "#?RADIANCE" or "#?RGBE", FORMAT=32-bit_rle_rgbe (other
+// formats refused), a blank line, the resolution line "-Y H +X W" (the only orientation accepted: rows top-down), then
+// H scanlines, each flat (4 bytes per texel) or new-style run-length encoded (2, 2, W >> 8, W & 255, then the four
+// channels one after the other in runs); a texel is channel * 2^(E - 136), 0 for E = 0 -- or PFM: "PF", width, height
+// and a scale whose sign gives the byte order (< 0 little-endian), then 3 floats per texel, rows BOTTOM-up (flipped
+// here).  Sizes 1..8192 x 1..4096; a truncated file, a bad header or a texel that is not finite or negative is refused.
+#include <cctype>
 #include <cmath>
+#include <cstdint>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -41,11 +52,150 @@ struct vcm_scene_file {
     std::vector<int> mat2light;
     std::vector<vcm_light> lights;
     vcm_scene_desc2 desc;
+    vcm_envmap *envmap = NULL;        /* `light envmap` */
+    vcm_scene_desc3 desc3;
+    ~vcm_scene_file() { vcm_envmap_free(envmap); }
 };
 
 namespace {
 
 thread_local std::string g_sceneError;
+
+/* ---- environment maps ---- */
+bool env_fail(const std::string &what) { g_sceneError = what; return false; }
+bool env_size_ok(long w, long h) { return w >= 1 && w <= 8192 && h >= 1 && h <= 4096; }
+bool read_file(const std::string &path, std::vector<unsigned char> &buf)
+{
+    FILE *f = fopen(path.c_str(), "rb");
+    if (!f) return env_fail("cannot open " + path);
+    unsigned char tmp[65536];
+    size_t n;
+    while ((n = fread(tmp, 1, sizeof(tmp), f)) > 0) {
+        buf.insert(buf.end(), tmp, tmp + n);
+        if (buf.size() > ((size_t)8192 * 4096 * 12 + 4096)) { fclose(f); return env_fail(path + ": larger than any accepted map"); }
+    }
+    fclose(f);
+    return true;
+}
+/* the next '\n'-terminated line from pos (without the '\n'); false at the end of the data */
+bool next_line(const std::vector<unsigned char> &b, size_t &pos, std::string &line)
+{
+    if (pos >= b.size()) return false;
+    size_t e = pos;
+    while (e < b.size() && b[e] != '\n') e++;
+    if (e >= b.size()) return false;   /* a header line without its end: truncated */
+    line.assign((const char *)&b[pos], e - pos);
+    pos = e + 1;
+    return true;
+}
+bool load_rgbe(const std::string &path, const std::vector<unsigned char> &b, std::vector<float> &rgb, int &W, int &H)
+{
+    size_t pos = 0;
+    std::string line;
+    if (!next_line(b, pos, line) || (line.compare(0, 10, "#?RADIANCE") != 0 && line.compare(0, 6, "#?RGBE") != 0))
+        return env_fail(path + ": not a Radiance file (#?RADIANCE / #?RGBE)");
+    for (;;) {
+        if (!next_line(b, pos, line)) return env_fail(path + ": truncated header");
+        if (line.empty()) break;
+        if (line.compare(0, 7, "FORMAT=") == 0 && line != "FORMAT=32-bit_rle_rgbe") return env_fail(path + ": unsupported " + line);
+    }
+    if (!next_line(b, pos, line)) return env_fail(path + ": no resolution line");
+    long h = 0, w = 0;
+    char tail = 0;
+    if (sscanf(line.c_str(), "-Y %ld +X %ld %c", &h, &w, &tail) != 2) return env_fail(path + ": resolution line '" + line + "' is not -Y H +X W");
+    if (!env_size_ok(w, h)) return env_fail(path + ": size outside 1..8192 x 1..4096");
+    W = (int)w; H = (int)h;
+    rgb.assign((size_t)W * H * 3, 0.f);
+    std::vector<unsigned char> scan((size_t)W * 4);
+    for (int y = 0; y < H; y++) {
+        const bool rle = W >= 8 && W < 32768 && pos + 4 <= b.size() && b[pos] == 2 && b[pos + 1] == 2 && (b[pos + 2] & 0x80) == 0 &&
+                         ((int)b[pos + 2] << 8 | b[pos + 3]) == W;
+        if (rle) {
+            pos += 4;
+            for (int c = 0; c < 4; c++) {
+                for (int x = 0; x < W;) {
+                    if (pos >= b.size()) return env_fail(path + ": truncated scanline " + std::to_string(y));
+                    int n = b[pos++];
+                    if (n > 128) {
+                        n -= 128;
+                        if (x + n > W) return env_fail(path + ": run overflows scanline " + std::to_string(y));
+                        if (pos >= b.size()) return env_fail(path + ": truncated scanline " + std::to_string(y));
+                        const unsigned char v = b[pos++];
+                        for (int k = 0; k < n; k++) scan[(size_t)(x++) * 4 + c] = v;
+                    } else {
+                        if (n == 0 || x + n > W) return env_fail(path + ": bad run in scanline " + std::to_string(y));
+                        if (pos + n > b.size()) return env_fail(path + ": truncated scanline " + std::to_string(y));
+                        for (int k = 0; k < n; k++) scan[(size_t)(x++) * 4 + c] = b[pos++];
+                    }
+                }
+            }
+        } else {
+            if (pos + (size_t)W * 4 > b.size()) return env_fail(path + ": truncated scanline " + std::to_string(y));
+            memcpy(scan.data(), &b[pos], (size_t)W * 4);
+            pos += (size_t)W * 4;
+        }
+        for (int x = 0; x < W; x++) {
+            const unsigned char *t = &scan[(size_t)x * 4];
+            const float f = t[3] ? ldexpf(1.f, (int)t[3] - 136) : 0.f;
+            for (int c = 0; c < 3; c++) rgb[((size_t)y * W + x) * 3 + c] = t[3] ? (float)t[c] * f : 0.f;
+        }
+    }
+    return true;
+}
+bool load_pfm(const std::string &path, const std::vector<unsigned char> &b, std::vector<float> &rgb, int &W, int &H)
+{
+    /* "PF" whitespace width whitespace height whitespace scale, ONE whitespace character, then the data */
+    size_t pos = 2;
+    std::string tok[3];
+    for (int t = 0; t < 3; t++) {
+        while (pos < b.size() && isspace(b[pos])) pos++;
+        while (pos < b.size() && !isspace(b[pos]) && tok[t].size() < 32) tok[t] += (char)b[pos++];
+        if (tok[t].empty() || pos >= b.size()) return env_fail(path + ": truncated PFM header");
+    }
+    pos++;   /* the single whitespace character after the scale */
+    char *end = NULL;
+    const long w = strtol(tok[0].c_str(), &end, 10);
+    if (*end) return env_fail(path + ": bad PFM width");
+    const long h = strtol(tok[1].c_str(), &end, 10);
+    if (*end) return env_fail(path + ": bad PFM height");
+    const double scale = strtod(tok[2].c_str(), &end);
+    if (*end || scale == 0.0 || !std::isfinite(scale)) return env_fail(path + ": bad PFM scale");
+    if (!env_size_ok(w, h)) return env_fail(path + ": size outside 1..8192 x 1..4096");
+    W = (int)w; H = (int)h;
+    const size_t n = (size_t)W * H * 3;
+    if (b.size() < pos + n * 4) return env_fail(path + ": truncated PFM data");
+    const bool little = scale < 0.0;
+    rgb.assign(n, 0.f);
+    for (int y = 0; y < H; y++)
+        for (size_t k = 0; k < (size_t)W * 3; k++) {
+            const unsigned char *q = &b[pos + ((size_t)y * W * 3 + k) * 4];
+            const uint32_t u = little ? (uint32_t)q[0] | (uint32_t)q[1] << 8 | (uint32_t)q[2] << 16 | (uint32_t)q[3] << 24
+                                      : (uint32_t)q[3] | (uint32_t)q[2] << 8 | (uint32_t)q[1] << 16 | (uint32_t)q[0] << 24;
+            float f;
+            memcpy(&f, &u, 4);
+            rgb[(size_t)(H - 1 - y) * W * 3 + k] = f;   /* PFM rows run bottom-up */
+        }
+    return true;
+}
+vcm_envmap *envmap_load(const std::string &path)
+{
+    std::vector<unsigned char> b;
+    if (!read_file(path, b)) return NULL;
+    std::vector<float> rgb;
+    int W = 0, H = 0;
+    bool ok;
+    if (b.size() >= 3 && b[0] == 'P' && b[1] == 'F' && isspace(b[2])) ok = load_pfm(path, b, rgb, W, H);
+    else if (b.size() >= 2 && b[0] == '#' && b[1] == '?') ok = load_rgbe(path, b, rgb, W, H);
+    else ok = env_fail(path + ": neither a Radiance .hdr nor a .pfm file");
+    if (!ok) return NULL;
+    for (size_t i = 0; i < rgb.size(); i++)
+        if (!std::isfinite(rgb[i]) || rgb[i] < 0.f) { env_fail(path + ": texel " + std::to_string(i / 3) + " is not finite or negative"); return NULL; }
+    float *px = new float[rgb.size()];
+    memcpy(px, rgb.data(), rgb.size() * sizeof(float));
+    vcm_envmap *m = new vcm_envmap;
+    m->width = W; m->height = H; m->rgb = px;
+    return m;
+}
 
 struct MtlEntry { vcm_material m; float ke[3]; bool emissive; int index; /* in materials, -1: not added yet */ };
 
@@ -265,7 +415,16 @@ struct Loader {
                 if (kind == "point" && floats(p, x, 6)) vcm_make_point_light(x, x + 3, &l);
                 else if (kind == "directional" && floats(p, x, 6)) vcm_make_directional_light(x, x + 3, &l);
                 else if (kind == "background" && floats(p, x, 1)) { vcm_make_background_light(x[0], &l); background = (int)out->lights.size(); }
-                else { ok = fail(at + ": light point|directional x y z r g b, or light background scale"); break; }
+                else if (kind == "envmap") {
+                    const std::string file = word(p);
+                    if (file.empty() || !floats(p, x, 1)) { ok = fail(at + ": light envmap <file> scale"); break; }
+                    if (out->envmap) { ok = fail(at + ": a second env map"); break; }
+                    out->envmap = envmap_load(base + file);
+                    if (!out->envmap) { ok = fail(at + ": " + g_sceneError); break; }
+                    vcm_make_envmap_light(x[0], &l);
+                    background = (int)out->lights.size();
+                }
+                else { ok = fail(at + ": light point|directional x y z r g b, light background scale, or light envmap file scale"); break; }
                 out->lights.push_back(l);
             } else ok = fail(at + ": unknown directive " + key);
         }
@@ -291,6 +450,8 @@ struct Loader {
             camFov = 45.f;
         }
         if (vcm_make_camera(camPos, camFwd, camUp, camFov, resX, resY, &d.camera) != 0) return fail("bad camera");
+        out->desc3.base = d;
+        out->desc3.envmap = out->envmap;
         return true;
     }
 };
@@ -327,5 +488,26 @@ vcm_scene_file *vcm_scene_load(const char *path, int resX, int resY)
 const vcm_scene_desc2 *vcm_scene_file_desc(const vcm_scene_file *s) { return s ? &s->desc : NULL; }
 
 void vcm_scene_file_free(vcm_scene_file *s) { delete s; }
+
+const vcm_scene_desc3 *vcm_scene_file_desc3(const vcm_scene_file *s) { return s ? &s->desc3 : NULL; }
+
+vcm_envmap *vcm_envmap_load(const char *path)
+{
+    g_sceneError.clear();
+    if (!path) { g_sceneError = "vcm_envmap_load: path is NULL"; return NULL; }
+    try {   /* nothing may be thrown through the C-ABI */
+        return envmap_load(path);
+    } catch (...) {
+        try { g_sceneError = "vcm_envmap_load: out of memory"; } catch (...) {}
+        return NULL;
+    }
+}
+
+void vcm_envmap_free(vcm_envmap *m)
+{
+    if (!m) return;
+    delete[] m->rgb;
+    delete m;
+}
 
 } // extern "C"

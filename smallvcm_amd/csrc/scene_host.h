@@ -41,6 +41,11 @@ struct SceneHost {
     std::vector<BvhWide> wide;            /* one per inner node: both children's boxes (the ordered traversals, vcm_core.h) */
     std::vector<int> leafPrims;
     std::vector<LeafPrim> leafData;       /* the leaves' primitives in leaf order (what the traversals read) */
+    /* the environment map (scene_host_set_envmap; envW == 0: none) and its sampling tables, DScene::envW ... */
+    int envW = 0, envH = 0, envGuideW = 0, envGuideH = 0;
+    std::vector<F4> envTexels;
+    std::vector<float> envMarg, envCond;
+    std::vector<int> envMargGuide, envCondGuide;
 
     /* the view the device functions take, filled IN PLACE: the arrays are addressed relative to the DScene object
        itself (vcm_core.h), so `d` must stay where it is while it is in use (host emulation) */
@@ -55,6 +60,9 @@ struct SceneHost {
         d.offFastPairs = (const char *)fastPairs.data() - base; d.offFastSpheres = (const char *)fastSpheres.data() - base;
         d.offWide = (const char *)wide.data() - base; d.offLeafData = (const char *)leafData.data() - base;
         d.offFastRects = (const char *)fastRects.data() - base;
+        d.offEnvTexels = (const char *)envTexels.data() - base; d.offEnvMarg = (const char *)envMarg.data() - base;
+        d.offEnvCond = (const char *)envCond.data() - base; d.offEnvMargGuide = (const char *)envMargGuide.data() - base;
+        d.offEnvCondGuide = (const char *)envCondGuide.data() - base;
     }
     void fill_scalars(DScene &d) const
     {
@@ -72,6 +80,7 @@ struct SceneHost {
         for (int k = 0; k < 3; k++) d.fastCenter[k] = fastCenter[k];
         for (int k = 0; k < 3; k++) d.nFastRects[k] = nFastRects[k];
         d.fastGmax = fastGmax;
+        d.envW = envW; d.envH = envH; d.envGuideW = envGuideW; d.envGuideH = envGuideH;
         { const char *e = getenv("SMALLVCM_AMD_NO_RECTS"); if (e && e[0] == '1') d.nFastRects[0] = d.nFastRects[1] = d.nFastRects[2] = 0; }   /* measurement switch */
     }
 };
@@ -89,6 +98,14 @@ inline bool scene_host_check(const SceneHost &s, std::string &err)
     return true;
 }
 
+/* an env-map light comes with its image (scene_host_set_envmap): vcm_scene_desc / vcm_scene_desc2 cannot carry one */
+inline bool scene_host_no_envmap(const SceneHost &s, std::string &err)
+{
+    for (const vcm_light &l : s.lights)
+        if (l.type == VCM_LIGHT_ENVMAP) { err = "an env-map light needs its image: vcm_scene_desc3 / vcm_create3"; return false; }
+    return true;
+}
+
 inline bool scene_host_from_desc(const vcm_scene_desc &sc, SceneHost &s, std::string &err)
 {
     if (sc.nPrims < 0 || sc.nPrims > VCM_MAX_PRIMS || sc.nMaterials < 0 || sc.nMaterials > VCM_MAX_MATERIALS || sc.nLights < 1 ||
@@ -101,10 +118,10 @@ inline bool scene_host_from_desc(const vcm_scene_desc &sc, SceneHost &s, std::st
     for (int k = 0; k < 3; k++) s.sceneCenter[k] = sc.sceneCenter[k];
     s.sceneRadius = sc.sceneRadius; s.invSceneRadiusSqr = sc.invSceneRadiusSqr;
     s.camera = sc.camera;
-    return scene_host_check(s, err);
+    return scene_host_check(s, err) && scene_host_no_envmap(s, err);
 }
 
-inline bool scene_host_from_desc2(const vcm_scene_desc2 &sc, SceneHost &s, std::string &err)
+inline bool scene_host_copy_desc2(const vcm_scene_desc2 &sc, SceneHost &s, std::string &err)
 {
     if (sc.nPrims < 0 || sc.nMaterials < 1 || sc.nLights < 1 || (sc.nPrims > 0 && !sc.prims) || !sc.materials || !sc.mat2light || !sc.lights) {
         err = "vcm_scene_desc2: bad counts or NULL arrays"; return false;
@@ -118,6 +135,99 @@ inline bool scene_host_from_desc2(const vcm_scene_desc2 &sc, SceneHost &s, std::
     s.sceneRadius = sc.sceneRadius; s.invSceneRadiusSqr = sc.invSceneRadiusSqr;
     s.camera = sc.camera;
     return scene_host_check(s, err);
+}
+inline bool scene_host_from_desc2(const vcm_scene_desc2 &sc, SceneHost &s, std::string &err)
+{
+    return scene_host_copy_desc2(sc, s, err) && scene_host_no_envmap(s, err);
+}
+
+/* ---- the environment map's tables (vcm_core.h env_search / env_sample_dir / env_eval) ----
+ * In binary64, stored as binary32: texel = {rgb * scale, pdf_uv / (2 pi^2)} with pdf_uv = W H x the probability the two
+ * float CDFs actually give the texel (so the pdf is that of the sampler, not of the weights before rounding); CDFs start
+ * at 0 and end at exactly 1; a row of zero weight gets a uniform conditional CDF (it is never drawn).  The guide of a
+ * CDF of n entries has G + 1 entries, G = the power of two >= n: guide[k] = the largest r < n with cdf[r] <= k / G. */
+inline int scene_host_env_guide_size(int n) { int g = 1; while (g < n) g <<= 1; return g; }
+inline void scene_host_env_guide(const float *cdf, int n, int G, int *guide)
+{
+    int r = 0;
+    for (int k = 0; k < G; k++) {
+        const float x = (float)k / (float)G;
+        while (r + 1 < n && cdf[r + 1] <= x) r++;
+        guide[k] = r;
+    }
+    guide[G] = n - 1;
+}
+inline bool scene_host_set_envmap(SceneHost &s, const vcm_envmap *m, std::string &err)
+{
+    int envLight = -1, nBackground = 0;
+    for (size_t i = 0; i < s.lights.size(); i++) {
+        if (s.lights[i].type == VCM_LIGHT_ENVMAP) { if (envLight >= 0) { err = "more than one env-map light"; return false; } envLight = (int)i; }
+        if (s.lights[i].type == VCM_LIGHT_ENVMAP || s.lights[i].type == VCM_LIGHT_BACKGROUND) nBackground++;
+    }
+    if (!m && envLight < 0) return true;   /* a version-3 description without a map: the version-2 scene */
+    if (!m) { err = "an env-map light without a map (vcm_scene_desc3::envmap is NULL)"; return false; }
+    if (envLight < 0) { err = "a map without an env-map light (vcm_make_envmap_light)"; return false; }
+    if (envLight != s.backgroundLight) { err = "the env-map light must be the scene's backgroundLight"; return false; }
+    if (nBackground > 1) { err = "a scene has at most one background or env-map light"; return false; }
+    const int W = m->width, H = m->height;
+    if (W < 1 || W > 8192 || H < 1 || H > 4096) { err = "env map size outside 1..8192 x 1..4096"; return false; }
+    if (!m->rgb) { err = "env map without texels"; return false; }
+    const float scale = s.lights[envLight].scale;
+    if (!std::isfinite(scale) || !(scale > 0.f)) { err = "env-map light scale must be finite and > 0"; return false; }
+    const size_t n = (size_t)W * H;
+    std::vector<double> rowSum((size_t)H, 0.0), w(n);
+    double total = 0.0;
+    for (int i = 0; i < H; i++) {
+        const double st = std::sin(3.14159265358979323846 * (i + 0.5) / H);
+        for (int j = 0; j < W; j++) {
+            const float *t = m->rgb + ((size_t)i * W + j) * 3;
+            for (int c = 0; c < 3; c++)
+                if (!std::isfinite(t[c]) || t[c] < 0.f) { err = "env map texel not finite or negative"; return false; }
+            const double lum = 0.212671 * t[0] + 0.715160 * t[1] + 0.072169 * t[2];   /* Luminance, utils.hxx:36-41 */
+            w[(size_t)i * W + j] = lum * st;
+            rowSum[(size_t)i] += lum * st;
+        }
+        total += rowSum[(size_t)i];
+    }
+    if (!(total > 0.0) || !std::isfinite(total)) { err = "env map has zero total luminance"; return false; }
+    s.envW = W; s.envH = H;
+    s.envMarg.assign((size_t)H + 1, 0.f);
+    s.envCond.assign((size_t)H * (W + 1), 0.f);
+    double acc = 0.0;
+    for (int i = 0; i < H; i++) {
+        acc += rowSum[(size_t)i];
+        s.envMarg[(size_t)i + 1] = i + 1 == H ? 1.f : (float)(acc / total);
+        float *cond = &s.envCond[(size_t)i * (W + 1)];
+        double a = 0.0;
+        for (int j = 0; j < W; j++) {
+            a += w[(size_t)i * W + j];
+            cond[j + 1] = j + 1 == W ? 1.f : (rowSum[(size_t)i] > 0.0 ? (float)(a / rowSum[(size_t)i]) : (float)((double)(j + 1) / W));
+        }
+    }
+    s.envTexels.resize(n);
+    const double norm = (double)W * H / (2.0 * 3.14159265358979323846 * 3.14159265358979323846);
+    for (int i = 0; i < H; i++) {
+        const double pr = (double)s.envMarg[(size_t)i + 1] - s.envMarg[(size_t)i];
+        const float *cond = &s.envCond[(size_t)i * (W + 1)];
+        for (int j = 0; j < W; j++) {
+            const float *t = m->rgb + ((size_t)i * W + j) * 3;
+            const double p = pr * ((double)cond[j + 1] - cond[j]);
+            s.envTexels[(size_t)i * W + j] = mk4(t[0] * scale, t[1] * scale, t[2] * scale, (float)(p * norm));
+        }
+    }
+    s.envGuideH = scene_host_env_guide_size(H);
+    s.envGuideW = scene_host_env_guide_size(W);
+    s.envMargGuide.resize((size_t)s.envGuideH + 1);
+    scene_host_env_guide(s.envMarg.data(), H, s.envGuideH, s.envMargGuide.data());
+    s.envCondGuide.resize((size_t)H * (s.envGuideW + 1));
+    for (int i = 0; i < H; i++)
+        scene_host_env_guide(&s.envCond[(size_t)i * (W + 1)], W, s.envGuideW, &s.envCondGuide[(size_t)i * (s.envGuideW + 1)]);
+    return true;
+}
+
+inline bool scene_host_from_desc3(const vcm_scene_desc3 &sc, SceneHost &s, std::string &err)
+{
+    return scene_host_copy_desc2(sc.base, s, err) && scene_host_set_envmap(s, sc.envmap, err);
 }
 
 /* ---- brute-force list: consecutive triangles in pairs, fields interleaved (vcm_core.h TriPair) ---- */

@@ -114,14 +114,21 @@ static std::atomic<unsigned long long> g_threadCounter{0};
 static thread_local unsigned long long g_threadId = 0;
 static unsigned long long this_thread_id() { if (!g_threadId) g_threadId = ++g_threadCounter; return g_threadId; }
 
-/* Kernels that cast rays exist once per kind of scene (vcm_core.h SceneList / SceneBvh); the launch picks. */
-#define LAUNCH_SC(c, K, ...) do { if (!(c)->scene->nodes.empty()) { if ((c)->intPhong) hipLaunchKernelGGL((K<SceneBvh>), __VA_ARGS__); \
+/* Kernels that cast rays exist once per kind of scene (vcm_core.h SceneList / SceneBvh); the launch picks.  A scene with
+   an environment map takes the kinds that carry its branch (SceneRectsE / SceneListE / SceneBvhE). */
+#define LAUNCH_SC(c, K, ...) do { if ((c)->envMap) { if (!(c)->scene->nodes.empty()) hipLaunchKernelGGL((K<SceneBvhE>), __VA_ARGS__); \
+                                                     else if ((c)->intPhong && (c)->sceneRects) hipLaunchKernelGGL((K<SceneRectsE>), __VA_ARGS__); \
+                                                     else hipLaunchKernelGGL((K<SceneListE>), __VA_ARGS__); } \
+                                  else if (!(c)->scene->nodes.empty()) { if ((c)->intPhong) hipLaunchKernelGGL((K<SceneBvh>), __VA_ARGS__); \
                                                                      else hipLaunchKernelGGL((K<SceneBvhG>), __VA_ARGS__); } \
                                   else if (!(c)->intPhong) hipLaunchKernelGGL((K<SceneList>), __VA_ARGS__); \
                                   else if ((c)->sceneRects) hipLaunchKernelGGL((K<SceneRects>), __VA_ARGS__); \
                                   else if ((c)->sceneQuads) hipLaunchKernelGGL((K<SceneQuads>), __VA_ARGS__); \
                                   else hipLaunchKernelGGL((K<SceneList>), __VA_ARGS__); } while (0)
-#define LAUNCH_SC_MODE(c, K, M, ...) do { if (!(c)->scene->nodes.empty()) { if ((c)->intPhong) hipLaunchKernelGGL((K<M, SceneBvh>), __VA_ARGS__); \
+#define LAUNCH_SC_MODE(c, K, M, ...) do { if ((c)->envMap) { if (!(c)->scene->nodes.empty()) hipLaunchKernelGGL((K<M, SceneBvhE>), __VA_ARGS__); \
+                                                             else if ((c)->intPhong && (c)->sceneRects) hipLaunchKernelGGL((K<M, SceneRectsE>), __VA_ARGS__); \
+                                                             else hipLaunchKernelGGL((K<M, SceneListE>), __VA_ARGS__); } \
+                                          else if (!(c)->scene->nodes.empty()) { if ((c)->intPhong) hipLaunchKernelGGL((K<M, SceneBvh>), __VA_ARGS__); \
                                                                              else hipLaunchKernelGGL((K<M, SceneBvhG>), __VA_ARGS__); } \
                                           else if (!(c)->intPhong) hipLaunchKernelGGL((K<M, SceneList>), __VA_ARGS__); \
                                           else if ((c)->sceneRects) hipLaunchKernelGGL((K<M, SceneRects>), __VA_ARGS__); \
@@ -188,6 +195,7 @@ struct vcm_ctx : Scratch {
     int mergeKind;                    /* VCM_MERGE_* */
     bool sceneQuads;                  /* every triangle pair of the list shares its plane part: the SceneQuads kernels */
     bool sceneRects;                  /* ... and is an axis-aligned rectangle: the SceneRects kernels */
+    bool envMap;                      /* the scene's background is an environment map: the SceneRectsE / SceneListE / SceneBvhE kernels */
     bool intPhong;                    /* every Phong exponent in use is an integer in [1, 65536]: the kernels whose pow is the binary
                                          exponentiation alone (detmath.h); otherwise the SceneList / SceneBvhG kernels and the general merge */
     IterParams P;
@@ -461,14 +469,17 @@ static int ensure_device(vcm_ctx *c)
         HIPCHK(hipEventCreateWithFlags(&c->evGrid, hipEventDisableTiming));
         {   /* the scene in ONE device allocation: the DScene header, then the arrays it addresses by offset */
             const SceneHost &h = *c->scene;
-            struct Part { const void *src; size_t bytes; size_t off; } parts[13] = {
+            struct Part { const void *src; size_t bytes; size_t off; } parts[18] = {
                 { h.prims.data(), h.prims.size() * sizeof(vcm_prim), 0 }, { h.materials.data(), h.materials.size() * sizeof(vcm_material), 0 },
                 { h.mat2light.data(), h.mat2light.size() * sizeof(int), 0 }, { h.lights.data(), h.lights.size() * sizeof(vcm_light), 0 },
                 { h.ops.data(), h.ops.size() * sizeof(PrimOp), 0 }, { h.pairs.data(), h.pairs.size() * sizeof(TriPair), 0 },
                 { h.nodes.data(), h.nodes.size() * sizeof(BvhNode), 0 }, { h.leafPrims.data(), h.leafPrims.size() * sizeof(int), 0 },
                 { h.fastPairs.data(), h.fastPairs.size() * sizeof(FastPair), 0 }, { h.fastSpheres.data(), h.fastSpheres.size() * sizeof(FastSphere), 0 },
                 { h.wide.data(), h.wide.size() * sizeof(BvhWide), 0 }, { h.leafData.data(), h.leafData.size() * sizeof(LeafPrim), 0 },
-                { h.fastRects.data(), h.fastRects.size() * sizeof(FastRect), 0 } };
+                { h.fastRects.data(), h.fastRects.size() * sizeof(FastRect), 0 },
+                { h.envTexels.data(), h.envTexels.size() * sizeof(F4), 0 }, { h.envMarg.data(), h.envMarg.size() * sizeof(float), 0 },
+                { h.envCond.data(), h.envCond.size() * sizeof(float), 0 }, { h.envMargGuide.data(), h.envMargGuide.size() * sizeof(int), 0 },
+                { h.envCondGuide.data(), h.envCondGuide.size() * sizeof(int), 0 } };
             size_t total = (sizeof(DScene) + 255) & ~(size_t)255;
             for (Part &p : parts) { p.off = total; total += (p.bytes + 255) & ~(size_t)255; }
             if (dalloc(&c->dSceneBlob, total + 256)) return -1;
@@ -488,6 +499,8 @@ static int ensure_device(vcm_ctx *c)
             view.offNodes = (long long)parts[6].off; view.offLeafPrims = (long long)parts[7].off;
             view.offFastPairs = (long long)parts[8].off; view.offFastSpheres = (long long)parts[9].off;
             view.offWide = (long long)parts[10].off; view.offLeafData = (long long)parts[11].off; view.offFastRects = (long long)parts[12].off;
+            view.offEnvTexels = (long long)parts[13].off; view.offEnvMarg = (long long)parts[14].off; view.offEnvCond = (long long)parts[15].off;
+            view.offEnvMargGuide = (long long)parts[16].off; view.offEnvCondGuide = (long long)parts[17].off;
             c->dScene = reinterpret_cast<DScene *>(c->dSceneBlob);
             HIPCHK(hipMemcpy(c->dScene, &view, sizeof(DScene), hipMemcpyHostToDevice));
         }
@@ -735,6 +748,7 @@ static vcm_ctx *create_from_host(SceneHost *h, int algorithm, float radiusFactor
     if (!c) { delete h; fail("vcm_create", "out of host memory"); return NULL; }
     memset((void *)c, 0, sizeof(*c));
     c->scene = h;
+    c->envMap = h->envW > 0;
     scene_host_build_accel(*h, scene_host_force_bvh());
     /* VertexCM::VertexCM vertexcm.hxx:222-244 */
     switch (algorithm) {
@@ -807,6 +821,16 @@ vcm_ctx *vcm_create_sharded2(const vcm_scene_desc2 *scene, int algorithm, float 
     return create_from_host(h, algorithm, radiusFactor, radiusAlpha, seed, device, rank, worldSize);
 }
 
+vcm_ctx *vcm_create_sharded3(const vcm_scene_desc3 *scene, int algorithm, float radiusFactor, float radiusAlpha,
+                             int seed, int device, int rank, int worldSize)
+{
+    if (!scene) { fail("vcm_create3", "scene is NULL"); return NULL; }
+    SceneHost *h = new (std::nothrow) SceneHost();
+    std::string err;
+    if (!h || !scene_host_from_desc3(*scene, *h, err)) { delete h; fail("vcm_create3", err.c_str()); return NULL; }
+    return create_from_host(h, algorithm, radiusFactor, radiusAlpha, seed, device, rank, worldSize);
+}
+
 /* Which device a renderer-per-host-core host puts its next renderer on (vcm_next_device).  The reference's driver
  * builds one renderer per host core and runs them concurrently (smallvcm.cxx:61-72, :99-108): on a multi-GPU node the
  * drop-in deals them round-robin over the visible devices -- every GPU renders whole iterations of its renderers
@@ -850,6 +874,11 @@ vcm_ctx *vcm_create(const vcm_scene_desc *scene, int algorithm, float radiusFact
 vcm_ctx *vcm_create2(const vcm_scene_desc2 *scene, int algorithm, float radiusFactor, float radiusAlpha, int seed)
 {
     return vcm_create_sharded2(scene, algorithm, radiusFactor, radiusAlpha, seed, next_device(true), 0, 1);
+}
+
+vcm_ctx *vcm_create3(const vcm_scene_desc3 *scene, int algorithm, float radiusFactor, float radiusAlpha, int seed)
+{
+    return vcm_create_sharded3(scene, algorithm, radiusFactor, radiusAlpha, seed, next_device(true), 0, 1);
 }
 
 void vcm_destroy(vcm_ctx *c)

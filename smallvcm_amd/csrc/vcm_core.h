@@ -366,6 +366,7 @@ struct alignas(16) BvhWide {
 struct DScene {
     /* (as a type, see the kinds below: may the kernels assume that every Phong exponent is an integer in [1, 65536]?) */
     static constexpr bool kIntPhong = false;
+    static constexpr bool kEnvMap = false;
     int nPrims, nMaterials, nLights, backgroundLight;
     float sceneCenter[3], sceneRadius, invSceneRadiusSqr;
     vcm_camera camera;
@@ -378,6 +379,11 @@ struct DScene {
     int fastOnePlane;   /* every FastPair has flags bit 2: the loops then contain no per-entry branch (one burst of loads) */
     int nFastRects[3];  /* every FastPair is an axis-aligned rectangle: their FastRect view, grouped by normal axis (else 0, 0, 0) */
     float fastGmax;     /* the longest rectangle edge (enters an error bound) */
+    /* the environment map of a VCM_LIGHT_ENVMAP light (envW == 0: none), built by scene_host.h: envW x envH texels
+       {rgb * scale, pdf * sin(theta)}, row 0 = the top; the marginal CDF over the rows (envH + 1 floats), one conditional
+       CDF per row (envW + 1 floats each) and the guide tables of both (envGuideH + 1 / envGuideW + 1 ints per CDF) */
+    int envW, envH, envGuideW, envGuideH;
+    long long offEnvTexels, offEnvMarg, offEnvCond, offEnvMargGuide, offEnvCondGuide;
     template <class T> VCM_HD const T *at(long long off) const { return reinterpret_cast<const T *>(reinterpret_cast<const char *>(this) + off); }
     VCM_HD const vcm_prim *prims() const { return at<vcm_prim>(offPrims); }
     VCM_HD const vcm_material *materials() const { return at<vcm_material>(offMaterials); }
@@ -392,6 +398,11 @@ struct DScene {
     VCM_HD const FastRect *fastRects() const { return at<FastRect>(offFastRects); }
     VCM_HD const FastPair *fastPairs() const { return at<FastPair>(offFastPairs); }
     VCM_HD const FastSphere *fastSpheres() const { return at<FastSphere>(offFastSpheres); }
+    VCM_HD const F4 *envTexels() const { return at<F4>(offEnvTexels); }
+    VCM_HD const float *envMarg() const { return at<float>(offEnvMarg); }
+    VCM_HD const float *envCond() const { return at<float>(offEnvCond); }
+    VCM_HD const int *envMargGuide() const { return at<int>(offEnvMargGuide); }
+    VCM_HD const int *envCondGuide() const { return at<int>(offEnvCondGuide); }
 };
 /* Which of the two a scene carries, as a TYPE: every kernel that casts rays exists once per kind (the launch picks by
  * nNodes), so the brute-force kernels hold no traversal code and the BVH kernels no list loop.  Compiled together the
@@ -401,14 +412,29 @@ struct DScene {
  * pow(x, n) of the lobe is detmath.h's binary exponentiation and nothing else -- the kernels of such a kind hold no call
  * of the general powf where a lobe is only EVALUATED (the call's register constraints cost k_merge_walk its fourth wave
  * per SIMD: 135 registers against 120).  Scenes with other exponents take SceneList / SceneBvhG. */
-struct SceneList : DScene { static constexpr bool kBvh = false; static constexpr bool kOnePlane = false; static constexpr bool kRects = false; static constexpr bool kIntPhong = false; };
-struct SceneBvh : DScene { static constexpr bool kBvh = true; static constexpr bool kOnePlane = false; static constexpr bool kRects = false; static constexpr bool kIntPhong = true; };
-struct SceneBvhG : DScene { static constexpr bool kBvh = true; static constexpr bool kOnePlane = false; static constexpr bool kRects = false; static constexpr bool kIntPhong = false; };
+struct SceneList : DScene { static constexpr bool kBvh = false; static constexpr bool kOnePlane = false; static constexpr bool kRects = false; static constexpr bool kIntPhong = false; static constexpr bool kEnvMap = false; };
+struct SceneBvh : DScene { static constexpr bool kBvh = true; static constexpr bool kOnePlane = false; static constexpr bool kRects = false; static constexpr bool kIntPhong = true; static constexpr bool kEnvMap = false; };
+struct SceneBvhG : DScene { static constexpr bool kBvh = true; static constexpr bool kOnePlane = false; static constexpr bool kRects = false; static constexpr bool kIntPhong = false; static constexpr bool kEnvMap = false; };
 /* a list whose triangle pairs all share their plane part (FastPair::flags bit 2: axis-aligned quads, i.e. the reference's
    Cornell boxes): its kernels carry only that loop */
-struct SceneQuads : DScene { static constexpr bool kBvh = false; static constexpr bool kOnePlane = true; static constexpr bool kRects = false; static constexpr bool kIntPhong = true; };
+struct SceneQuads : DScene { static constexpr bool kBvh = false; static constexpr bool kOnePlane = true; static constexpr bool kRects = false; static constexpr bool kIntPhong = true; static constexpr bool kEnvMap = false; };
 /* a list whose triangle pairs are all axis-aligned rectangles (FastRect): the reference's own boxes */
-struct SceneRects : DScene { static constexpr bool kBvh = false; static constexpr bool kOnePlane = true; static constexpr bool kRects = true; static constexpr bool kIntPhong = true; };
+struct SceneRects : DScene { static constexpr bool kBvh = false; static constexpr bool kOnePlane = true; static constexpr bool kRects = true; static constexpr bool kIntPhong = true; static constexpr bool kEnvMap = false; };
+
+/* kEnvMap: the scene's background is an environment map (VCM_LIGHT_ENVMAP).  Its lookup and sampling exist only in the
+   kernels of these three kinds -- compiled into the others they would cost registers, i.e. waves -- and every scene with a
+   map is routed to them: the reference's boxes (axis-aligned rectangles, integer exponents) to SceneRectsE, any other
+   list to SceneListE, a BVH to SceneBvhE (general Phong exponents for both). */
+struct SceneRectsE : DScene { static constexpr bool kBvh = false; static constexpr bool kOnePlane = true; static constexpr bool kRects = true; static constexpr bool kIntPhong = true; static constexpr bool kEnvMap = true; };
+struct SceneListE : DScene { static constexpr bool kBvh = false; static constexpr bool kOnePlane = false; static constexpr bool kRects = false; static constexpr bool kIntPhong = false; static constexpr bool kEnvMap = true; };
+struct SceneBvhE : DScene { static constexpr bool kBvh = true; static constexpr bool kOnePlane = false; static constexpr bool kRects = false; static constexpr bool kIntPhong = false; static constexpr bool kEnvMap = true; };
+/* the host builds (emulation, known answers) carry the env-map branch in every kind: there it costs nothing, and the
+   emulation picks its kinds without looking at the lights */
+#if defined(__HIP_DEVICE_COMPILE__)
+#define VCM_ENV_KIND(S) (S::kEnvMap)
+#else
+#define VCM_ENV_KIND(S) true
+#endif
 
 /* ---- the scene's small tables in LDS ----
  * A lane's material, the primitive its ray ends on, the light it samples are GATHERS (the index is per lane): as global
@@ -1836,10 +1862,111 @@ VCM_HD vcm_light get_light(const DScene &sc, int idx)
     return scene_light(sc, idx);
 }
 
-VCM_HD V3 light_illuminate(const vcm_light &l, const DScene &sc, V3 recvPos, float rx, float ry,
+/* ---- the environment map (VCM_LIGHT_ENVMAP): BackgroundLight (:401-514) with an image where it says "replace this
+ * with image sampling / lookup" (:420, :450, :487).  Equirectangular, +z up: theta = acos z from +z, phi = atan2(y, x)
+ * in [0, 2 pi), u = phi / 2 pi, v = theta / pi, row 0 = the top; nearest texel.  Texels are drawn from a piecewise-
+ * constant 2D distribution (marginal CDF over the rows, conditional CDF per row, weight = luminance x sin theta at the row
+ * centre) and the point inside the texel uniformly in (u, v): pdf_W = pdf_uv / (2 pi^2 sin theta).  A texel stores that
+ * pdf times sin theta, so the lookup of ANY direction yields its radiance and pdf with one 16-byte load; Illuminate and
+ * Emit return the lookup of the direction they sampled -- the same function GetRadiance evaluates, so the two strategies'
+ * MIS pdfs agree bit for bit. */
+/* the largest r in [0, n-1] with cdf[r] <= x: guide[k] holds it for x = k / G, G a power of two (x G is exact), so the
+   answer for x in [k / G, (k + 1) / G) lies in [guide[k], guide[k + 1]] -- usually one texel, a few halvings at most */
+VCM_HD int env_search(const float *cdf, const int *guide, int G, float x)
+{
+    int k = (int)(x * (float)G);
+    k = k > G - 1 ? G - 1 : k;
+    int lo = guide[k], hi = guide[k + 1];
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (cdf[mid] <= x) lo = mid; else hi = mid - 1;
+    }
+    return lo;
+}
+/* the direction of (u, v) = the sampled texel + the fractions of r0 (row) and r1 (column) inside it; 2 floats */
+VCM_HD V3 env_sample_dir(const DScene &sc, float r0, float r1)
+{
+    const int W = sc.envW, H = sc.envH;
+    const float *marg = sc.envMarg();
+    const int row = env_search(marg, sc.envMargGuide(), sc.envGuideH, r0);
+    const float *cond = sc.envCond() + (size_t)row * (W + 1);
+    const int col = env_search(cond, sc.envCondGuide() + (size_t)row * (sc.envGuideW + 1), sc.envGuideW, r1);
+    const float dv = (r0 - marg[row]) / (marg[row + 1] - marg[row]);
+    const float du = (r1 - cond[col]) / (cond[col + 1] - cond[col]);
+    const float v = ((float)row + dv) / (float)H, u = ((float)col + du) / (float)W;
+    float st, ct, sp, cp;
+    dm_sincosf_cold(v * 3.14159265f, st, ct);
+    dm_sincosf_cold(u * 6.28318531f, sp, cp);
+    return mk3(st * cp, st * sp, ct);
+}
+/* radiance and solid-angle pdf of the texel around direction d (0, 0 at the poles and for black texels).  theta =
+   acos z is evaluated as atan2(sqrt(x^2 + y^2), z): the same angle, without acos's loss near the poles, where z rounds
+   to +-1 for a whole row of a large map */
+VCM_HD int env_texel_index(const DScene &sc, V3 d, float &rho)
+{
+    const int W = sc.envW, H = sc.envH;
+    rho = sqrtf(d.x * d.x + d.y * d.y);
+    const float theta = dm_atan2f(rho, d.z);
+    float phi = dm_atan2f(d.y, d.x);
+    if (phi < 0.f) phi = phi + 6.28318531f;
+    int col = (int)(phi * 0.15915494f * (float)W), row = (int)(theta * 0.31830989f * (float)H);
+    col = col > W - 1 ? W - 1 : (col < 0 ? 0 : col);
+    row = row > H - 1 ? H - 1 : (row < 0 ? 0 : row);
+    return row * W + col;
+}
+VCM_HD V3 env_eval(const DScene &sc, V3 d, float &pdfW)
+{
+    float rho;
+    const F4 t = sc.envTexels()[env_texel_index(sc, d, rho)];
+    pdfW = rho > 0.f ? t.w / rho : 0.f;
+    if (!(pdfW > 0.f)) { pdfW = 0.f; return sp3(0.f); }
+    return mk3(t.x, t.y, t.z);
+}
+VCM_HD V3 env_illuminate(const DScene &sc, float rx, float ry, V3 &dirToLight, float &distance, float &directPdfW,
+                         float &emissionPdfW, float &cosAtLight)
+{   /* BackgroundLight::Illuminate :410-437 with the image */
+    dirToLight = env_sample_dir(sc, rx, ry);
+    const V3 radiance = env_eval(sc, dirToLight, directPdfW);
+    distance = 1e36f;
+    emissionPdfW = directPdfW * concentric_disc_pdf_a() * sc.invSceneRadiusSqr;
+    cosAtLight = 1.f;
+    return radiance;
+}
+VCM_HD V3 env_emit(const DScene &sc, float dx, float dy, float px, float py, V3 &position, V3 &direction,
+                   float &emissionPdfW, float &directPdfA, float &cosThetaLight)
+{   /* BackgroundLight::Emit :439-481 with the image: the photon ARRIVES from the sampled d, so it travels along -d */
+    const V3 d = env_sample_dir(sc, dx, dy);
+    float directPdf;
+    const V3 radiance = env_eval(sc, d, directPdf);
+    /* a sample whose lookup lands on a black texel next to the one drawn (rounding at a texel edge) carries nothing;
+       a pdf of 1 keeps the light path's throughput (radiance / pdf) at zero instead of 0 / 0 */
+    if (directPdf == 0.f) directPdf = 1.f;
+    direction = -d;
+    float x, y;
+    sample_concentric_disc(px, py, x, y);
+    Frame frame;
+    frame_from_z(frame, direction);
+    position = ld3(sc.sceneCenter) + sc.sceneRadius * (-direction + frame.mX * x + frame.mY * y);
+    emissionPdfW = directPdf * concentric_disc_pdf_a() * sc.invSceneRadiusSqr;
+    directPdfA = directPdf;
+    cosThetaLight = 1.f;
+    return radiance;
+}
+VCM_HD V3 env_get_radiance(const DScene &sc, V3 rayDir, float &directPdfA, float &emissionPdfW)
+{   /* BackgroundLight::GetRadiance :483-504 with the image */
+    const V3 radiance = env_eval(sc, rayDir, directPdfA);
+    emissionPdfW = directPdfA * concentric_disc_pdf_a() * sc.invSceneRadiusSqr;
+    return radiance;
+}
+
+/* S = the scene's kind: only the kinds with kEnvMap hold the env-map branch (VCM_ENV_KIND) */
+template <class S>
+VCM_HD V3 light_illuminate(const vcm_light &l, const S &sc, V3 recvPos, float rx, float ry,
                            V3 &dirToLight, float &distance, float &directPdfW, float &emissionPdfW,
                            float &cosAtLight)
 {
+    if constexpr (VCM_ENV_KIND(S))
+        if (l.type == VCM_LIGHT_ENVMAP) return env_illuminate(sc, rx, ry, dirToLight, distance, directPdfW, emissionPdfW, cosAtLight);
     if (l.type == VCM_LIGHT_AREA) {   /* AreaLight::Illuminate :129-166 */
         float u, v;
         sample_uniform_triangle(rx, ry, u, v);
@@ -1880,9 +2007,12 @@ VCM_HD V3 light_illuminate(const vcm_light &l, const DScene &sc, V3 recvPos, flo
     }
 }
 
-VCM_HD V3 light_emit(const vcm_light &l, const DScene &sc, float dx, float dy, float px, float py,
+template <class S>
+VCM_HD V3 light_emit(const vcm_light &l, const S &sc, float dx, float dy, float px, float py,
                      V3 &position, V3 &direction, float &emissionPdfW, float &directPdfA, float &cosThetaLight)
 {
+    if constexpr (VCM_ENV_KIND(S))
+        if (l.type == VCM_LIGHT_ENVMAP) return env_emit(sc, dx, dy, px, py, position, direction, emissionPdfW, directPdfA, cosThetaLight);
     if (l.type == VCM_LIGHT_AREA) {   /* AreaLight::Emit :168-198 */
         float u, v;
         sample_uniform_triangle(px, py, u, v);
@@ -1926,9 +2056,12 @@ VCM_HD V3 light_emit(const vcm_light &l, const DScene &sc, float dx, float dy, f
     }
 }
 
-VCM_HD V3 light_get_radiance(const vcm_light &l, const DScene &sc, V3 rayDir,
+template <class S>
+VCM_HD V3 light_get_radiance(const vcm_light &l, const S &sc, V3 rayDir,
                              float &directPdfA, float &emissionPdfW)
 {
+    if constexpr (VCM_ENV_KIND(S))
+        if (l.type == VCM_LIGHT_ENVMAP) return env_get_radiance(sc, rayDir, directPdfA, emissionPdfW);
     if (l.type == VCM_LIGHT_AREA) {   /* :200-221 */
         const float cosOutL = smax(0.f, dot(ld3(l.frameZ), -rayDir));
         if (cosOutL == 0.f) return sp3(0.f);
@@ -2005,7 +2138,8 @@ VCM_HD bool sample_scattering(const S &sc, const IterParams &P, bool lightSample
 /* ================= light sub-path (vertexcm.hxx:321-396) ============== */
 
 /* GenerateLightSample :816-858 */
-VCM_HD void generate_light_sample(const DScene &sc, const IterParams &P, PathRng &rng, SubPathState &st)
+template <class S>
+VCM_HD void generate_light_sample(const S &sc, const IterParams &P, PathRng &rng, SubPathState &st)
 {
     const int lightCount = sc.nLights;
     const float lightPickProb = 1.f / lightCount;
@@ -2101,7 +2235,8 @@ struct LightPath {
 struct LaneBox { float mn[3], mx[3]; };
 VCM_HD void lane_box_init(LaneBox &b) { for (int k = 0; k < 3; k++) { b.mn[k] = 3.0e38f; b.mx[k] = -3.0e38f; } }
 
-VCM_HD void light_path_begin(const DScene &sc, const IterParams &P, LightPath &lp, int localPath)
+template <class S>
+VCM_HD void light_path_begin(const S &sc, const IterParams &P, LightPath &lp, int localPath)
 {
     lp.lp = localPath;
     lp.nStored = 0;
@@ -2193,7 +2328,8 @@ VCM_HD void connect_stored_vertex_to_camera(const SC &sc, const IterParams &P, c
 /* ================= camera sub-path (vertexcm.hxx:415-545) ============= */
 
 /* GetLightRadiance :617-658 */
-VCM_HD V3 get_light_radiance(const DScene &sc, const IterParams &P, const vcm_light &light,
+template <class S>
+VCM_HD V3 get_light_radiance(const S &sc, const IterParams &P, const vcm_light &light,
                              const SubPathState &st, V3 rayDir)
 {
     const int lightCount = sc.nLights;

@@ -10,6 +10,7 @@
 //              [--res W H] [--seed S] [--minlen A] [--maxlen B]
 //              [--renderers R] [--radius-factor F] [--radius-alpha A]
 //              [--device D] [--strict] [--warmup W] [-o out.pfm] [--json] [--scene-file f.vcmscene|f.obj]
+//              [--envmap f.hdr|f.pfm [--envmap-scale S]]
 //              [--gpus N [--shards S] [--inflight K] [--devices 0,1,..] [--collectives rccl|threads] [--same-window]]
 //
 // --gpus N: the multi-GPU host (vcm_farm.hpp): N ranks = N host threads, one per GPU, cut into N / S groups; a
@@ -17,6 +18,9 @@
 // renderers take turns on a group, one RCCL all-reduce of the framebuffers at read-out.  --shards 1 = one renderer per
 // GPU (the reference's own iteration-parallel scheme).  --collectives threads replaces RCCL by an in-process
 // stand-in so that several ranks can share one GPU (tests; RCCL refuses two ranks on one device).
+//
+// --envmap: the built-in scene's BackgroundLight (scene 3) replaced by an environment map (vcm_envmap_load,
+// radiance = texel * S, S = 1 by default) over the same geometry; a scene file names its map itself (`light envmap`).
 //
 // -s / -a / -i keep the meaning they have in the reference's CLI
 // (src/config.hxx:246-395; scenes = g_SceneConfigs[0..3], :146-151).
@@ -68,7 +72,8 @@ int main(int argc, char **argv)
     std::vector<float> rankMs;
     std::vector<int> devices;
     float radiusFactor = 0.003f, radiusAlpha = 0.75f;
-    std::string out, algoName = "vcm", sceneFile;
+    std::string out, algoName = "vcm", sceneFile, envFile;
+    float envScale = 1.f;
     for (int i = 1; i < argc; i++) {
         const std::string a(argv[i]);
         auto need = [&](int n) { if (i + n >= argc) { fprintf(stderr, "vcm_render: %s needs %d argument(s)\n", a.c_str(), n); exit(2); } };
@@ -92,6 +97,8 @@ int main(int argc, char **argv)
         else if (a == "--devices") { need(1); for (const char *p = argv[++i]; *p;) { char *e; devices.push_back((int)strtol(p, &e, 10)); p = (*e == ',') ? e + 1 : e; if (e == p && *p) break; } }
         else if (a == "--same-window") sameWindow = 1;   // benchmark schedule: every renderer runs the iteration indices warmup ..
         else if (a == "--scene-file") { need(1); sceneFile = argv[++i]; }   // instead of -s: OBJ + MTL / .vcmscene (vcm_scene_load)
+        else if (a == "--envmap") { need(1); envFile = argv[++i]; }
+        else if (a == "--envmap-scale") { need(1); envScale = (float)atof(argv[++i]); }
         else if (a == "--strict") strict = 1;
         else if (a == "--json") json = 1;
         else { fprintf(stderr, "vcm_render: unknown option %s (see the header of vcm_render.cpp)\n", a.c_str()); return 2; }
@@ -104,11 +111,42 @@ int main(int argc, char **argv)
     vcm_scene_desc scene;
     if (vcm_scene_cornell(resX, resY, vcm_scene_config_mask(sceneID), &scene)) return die("vcm_scene_cornell");
     vcm_scene_file *loaded = NULL;   // --scene-file: a version-2 description (any number of primitives, BVH)
+    const vcm_scene_desc3 *envScene = NULL;   // a scene with an environment map (--envmap, or a scene file's `light envmap`)
     if (!sceneFile.empty()) {
         loaded = vcm_scene_load(sceneFile.c_str(), resX, resY);
         if (!loaded) { fprintf(stderr, "vcm_render: %s\n", vcm_scene_load_error()); return 2; }
         if (gpus > 0) { fprintf(stderr, "vcm_render: --scene-file with --gpus is not supported (the farm takes the built-in scenes)\n"); return 2; }
+        if (vcm_scene_file_desc3(loaded)->envmap) envScene = vcm_scene_file_desc3(loaded);
     }
+    // --envmap: the built-in scene as a version-3 description whose background light is the map
+    vcm_envmap *envmap = NULL;
+    std::vector<vcm_light> envLights;
+    vcm_scene_desc3 envDesc;
+    if (!envFile.empty()) {
+        if (gpus > 0) { fprintf(stderr, "vcm_render: --envmap with --gpus is not supported (the farm takes the built-in scenes)\n"); return 2; }
+        if (loaded) { fprintf(stderr, "vcm_render: --envmap with --scene-file: name the map in the scene file (light envmap)\n"); return 2; }
+        if (scene.backgroundLight < 0) { fprintf(stderr, "vcm_render: --envmap replaces the scene's background light; scene %d has none (scene 3 has)\n", sceneID); return 2; }
+        envmap = vcm_envmap_load(envFile.c_str());
+        if (!envmap) { fprintf(stderr, "vcm_render: %s\n", vcm_scene_load_error()); return 2; }
+        envLights.assign(scene.lights, scene.lights + scene.nLights);
+        vcm_make_envmap_light(envScale, &envLights[(size_t)scene.backgroundLight]);
+        memset(&envDesc, 0, sizeof(envDesc));
+        vcm_scene_desc2 &b = envDesc.base;
+        b.nPrims = scene.nPrims; b.prims = scene.prims;
+        b.nMaterials = scene.nMaterials; b.materials = scene.materials; b.mat2light = scene.mat2light;
+        b.nLights = scene.nLights; b.lights = envLights.data();
+        b.backgroundLight = scene.backgroundLight;
+        memcpy(b.sceneCenter, scene.sceneCenter, sizeof(b.sceneCenter));
+        b.sceneRadius = scene.sceneRadius; b.invSceneRadiusSqr = scene.invSceneRadiusSqr;
+        b.camera = scene.camera;
+        envDesc.envmap = envmap;
+        envScene = &envDesc;
+    }
+    auto create = [&](int s) {
+        return envScene ? vcm_create_sharded3(envScene, algorithm, radiusFactor, radiusAlpha, s, device, 0, 1)
+             : loaded ? vcm_create_sharded2(vcm_scene_file_desc(loaded), algorithm, radiusFactor, radiusAlpha, s, device, 0, 1)
+                      : vcm_create_sharded(&scene, algorithm, radiusFactor, radiusAlpha, s, device, 0, 1);
+    };
 
     const size_t n3 = (size_t)resX * resY * 3;
     std::vector<float> fb(n3, 0.f), tmp(n3);
@@ -141,15 +179,13 @@ int main(int argc, char **argv)
     // render(): one renderer per "thread", seed base + i (smallvcm.cxx:61-72)
     r.assign((size_t)renderers, (vcm_ctx *)NULL);
     for (int g = 0; g < renderers; g++) {
-        r[g] = loaded ? vcm_create_sharded2(vcm_scene_file_desc(loaded), algorithm, radiusFactor, radiusAlpha, seed + g, device, 0, 1)
-                      : vcm_create_sharded(&scene, algorithm, radiusFactor, radiusAlpha, seed + g, device, 0, 1);
+        r[g] = create(seed + g);
         if (!r[g]) return die("vcm_create");
         if (strict && vcm_set_strict_order(r[g], 1)) return die("vcm_set_strict_order");
     }
     // untimed warm-up on a throw-away renderer: allocations, first-launch costs
     if (warmup > 0) {
-        vcm_ctx *w = loaded ? vcm_create_sharded2(vcm_scene_file_desc(loaded), algorithm, radiusFactor, radiusAlpha, seed, device, 0, 1)
-                            : vcm_create_sharded(&scene, algorithm, radiusFactor, radiusAlpha, seed, device, 0, 1);
+        vcm_ctx *w = create(seed);
         if (!w) return die("vcm_create");
         for (int it = 0; it < warmup; it++) if (vcm_run_iteration(w, it, minLen, maxLen)) return die("vcm_run_iteration");
         vcm_synchronize(w);
@@ -235,6 +271,7 @@ int main(int argc, char **argv)
     }
     for (size_t g = 0; g < r.size(); g++) vcm_destroy(r[g]);
     vcm_scene_file_free(loaded);
+    vcm_envmap_free(envmap);
     double mean[3] = { 0, 0, 0 };
     for (size_t i = 0; i < n3; i++) mean[i % 3] += fb[i];
     const double paths = (algorithm == VCM_ALGO_PATH_TRACE || algorithm == VCM_ALGO_EYE_LIGHT ? 1.0 : 2.0) * resX * resY * iterations;

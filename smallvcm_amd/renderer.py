@@ -21,7 +21,7 @@ import os
 
 import numpy as np
 
-from ._abi import (SceneDesc, SceneDesc2, Stats, SCENE_CONFIGS, VCM_MERGE_RECORD_FLOATS, ALGO_LIGHT_TRACE, ALGO_PPM, ALGO_BPM,
+from ._abi import (SceneDesc, SceneDesc2, SceneDesc3, Stats, SCENE_CONFIGS, VCM_MERGE_RECORD_FLOATS, ALGO_LIGHT_TRACE, ALGO_PPM, ALGO_BPM,
                    ALGO_BPT, ALGO_VCM)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -56,6 +56,9 @@ def load_library(require_gpu=True):
                                          C.c_int, C.c_int]
         L.vcm_create_sharded2.restype = vp
         L.vcm_create_sharded2.argtypes = [C.POINTER(SceneDesc2), C.c_int, C.c_float, C.c_float, C.c_int, C.c_int,
+                                          C.c_int, C.c_int]
+        L.vcm_create_sharded3.restype = vp
+        L.vcm_create_sharded3.argtypes = [C.POINTER(SceneDesc3), C.c_int, C.c_float, C.c_float, C.c_int, C.c_int,
                                           C.c_int, C.c_int]
         L.vcm_destroy.argtypes = [vp]
         L.vcm_destroy.restype = None
@@ -135,7 +138,8 @@ class HipBackend:
         self.resx = int(scene.camera.resolution[0])
         self.resy = int(scene.camera.resolution[1])
         self.N = self.resx * self.resy
-        create = self.L.vcm_create_sharded2 if isinstance(scene, SceneDesc2) else self.L.vcm_create_sharded
+        create = (self.L.vcm_create_sharded3 if isinstance(scene, SceneDesc3) else
+                  self.L.vcm_create_sharded2 if isinstance(scene, SceneDesc2) else self.L.vcm_create_sharded)
         self.ctx = create(C.byref(scene), algorithm, radius_factor, radius_alpha, seed, device, rank, world)
         if not self.ctx:
             raise RuntimeError("smallvcm_amd: vcm_create failed: %s" % self.L.vcm_last_error().decode())

@@ -12,7 +12,9 @@ vcm_make_camera, ... each of which computes the derived members exactly as the r
 """
 import ctypes as C
 
-from ._abi import Camera, Light, Material, Prim, SceneDesc2
+import numpy as np
+
+from ._abi import Camera, EnvMap, Light, Material, Prim, SceneDesc2, SceneDesc3
 
 
 def _f3(v):
@@ -37,6 +39,8 @@ class SceneBuilder:
         L.vcm_make_point_light.restype = None
         L.vcm_make_background_light.argtypes = [C.c_float, C.POINTER(Light)]
         L.vcm_make_background_light.restype = None
+        L.vcm_make_envmap_light.argtypes = [C.c_float, C.POINTER(Light)]
+        L.vcm_make_envmap_light.restype = None
         L.vcm_make_material.argtypes = [C.POINTER(Material)]
         L.vcm_make_material.restype = None
         L.vcm_make_camera.argtypes = [fp, fp, fp, C.c_float, C.c_int, C.c_int, C.POINTER(Camera)]
@@ -44,6 +48,7 @@ class SceneBuilder:
         L.vcm_make_scene_sphere.restype = None
         self.prims, self.materials, self.mat2light, self.lights = [], [], [], []
         self.background = -1
+        self.envmap = None
 
     # ---- materials (materials.hxx:33-65) ----
     def material(self, diffuse=(0, 0, 0), phong=(0, 0, 0), exponent=1.0, mirror=(0, 0, 0), ior=-1.0):
@@ -97,6 +102,18 @@ class SceneBuilder:
         self.lights.append(light)
         self.background = len(self.lights) - 1
 
+    def envmap_light(self, image, scale=1.0):
+        """an environment map as the scene's background: image = float32 [H, W, 3], row 0 = the top of the sky
+        (equirectangular, +z up; include/smallvcm_amd.h vcm_envmap).  build() then returns a SceneDesc3."""
+        img = np.ascontiguousarray(image, dtype=np.float32)
+        if img.ndim != 3 or img.shape[2] != 3:
+            raise ValueError("envmap_light: image must be [H, W, 3]")
+        light = Light()
+        self.L.vcm_make_envmap_light(float(scale), C.byref(light))
+        self.lights.append(light)
+        self.background = len(self.lights) - 1
+        self.envmap = img
+
     # ---- the description ----
     def build(self, position, forward, up, fov_deg, resx, resy):
         d = SceneDesc2()
@@ -114,4 +131,13 @@ class SceneBuilder:
         if self.L.vcm_make_camera(_f3(position), _f3(forward), _f3(up), float(fov_deg), int(resx), int(resy), C.byref(d.camera)) != 0:
             raise ValueError("bad camera")
         d._keep = (prims, mats, m2l, lights)   # the arrays live as long as the description
-        return d
+        if self.envmap is None:
+            return d
+        d3 = SceneDesc3()
+        d3.base = d
+        m = EnvMap()
+        m.height, m.width = int(self.envmap.shape[0]), int(self.envmap.shape[1])
+        m.rgb = self.envmap.ctypes.data_as(C.POINTER(C.c_float))
+        d3.envmap = C.pointer(m)
+        d3._keep = (d._keep, self.envmap, m)
+        return d3
