@@ -148,6 +148,22 @@ typedef struct vcm_scene_desc3 {
     const vcm_envmap *envmap;
 } vcm_scene_desc3;
 
+/* A thin lens in place of the pinhole (DESIGN.md "Thin lens"): a disc of radius apertureRadius (world units, >= 0)
+ * centred at the camera position and perpendicular to its forward axis, focused on the plane at focusDistance (world
+ * units, > 0) along forward.  Every raster sample keeps its pixel; its ray starts at a uniformly drawn lens point and
+ * passes through the sample's point on the focus plane.  apertureRadius == 0 is the pinhole. */
+typedef struct vcm_thin_lens {
+    float apertureRadius;
+    float focusDistance;
+} vcm_thin_lens;
+
+/* Scene description, version 4: a version-3 scene (environment map or not) seen through an optional thin lens.
+ * `lens` NULL, or an apertureRadius of 0, renders exactly what vcm_create3 renders.  The lens is copied. */
+typedef struct vcm_scene_desc4 {
+    vcm_scene_desc3      base;
+    const vcm_thin_lens *lens;
+} vcm_scene_desc4;
+
 /* VertexCM::AlgorithmType (src/vertexcm.hxx:182-204) -- same values */
 enum {
     VCM_ALGO_LIGHT_TRACE = 0,
@@ -232,6 +248,14 @@ vcm_ctx *vcm_create_sharded2(const vcm_scene_desc2 *scene, int algorithm,
 vcm_ctx *vcm_create3(const vcm_scene_desc3 *scene, int algorithm,
                      float radiusFactor, float radiusAlpha, int seed);
 vcm_ctx *vcm_create_sharded3(const vcm_scene_desc3 *scene, int algorithm,
+                             float radiusFactor, float radiusAlpha, int seed,
+                             int device, int rank, int worldSize);
+
+/* The same for a version-4 scene description (thin lens).  NULL with vcm_last_error() for a bad lens (apertureRadius
+ * negative or not finite; focusDistance <= 0 or not finite) or a bad version-3 scene. */
+vcm_ctx *vcm_create4(const vcm_scene_desc4 *scene, int algorithm,
+                     float radiusFactor, float radiusAlpha, int seed);
+vcm_ctx *vcm_create_sharded4(const vcm_scene_desc4 *scene, int algorithm,
                              float radiusFactor, float radiusAlpha, int seed,
                              int device, int rank, int worldSize);
 
@@ -448,7 +472,7 @@ void vcm_make_scene_sphere(const vcm_prim *prims, int nPrims, float *center3, fl
  * scene.hxx:132-398, is the only way a scene comes into being).  vcm_scene_load reads a `.vcmscene` text file --
  * directives processed in order: `obj <file>` (Wavefront OBJ triangles with their MTL library: Kd / Ks+Ns / illum /
  * Ni -> Material, Ke -> one AreaLight per triangle as in scene.hxx:333-361), `sphere`, `camera`, `light
- * point|directional|background`, `mtllib` -- or a bare `.obj` (default camera), and builds the version-2 description
+ * point|directional|background|envmap`, `lens`, `mtllib` -- or a bare `.obj` (default camera), and builds the version-2 description
  * with the vcm_make_* constructors above; smallvcm_amd/csrc/scene_file.cpp documents the format.  The description
  * points into the handle: keep it until the renderers are created (vcm_create2 copies).  NULL on failure, with the
  * reason in vcm_scene_load_error(). */
@@ -460,6 +484,9 @@ const char *vcm_scene_load_error(void);
 /* The scene as a version-3 description: envmap set when the file has a `light envmap <file> <scale>` directive, NULL
  * otherwise.  Points into the handle, like vcm_scene_file_desc. */
 const vcm_scene_desc3 *vcm_scene_file_desc3(const vcm_scene_file *scene);
+/* The scene as a version-4 description: lens set when the file has a `lens <apertureRadius> <focusDistance>`
+ * directive, NULL otherwise; its base is vcm_scene_file_desc3's.  Points into the handle, like vcm_scene_file_desc. */
+const vcm_scene_desc4 *vcm_scene_file_desc4(const vcm_scene_file *scene);
 
 /* Environment maps from files: Radiance RGBE (.hdr: "#?RADIANCE" / "#?RGBE", FORMAT=32-bit_rle_rgbe, "-Y H +X W", flat
  * or new-style run-length scanlines) or PFM (.pfm: "PF", either byte order; its bottom-up rows are flipped), picked by

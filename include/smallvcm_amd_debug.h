@@ -57,7 +57,10 @@ enum {
     VCM_KAT_LIGHT_RADIANCE = 6,   /* in: light, rayDir, hitPoint -> radiance, directPdfA, emissionPdfW */
     VCM_KAT_CAMERA = 7,           /* in: raster x, y, world point -> ray dir, raster of the point, CheckRaster
                                                                                                              camera.hxx:95-117 */
-    VCM_KAT_OPS = 8
+    VCM_KAT_LENS = 8,             /* in: raster x, y, lens sample u1, u2, world point -> ray origin, ray dir, cameraPdfW, raster
+                                     of the world point through that lens point, valid (1: in front of the lens); needs a
+                                     context with a thin lens (vcm_create4)                       DESIGN.md "Thin lens" */
+    VCM_KAT_OPS = 9
 };
 int vcm_debug_kat(vcm_ctx *ctx, int op, int n, const float *in, float *out);
 

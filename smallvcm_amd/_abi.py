@@ -91,6 +91,22 @@ class SceneDesc3(C.Structure):
         return self.base.camera
 
 
+class ThinLens(C.Structure):
+    """vcm_thin_lens: aperture radius (>= 0; 0 = the pinhole) and focus distance along the camera's forward axis (> 0),
+    world units (include/smallvcm_amd.h)"""
+    _fields_ = [("apertureRadius", C.c_float), ("focusDistance", C.c_float)]
+
+
+class SceneDesc4(C.Structure):
+    """vcm_scene_desc4: a version-3 scene and an optional thin lens.  Like SceneDesc2 the arrays are owned by the
+    Python object that built it."""
+    _fields_ = [("base", SceneDesc3), ("lens", C.POINTER(ThinLens))]
+
+    @property
+    def camera(self):
+        return self.base.base.camera
+
+
 class Stats(C.Structure):
     _fields_ = [("lightVertices", C.c_longlong), ("gridVertices", C.c_longlong),
                 ("lightRays", C.c_longlong), ("cameraRays", C.c_longlong),

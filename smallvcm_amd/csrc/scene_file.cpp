@@ -18,6 +18,9 @@
 //       light background scale                           BackgroundLight (lights.hxx:404-408)
 //       light envmap <file.hdr|file.pfm> scale           an environment map as the background (vcm_scene_desc3,
 //                                                        vcm_scene_file_desc3; the image: vcm_envmap_load below)
+//       lens apertureRadius focusDistance                a thin lens instead of the pinhole, at most one: radius >= 0
+//                                                        and focus distance > 0 in world units, both finite, nothing
+//                                                        after them (vcm_scene_desc4, vcm_scene_file_desc4)
 //   .obj        v, f (triangles; polygons are fanned around their first vertex; v, v/vt, v/vt/vn, v//vn; negative
 //               = relative indices), usemtl, mtllib; everything else is skipped
 //   .mtl        newmtl, Kd -> mDiffuseReflectance, Ks + Ns -> mPhongReflectance / mPhongExponent (materials.hxx:54-65),
@@ -54,6 +57,9 @@ struct vcm_scene_file {
     vcm_scene_desc2 desc;
     vcm_envmap *envmap = NULL;        /* `light envmap` */
     vcm_scene_desc3 desc3;
+    bool haveLens = false;            /* `lens` */
+    vcm_thin_lens lens;
+    vcm_scene_desc4 desc4;
     ~vcm_scene_file() { vcm_envmap_free(envmap); }
 };
 
@@ -408,6 +414,16 @@ struct Loader {
                 if (!floats(p, x, 10)) { ok = fail(at + ": camera px py pz fx fy fz ux uy uz fov"); break; }
                 memcpy(camPos, x, 12); memcpy(camFwd, x + 3, 12); memcpy(camUp, x + 6, 12); camFov = x[9];
                 haveCamera = true;
+            } else if (key == "lens") {
+                float x[2];
+                const bool got = floats(p, x, 2);
+                const std::string rest = got ? word(p) : std::string();
+                if (!got || (!rest.empty() && rest[0] != '#')) { ok = fail(at + ": lens apertureRadius focusDistance"); break; }
+                if (out->haveLens) { ok = fail(at + ": a second lens"); break; }
+                if (!std::isfinite(x[0]) || x[0] < 0.f) { ok = fail(at + ": lens apertureRadius must be finite and >= 0"); break; }
+                if (!std::isfinite(x[1]) || !(x[1] > 0.f)) { ok = fail(at + ": lens focusDistance must be finite and > 0"); break; }
+                out->lens.apertureRadius = x[0]; out->lens.focusDistance = x[1];
+                out->haveLens = true;
             } else if (key == "light") {
                 const std::string kind = word(p);
                 vcm_light l;
@@ -452,6 +468,8 @@ struct Loader {
         if (vcm_make_camera(camPos, camFwd, camUp, camFov, resX, resY, &d.camera) != 0) return fail("bad camera");
         out->desc3.base = d;
         out->desc3.envmap = out->envmap;
+        out->desc4.base = out->desc3;
+        out->desc4.lens = out->haveLens ? &out->lens : NULL;
         return true;
     }
 };
@@ -490,6 +508,7 @@ const vcm_scene_desc2 *vcm_scene_file_desc(const vcm_scene_file *s) { return s ?
 void vcm_scene_file_free(vcm_scene_file *s) { delete s; }
 
 const vcm_scene_desc3 *vcm_scene_file_desc3(const vcm_scene_file *s) { return s ? &s->desc3 : NULL; }
+const vcm_scene_desc4 *vcm_scene_file_desc4(const vcm_scene_file *s) { return s ? &s->desc4 : NULL; }
 
 vcm_envmap *vcm_envmap_load(const char *path)
 {

@@ -46,6 +46,8 @@ struct SceneHost {
     std::vector<F4> envTexels;
     std::vector<float> envMarg, envCond;
     std::vector<int> envMargGuide, envCondGuide;
+    /* the thin lens (scene_host_set_lens; lensRadius == 0: the pinhole), DScene::lensRadius ... */
+    float lensRadius = 0.f, lensFocus = 1.f, lensRight[3] = { 0.f, 0.f, 0.f }, lensUp[3] = { 0.f, 0.f, 0.f };
 
     /* the view the device functions take, filled IN PLACE: the arrays are addressed relative to the DScene object
        itself (vcm_core.h), so `d` must stay where it is while it is in use (host emulation) */
@@ -81,6 +83,8 @@ struct SceneHost {
         for (int k = 0; k < 3; k++) d.nFastRects[k] = nFastRects[k];
         d.fastGmax = fastGmax;
         d.envW = envW; d.envH = envH; d.envGuideW = envGuideW; d.envGuideH = envGuideH;
+        d.lensRadius = lensRadius; d.lensFocus = lensFocus;
+        for (int k = 0; k < 3; k++) { d.lensRight[k] = lensRight[k]; d.lensUp[k] = lensUp[k]; }
         { const char *e = getenv("SMALLVCM_AMD_NO_RECTS"); if (e && e[0] == '1') d.nFastRects[0] = d.nFastRects[1] = d.nFastRects[2] = 0; }   /* measurement switch */
     }
 };
@@ -228,6 +232,43 @@ inline bool scene_host_set_envmap(SceneHost &s, const vcm_envmap *m, std::string
 inline bool scene_host_from_desc3(const vcm_scene_desc3 &sc, SceneHost &s, std::string &err)
 {
     return scene_host_copy_desc2(sc.base, s, err) && scene_host_set_envmap(s, sc.envmap, err);
+}
+
+/* ---- the thin lens (vcm_core.h lens_point / lens_ray / lens_project) ----
+ * The disc's basis, in binary64 from the camera as stored: right = the world direction of raster +x (the difference of
+ * rasterToWorld at raster (1, 0) and (0, 0)) made orthogonal to forward, up = forward x right. */
+inline bool scene_host_set_lens(SceneHost &s, const vcm_thin_lens *lens, std::string &err)
+{
+    s.lensRadius = 0.f; s.lensFocus = 1.f;
+    if (!lens) return true;
+    const float R = lens->apertureRadius, F = lens->focusDistance;
+    if (!std::isfinite(R) || R < 0.f) { err = "thin lens: apertureRadius must be finite and >= 0"; return false; }
+    if (!std::isfinite(F) || !(F > 0.f)) { err = "thin lens: focusDistance must be finite and > 0"; return false; }
+    if (R == 0.f) return true;   /* the pinhole */
+    const float *m = s.camera.rasterToWorld;
+    double a[3], b[3], f[3], r[3], u[3];
+    for (int k = 0; k < 3; k++) {   /* transform_point at (0, 0, 0) and (1, 0, 0) */
+        a[k] = (double)m[12 + k] / (double)m[15];
+        b[k] = ((double)m[12 + k] + m[k]) / ((double)m[15] + m[3]);
+        f[k] = s.camera.forward[k];
+    }
+    const double fl = std::sqrt(f[0] * f[0] + f[1] * f[1] + f[2] * f[2]);
+    if (!(fl > 0.0) || !std::isfinite(fl)) { err = "thin lens: the camera has no forward direction"; return false; }
+    for (int k = 0; k < 3; k++) { f[k] /= fl; r[k] = b[k] - a[k]; }
+    const double rf = r[0] * f[0] + r[1] * f[1] + r[2] * f[2];
+    for (int k = 0; k < 3; k++) r[k] -= rf * f[k];
+    const double rl = std::sqrt(r[0] * r[0] + r[1] * r[1] + r[2] * r[2]);
+    if (!(rl > 0.0) || !std::isfinite(rl)) { err = "thin lens: the camera's raster axes are degenerate"; return false; }
+    for (int k = 0; k < 3; k++) r[k] /= rl;
+    u[0] = f[1] * r[2] - f[2] * r[1]; u[1] = f[2] * r[0] - f[0] * r[2]; u[2] = f[0] * r[1] - f[1] * r[0];
+    s.lensRadius = R; s.lensFocus = F;
+    for (int k = 0; k < 3; k++) { s.lensRight[k] = (float)r[k]; s.lensUp[k] = (float)u[k]; }
+    return true;
+}
+
+inline bool scene_host_from_desc4(const vcm_scene_desc4 &sc, SceneHost &s, std::string &err)
+{
+    return scene_host_from_desc3(sc.base, s, err) && scene_host_set_lens(s, sc.lens, err);
 }
 
 /* ---- brute-force list: consecutive triangles in pairs, fields interleaved (vcm_core.h TriPair) ---- */

@@ -115,25 +115,34 @@ static thread_local unsigned long long g_threadId = 0;
 static unsigned long long this_thread_id() { if (!g_threadId) g_threadId = ++g_threadCounter; return g_threadId; }
 
 /* Kernels that cast rays exist once per kind of scene (vcm_core.h SceneList / SceneBvh); the launch picks.  A scene with
-   an environment map takes the kinds that carry its branch (SceneRectsE / SceneListE / SceneBvhE). */
-#define LAUNCH_SC(c, K, ...) do { if ((c)->envMap) { if (!(c)->scene->nodes.empty()) hipLaunchKernelGGL((K<SceneBvhE>), __VA_ARGS__); \
-                                                     else if ((c)->intPhong && (c)->sceneRects) hipLaunchKernelGGL((K<SceneRectsE>), __VA_ARGS__); \
-                                                     else hipLaunchKernelGGL((K<SceneListE>), __VA_ARGS__); } \
-                                  else if (!(c)->scene->nodes.empty()) { if ((c)->intPhong) hipLaunchKernelGGL((K<SceneBvh>), __VA_ARGS__); \
-                                                                     else hipLaunchKernelGGL((K<SceneBvhG>), __VA_ARGS__); } \
-                                  else if (!(c)->intPhong) hipLaunchKernelGGL((K<SceneList>), __VA_ARGS__); \
-                                  else if ((c)->sceneRects) hipLaunchKernelGGL((K<SceneRects>), __VA_ARGS__); \
-                                  else if ((c)->sceneQuads) hipLaunchKernelGGL((K<SceneQuads>), __VA_ARGS__); \
-                                  else hipLaunchKernelGGL((K<SceneList>), __VA_ARGS__); } while (0)
-#define LAUNCH_SC_MODE(c, K, M, ...) do { if ((c)->envMap) { if (!(c)->scene->nodes.empty()) hipLaunchKernelGGL((K<M, SceneBvhE>), __VA_ARGS__); \
-                                                             else if ((c)->intPhong && (c)->sceneRects) hipLaunchKernelGGL((K<M, SceneRectsE>), __VA_ARGS__); \
-                                                             else hipLaunchKernelGGL((K<M, SceneListE>), __VA_ARGS__); } \
-                                          else if (!(c)->scene->nodes.empty()) { if ((c)->intPhong) hipLaunchKernelGGL((K<M, SceneBvh>), __VA_ARGS__); \
-                                                                             else hipLaunchKernelGGL((K<M, SceneBvhG>), __VA_ARGS__); } \
-                                          else if (!(c)->intPhong) hipLaunchKernelGGL((K<M, SceneList>), __VA_ARGS__); \
-                                          else if ((c)->sceneRects) hipLaunchKernelGGL((K<M, SceneRects>), __VA_ARGS__); \
-                                          else if ((c)->sceneQuads) hipLaunchKernelGGL((K<M, SceneQuads>), __VA_ARGS__); \
-                                          else hipLaunchKernelGGL((K<M, SceneList>), __VA_ARGS__); } while (0)
+   an environment map takes the kinds that carry its branch (SceneRectsE / SceneListE / SceneBvhE).  W wraps the kind:
+   Pinhole is the kind itself, WithLens (vcm_core.h) the thin-lens instantiation of the kernels that hold the camera
+   vertex, which LAUNCH_SC_CAM / LAUNCH_SC_MODE_CAM pick for a scene with a lens. */
+template <class S> using Pinhole = S;
+#define LAUNCH_SC_W(c, W, K, ...) do { if ((c)->envMap) { if (!(c)->scene->nodes.empty()) hipLaunchKernelGGL((K<W<SceneBvhE>>), __VA_ARGS__); \
+                                                     else if ((c)->intPhong && (c)->sceneRects) hipLaunchKernelGGL((K<W<SceneRectsE>>), __VA_ARGS__); \
+                                                     else hipLaunchKernelGGL((K<W<SceneListE>>), __VA_ARGS__); } \
+                                  else if (!(c)->scene->nodes.empty()) { if ((c)->intPhong) hipLaunchKernelGGL((K<W<SceneBvh>>), __VA_ARGS__); \
+                                                                     else hipLaunchKernelGGL((K<W<SceneBvhG>>), __VA_ARGS__); } \
+                                  else if (!(c)->intPhong) hipLaunchKernelGGL((K<W<SceneList>>), __VA_ARGS__); \
+                                  else if ((c)->sceneRects) hipLaunchKernelGGL((K<W<SceneRects>>), __VA_ARGS__); \
+                                  else if ((c)->sceneQuads) hipLaunchKernelGGL((K<W<SceneQuads>>), __VA_ARGS__); \
+                                  else hipLaunchKernelGGL((K<W<SceneList>>), __VA_ARGS__); } while (0)
+#define LAUNCH_SC_MODE_W(c, W, K, M, ...) do { if ((c)->envMap) { if (!(c)->scene->nodes.empty()) hipLaunchKernelGGL((K<M, W<SceneBvhE>>), __VA_ARGS__); \
+                                                             else if ((c)->intPhong && (c)->sceneRects) hipLaunchKernelGGL((K<M, W<SceneRectsE>>), __VA_ARGS__); \
+                                                             else hipLaunchKernelGGL((K<M, W<SceneListE>>), __VA_ARGS__); } \
+                                          else if (!(c)->scene->nodes.empty()) { if ((c)->intPhong) hipLaunchKernelGGL((K<M, W<SceneBvh>>), __VA_ARGS__); \
+                                                                             else hipLaunchKernelGGL((K<M, W<SceneBvhG>>), __VA_ARGS__); } \
+                                          else if (!(c)->intPhong) hipLaunchKernelGGL((K<M, W<SceneList>>), __VA_ARGS__); \
+                                          else if ((c)->sceneRects) hipLaunchKernelGGL((K<M, W<SceneRects>>), __VA_ARGS__); \
+                                          else if ((c)->sceneQuads) hipLaunchKernelGGL((K<M, W<SceneQuads>>), __VA_ARGS__); \
+                                          else hipLaunchKernelGGL((K<M, W<SceneList>>), __VA_ARGS__); } while (0)
+#define LAUNCH_SC(c, K, ...) LAUNCH_SC_W(c, Pinhole, K, __VA_ARGS__)
+#define LAUNCH_SC_MODE(c, K, M, ...) LAUNCH_SC_MODE_W(c, Pinhole, K, M, __VA_ARGS__)
+#define LAUNCH_SC_CAM(c, K, ...) do { if ((c)->lens) LAUNCH_SC_W(c, WithLens, K, __VA_ARGS__); \
+                                      else LAUNCH_SC_W(c, Pinhole, K, __VA_ARGS__); } while (0)
+#define LAUNCH_SC_MODE_CAM(c, K, M, ...) do { if ((c)->lens) LAUNCH_SC_MODE_W(c, WithLens, K, M, __VA_ARGS__); \
+                                              else LAUNCH_SC_MODE_W(c, Pinhole, K, M, __VA_ARGS__); } while (0)
 
 #ifndef VCM_MERGE_DEFAULT
 #define VCM_MERGE_DEFAULT VCM_MERGE_PAIRS
@@ -196,6 +205,7 @@ struct vcm_ctx : Scratch {
     bool sceneQuads;                  /* every triangle pair of the list shares its plane part: the SceneQuads kernels */
     bool sceneRects;                  /* ... and is an axis-aligned rectangle: the SceneRects kernels */
     bool envMap;                      /* the scene's background is an environment map: the SceneRectsE / SceneListE / SceneBvhE kernels */
+    bool lens;                        /* the camera is a thin lens: the WithLens kernels for the camera vertex (LAUNCH_SC_CAM) */
     bool intPhong;                    /* every Phong exponent in use is an integer in [1, 65536]: the kernels whose pow is the binary
                                          exponentiation alone (detmath.h); otherwise the SceneList / SceneBvhG kernels and the general merge */
     IterParams P;
@@ -749,6 +759,7 @@ static vcm_ctx *create_from_host(SceneHost *h, int algorithm, float radiusFactor
     memset((void *)c, 0, sizeof(*c));
     c->scene = h;
     c->envMap = h->envW > 0;
+    c->lens = h->lensRadius > 0.f;
     scene_host_build_accel(*h, scene_host_force_bvh());
     /* VertexCM::VertexCM vertexcm.hxx:222-244 */
     switch (algorithm) {
@@ -831,6 +842,16 @@ vcm_ctx *vcm_create_sharded3(const vcm_scene_desc3 *scene, int algorithm, float 
     return create_from_host(h, algorithm, radiusFactor, radiusAlpha, seed, device, rank, worldSize);
 }
 
+vcm_ctx *vcm_create_sharded4(const vcm_scene_desc4 *scene, int algorithm, float radiusFactor, float radiusAlpha,
+                             int seed, int device, int rank, int worldSize)
+{
+    if (!scene) { fail("vcm_create4", "scene is NULL"); return NULL; }
+    SceneHost *h = new (std::nothrow) SceneHost();
+    std::string err;
+    if (!h || !scene_host_from_desc4(*scene, *h, err)) { delete h; fail("vcm_create4", err.c_str()); return NULL; }
+    return create_from_host(h, algorithm, radiusFactor, radiusAlpha, seed, device, rank, worldSize);
+}
+
 /* Which device a renderer-per-host-core host puts its next renderer on (vcm_next_device).  The reference's driver
  * builds one renderer per host core and runs them concurrently (smallvcm.cxx:61-72, :99-108): on a multi-GPU node the
  * drop-in deals them round-robin over the visible devices -- every GPU renders whole iterations of its renderers
@@ -879,6 +900,11 @@ vcm_ctx *vcm_create2(const vcm_scene_desc2 *scene, int algorithm, float radiusFa
 vcm_ctx *vcm_create3(const vcm_scene_desc3 *scene, int algorithm, float radiusFactor, float radiusAlpha, int seed)
 {
     return vcm_create_sharded3(scene, algorithm, radiusFactor, radiusAlpha, seed, next_device(true), 0, 1);
+}
+
+vcm_ctx *vcm_create4(const vcm_scene_desc4 *scene, int algorithm, float radiusFactor, float radiusAlpha, int seed)
+{
+    return vcm_create_sharded4(scene, algorithm, radiusFactor, radiusAlpha, seed, next_device(true), 0, 1);
 }
 
 void vcm_destroy(vcm_ctx *c)
@@ -1163,7 +1189,7 @@ static int flush_light_splats(vcm_ctx *c)
         F4 *list = c->dSplatList;
         if (c->prezeroed) HIPCHK(hipStreamWaitEvent(q, c->evZero, 0));
         else if (zero_ranges(q, pixCount, ((size_t)c->N + 1) * sizeof(int))) return -1;
-        LAUNCH_SC(c, k_connect_camera, dim3(task_blocks(c->nLocal)), dim3(256), 0, q, c->dScene, c->P, c->store,
+        LAUNCH_SC_CAM(c, k_connect_camera, dim3(task_blocks(c->nLocal)), dim3(256), 0, q, c->dScene, c->P, c->store,
                            (const int *)c->dSlotOfVertex, (const int *)c->dLocalTotal, c->dFb, c->dSplat, pixCount,
                            arrival, c->dStats);
         if (launch_scan_on<int>(c, overlap ? 2 : 0, q, pixCount, c->N, pixStart, NULL, 1, overlap ? none : take_stamps(c, q))) return -1;
@@ -1222,7 +1248,7 @@ static int vcm_trace_light_impl(vcm_ctx *c)
         LAUNCH_SC_MODE(c, k_light_trace, 1, dim3(blocks), dim3(VCM_TRACE_BLOCK), 0, c->stream, c->dScene, c->P, c->store,
                            c->dFb, c->dRngLight, c->dStats, chunk, take_stamps(c, c->stream), c->vs.count + 16, c->dHdr);
     else
-        LAUNCH_SC_MODE(c, k_light_trace, 0, dim3(blocks), dim3(VCM_TRACE_BLOCK), 0, c->stream, c->dScene, c->P, c->store,
+        LAUNCH_SC_MODE_CAM(c, k_light_trace, 0, dim3(blocks), dim3(VCM_TRACE_BLOCK), 0, c->stream, c->dScene, c->P, c->store,
                            c->dFb, c->dRngLight, c->dStats, chunk, take_stamps(c, c->stream), c->vs.count + 16, c->dHdr);
     HIPCHK(hipGetLastError());
     c->bboxFromLight = c->world == 1;   /* K1 keeps the box of what it stores (k_bbox, a pass of its own over the vertices, serves imported records) */
@@ -1619,10 +1645,10 @@ static int vcm_trace_camera_impl(vcm_ctx *c)
     if (mark(c, EV_CAMERA_K0)) return -1;
     if (c->renderer) {   /* PathTracer / EyeLight: colour + jittered pixel per path; K5 adds them in path order */
         if (c->renderer == 1)
-            LAUNCH_SC(c, k_path_trace, dim3(blocks), dim3(VCM_TRACE_BLOCK), 0, c->stream, c->dScene, c->P, c->dCamOut,
+            LAUNCH_SC_CAM(c, k_path_trace, dim3(blocks), dim3(VCM_TRACE_BLOCK), 0, c->stream, c->dScene, c->P, c->dCamOut,
                                c->dRngCam, c->dStats, chunk, take_stamps(c, c->stream), c->vs.count + 8);
         else
-            LAUNCH_SC(c, k_eye_light, dim3(2048), dim3(256), 0, c->stream, c->dScene, c->P, c->dCamOut, c->dRngCam,
+            LAUNCH_SC_CAM(c, k_eye_light, dim3(2048), dim3(256), 0, c->stream, c->dScene, c->P, c->dCamOut, c->dRngCam,
                                c->dStats, take_stamps(c, c->stream));
         HIPCHK(hipGetLastError());
         if (mark(c, EV_CAMERA_K1)) return -1;
@@ -1641,7 +1667,7 @@ static int vcm_trace_camera_impl(vcm_ctx *c)
             if (c->prezeroed) HIPCHK(hipStreamWaitEvent(c->stream, c->evZero, 0));
             else if (zero_ranges(c->stream, c->dQueryCount, ((size_t)c->P.nBuckets + 1) * sizeof(int))) return -1;
         }
-        LAUNCH_SC_MODE(c, k_camera_trace, 1, dim3(blocks), dim3(VCM_TRACE_BLOCK), 0, c->stream, c->dScene, c->P,
+        LAUNCH_SC_MODE_CAM(c, k_camera_trace, 1, dim3(blocks), dim3(VCM_TRACE_BLOCK), 0, c->stream, c->dScene, c->P,
                            c->store, grid_of(c), c->vs, c->dCamOut, c->dCamMask, c->dRngCam, c->dStats, chunk, take_stamps(c, c->stream));
         if (mark(c, EV_CAMERA_K1)) return -1;
         if (c->useVC) {   /* K3b, K3c: dense DI / VC tasks */
@@ -1699,7 +1725,7 @@ static int vcm_trace_camera_impl(vcm_ctx *c)
         if (mark(c, EV_CONNECT_K1)) return -1;
     } else {
         if (c->useVM && !c->gridBuilt) return fail("vcm_trace_camera", "strict mode merges inside the camera pass: call vcm_build_grid first");
-        LAUNCH_SC_MODE(c, k_camera_trace, 0, dim3(blocks), dim3(VCM_TRACE_BLOCK), 0, c->stream, c->dScene, c->P,
+        LAUNCH_SC_MODE_CAM(c, k_camera_trace, 0, dim3(blocks), dim3(VCM_TRACE_BLOCK), 0, c->stream, c->dScene, c->P,
                            c->store, grid_of(c), c->vs, c->dCamOut, c->dCamMask, c->dRngCam, c->dStats, chunk, take_stamps(c, c->stream));
         if (mark(c, EV_CAMERA_K1)) return -1;
         if (mark(c, EV_CONNECT_K1)) return -1;
@@ -2347,6 +2373,7 @@ int vcm_debug_numeric_spec(int op, int n, const float *a, const float *b, float 
 int vcm_debug_kat(vcm_ctx *c, int op, int n, const float *in, float *out)
 {
     if (!c || !in || !out || n < 0 || op < 0 || op >= VCM_KAT_OPS) return fail("vcm_debug_kat", "bad argument");
+    if (op == VCM_KAT_LENS && !c->lens) return fail("vcm_debug_kat", "VCM_KAT_LENS needs a context with a thin lens (vcm_create4)");
     if (ensure_device(c)) return -1;
     if (n == 0) return 0;
     float *din = NULL, *dout = NULL;
@@ -2354,7 +2381,7 @@ int vcm_debug_kat(vcm_ctx *c, int op, int n, const float *in, float *out)
     HIPCHK(hipMalloc((void **)&din, bytes));
     HIPCHK(hipMalloc((void **)&dout, bytes));
     HIPCHK(hipMemcpy(din, in, bytes, hipMemcpyHostToDevice));
-    LAUNCH_SC(c, k_kat, dim3((n + 63) / 64), dim3(64), 0, 0, (const DScene *)c->dScene, op, n, (const float *)din, dout);
+    LAUNCH_SC_CAM(c, k_kat, dim3((n + 63) / 64), dim3(64), 0, 0, (const DScene *)c->dScene, op, n, (const float *)din, dout);
     hipError_t e = hipGetLastError();
     if (e == hipSuccess) e = hipMemcpy(out, dout, bytes, hipMemcpyDeviceToHost);
     (void)hipFree(din); (void)hipFree(dout);

@@ -367,6 +367,7 @@ struct DScene {
     /* (as a type, see the kinds below: may the kernels assume that every Phong exponent is an integer in [1, 65536]?) */
     static constexpr bool kIntPhong = false;
     static constexpr bool kEnvMap = false;
+    static constexpr bool kLens = false;
     int nPrims, nMaterials, nLights, backgroundLight;
     float sceneCenter[3], sceneRadius, invSceneRadiusSqr;
     vcm_camera camera;
@@ -384,6 +385,9 @@ struct DScene {
        CDF per row (envW + 1 floats each) and the guide tables of both (envGuideH + 1 / envGuideW + 1 ints per CDF) */
     int envW, envH, envGuideW, envGuideH;
     long long offEnvTexels, offEnvMarg, offEnvCond, offEnvMargGuide, offEnvCondGuide;
+    /* the thin lens (lensRadius == 0: the pinhole), built by scene_host.h: aperture radius, focus distance along the
+       camera's forward axis, and the lens disc's orthonormal basis (lensRight = the raster +x direction) */
+    float lensRadius, lensFocus, lensRight[3], lensUp[3];
     template <class T> VCM_HD const T *at(long long off) const { return reinterpret_cast<const T *>(reinterpret_cast<const char *>(this) + off); }
     VCM_HD const vcm_prim *prims() const { return at<vcm_prim>(offPrims); }
     VCM_HD const vcm_material *materials() const { return at<vcm_material>(offMaterials); }
@@ -434,6 +438,19 @@ struct SceneBvhE : DScene { static constexpr bool kBvh = true; static constexpr 
 #define VCM_ENV_KIND(S) (S::kEnvMap)
 #else
 #define VCM_ENV_KIND(S) true
+#endif
+
+/* kLens: the camera is a thin lens (DScene::lensRadius > 0).  Only the kernels that hold the camera vertex (strict K1,
+   K3, the path tracer, eye light, k_connect_camera) and the known-answer kernel exist in these kinds, one over each kind
+   above; a scene with a lens launches them there and every other kernel where it would without one.  The host builds
+   carry the lens branch in every kind and take it at run time. */
+template <class S> struct WithLens : S { static constexpr bool kLens = true; };
+#if defined(__HIP_DEVICE_COMPILE__)
+#define VCM_LENS_KIND(S) (S::kLens)
+#define VCM_LENS_ON(S, sc) (S::kLens)
+#else
+#define VCM_LENS_KIND(S) true
+#define VCM_LENS_ON(S, sc) ((sc).lensRadius > 0.f)
 #endif
 
 /* ---- the scene's small tables in LDS ----
@@ -2170,21 +2187,71 @@ VCM_HD void generate_light_sample(const S &sc, const IterParams &P, PathRng &rng
     st.dVM = st.dVC * P.misVcWeightFactor;
 }
 
+/* ---- the thin lens (DESIGN.md "Thin lens") ----
+ * The lens draws come from streams of their own, so that the light (kind 0) and camera (kind 1) tapes keep their
+ * meaning: kind 2 = a camera path's lens point (block 0, keyed by the global path), kind 3 = the lens point of a light
+ * vertex's connection to the camera (keyed by the global light path, block = the vertex's pathLength).  Both are
+ * functions of (seed, local iteration, path, vertex), so strict and wavefront order and every shard draw the same. */
+VCM_HD void lens_rnd(const IterParams &P, uint32_t kind, uint32_t path, uint32_t block, float *r)
+{
+    PathRng rng;
+    rng_init(rng, P.seed, P.localIter, path, kind);
+    rng_peek_block(rng, block << 2, r, 2);
+}
+/* the lens point of the sample (r0, r1): concentric disc, scaled by the aperture radius, in the lens plane */
+VCM_HD V3 lens_point(const DScene &sc, float r0, float r1)
+{
+    float u, v;
+    sample_concentric_disc(r0, r1, u, v);
+    return ld3(sc.camera.position) + sc.lensRadius * (u * ld3(sc.lensRight) + v * ld3(sc.lensUp));
+}
+/* a camera ray through the lens: d0 = the pinhole direction of the raster sample, its point on the focus plane
+   p = c + d0 F / (d0 . f), the ray from the lens point to p */
+VCM_HD void lens_ray(const DScene &sc, V3 d0, float r0, float r1, V3 &org, V3 &dir)
+{
+    const V3 c = ld3(sc.camera.position);
+    const V3 p = c + d0 * (sc.lensFocus / dot(d0, ld3(sc.camera.forward)));
+    org = lens_point(sc, r0, r1);
+    dir = normalize(p - org);
+}
+/* the raster of world point x seen through lens point l: x projected from l onto the focus plane, then WorldToRaster;
+   false when x is not in front of the lens plane */
+VCM_HD bool lens_project(const DScene &sc, V3 l, V3 x, V3 &raster)
+{
+    const vcm_camera &cam = sc.camera;
+    const float z = dot(x - ld3(cam.position), ld3(cam.forward));
+    if (z <= 0.f) return false;
+    const V3 p = l + (x - l) * (sc.lensFocus / z);
+    raster = transform_point(cam.worldToRaster, p);
+    return true;
+}
+
 /* ConnectToCamera :862-933; the splat is an atomic add (Framebuffer::AddColor
  * framebuffer.hxx:43-57 on an arbitrary pixel) */
 /* splatOut == NULL: the splat is an fp32 atomic add on fb (strict mode);
  * otherwise *splatOut receives (contrib.rgb, pixel) -- pixel -1 when nothing is
  * splatted -- and k_splat_apply adds the splats of a pixel in vertex order. */
+/* lensPath: the global index of the light path (the lens kinds' kind-3 draw; unused without a lens).  With a lens the
+ * camera vertex is a lens point drawn per light vertex, and the rest is evaluated from it: the lens-area pdf of that
+ * vertex is common to every strategy that holds it, so it enters no MIS weight, and it cancels the importance's. */
 template <class SC>
 VCM_HD void connect_to_camera(const SC &sc, const IterParams &P, const SubPathState &st, V3 hitpoint,
-                              const Bsdf &bsdf, float *fb, LaneStats &ls, F4 *splatOut = 0)
+                              const Bsdf &bsdf, float *fb, LaneStats &ls, F4 *splatOut, int lensPath)
 {
     if (splatOut) *splatOut = mk4(0.f, 0.f, 0.f, u2f(0xffffffffu));
     RC_DECL;
     const vcm_camera &cam = sc.camera;
-    V3 directionToCamera = ld3(cam.position) - hitpoint;
+    V3 camPos = ld3(cam.position);
+    V3 ip;
+    if (VCM_LENS_ON(SC, sc)) {
+        float r[2];
+        lens_rnd(P, 3u, (uint32_t)lensPath, st.pathLength, r);
+        camPos = lens_point(sc, r[0], r[1]);
+        if (!lens_project(sc, camPos, hitpoint, ip)) return;
+    }
+    V3 directionToCamera = camPos - hitpoint;
     if (dot(ld3(cam.forward), -directionToCamera) <= 0.f) return;
-    const V3 ip = transform_point(cam.worldToRaster, hitpoint);
+    if (!VCM_LENS_ON(SC, sc)) ip = transform_point(cam.worldToRaster, hitpoint);
     if (!(ip.x >= 0 && ip.y >= 0 && ip.x < cam.resolution[0] && ip.y < cam.resolution[1])) return;
     const float distEye2 = lensqr(directionToCamera);
     const float distance = sqrtf(distEye2);
@@ -2285,7 +2352,7 @@ VCM_HD bool light_path_step(const SC &sc, const IterParams &P, LightPath &lp, co
         if (P.useVC || P.useVM) ls.stored++;   /* the reference stores nothing in light-trace mode (:364) */
     }
     if (MODE == 0 && !bsdf.isDelta && (P.useVC || P.lightTraceOnly)) {   /* :380-384 */
-        if (st.pathLength + 1 >= P.minLen) connect_to_camera(sc, P, st, hitPoint, bsdf, fb, ls);
+        if (st.pathLength + 1 >= P.minLen) connect_to_camera(sc, P, st, hitPoint, bsdf, fb, ls, (F4 *)0, P.p0 + lp.lp);
     }
     RC_MARK(2);
     if (st.pathLength + 2 > P.maxLen) return false;   /* :387 */
@@ -2322,7 +2389,9 @@ VCM_HD void connect_stored_vertex_to_camera(const SC &sc, const IterParams &P, c
     st.dVCM = b.w; st.dVC = c.w; st.dVM = d.w;
     Bsdf bsdf;
     bsdf_restore(bsdf, mk3(c.x, c.y, c.z), mk3(d.x, d.y, d.z), f2u(a.w) >> 8, sc);
-    connect_to_camera(sc, P, st, mk3(a.x, a.y, a.z), bsdf, fb, ls, splatOut);
+    /* the slot is nStored * nLocal + lp (light_path_step): the light path is recoverable without a field of its own */
+    const int lensPath = VCM_LENS_ON(SC, sc) ? P.p0 + (int)(slot % (size_t)P.nLocal) : 0;
+    connect_to_camera(sc, P, st, mk3(a.x, a.y, a.z), bsdf, fb, ls, splatOut, lensPath);
 }
 
 /* ================= camera sub-path (vertexcm.hxx:415-545) ============= */
@@ -2860,8 +2929,11 @@ VCM_HD int wave_queue_take(int &base, int &left, int *counter, int blockSize, in
 #endif
 }
 
-/* GenerateCameraSample :564-606 (+ Camera::GenerateRay camera.hxx:108-117) */
-VCM_HD void camera_path_begin(const DScene &sc, const IterParams &P, CameraPath &cp, int localPath, const uint32_t *lightLenMask = 0)
+/* GenerateCameraSample :564-606 (+ Camera::GenerateRay camera.hxx:108-117); with a lens the ray starts at a lens point
+   (kind-2 draw) and cameraPdfW keeps its formula with cos = forward . dir: by similar triangles it is the same
+   per-pixel density */
+template <class S>
+VCM_HD void camera_path_begin(const S &sc, const IterParams &P, CameraPath &cp, int localPath, const uint32_t *lightLenMask = 0)
 {
     const vcm_camera &cam = sc.camera;
     const int pathIdx = P.p0 + localPath;
@@ -2880,8 +2952,13 @@ VCM_HD void camera_path_begin(const DScene &sc, const IterParams &P, CameraPath 
     cp.sx = float(x) + jx;
     cp.sy = float(y) + jy;
     const V3 worldRaster = transform_point(cam.rasterToWorld, mk3(cp.sx, cp.sy, 0.f));
-    const V3 org = ld3(cam.position);
-    const V3 dir = normalize(worldRaster - org);
+    V3 org = ld3(cam.position);
+    V3 dir = normalize(worldRaster - org);
+    if (VCM_LENS_ON(S, sc)) {
+        float r[2];
+        lens_rnd(P, 2u, (uint32_t)pathIdx, 0u, r);
+        lens_ray(sc, dir, r[0], r[1], org, dir);
+    }
     const float cosAtCamera = dot(ld3(cam.forward), dir);
     const float imagePointToCameraDist = cam.imagePlaneDist / cosAtCamera;
     const float imageToSolidAngleFactor = sqr(imagePointToCameraDist) / cosAtCamera;
@@ -3189,7 +3266,8 @@ struct PtPath {
     int lp;
 };
 VCM_HD float mis2(float samplePdf, float otherPdf) { return mis(samplePdf) / (mis(samplePdf) + mis(otherPdf)); }   /* :226-231 */
-VCM_HD void pt_path_begin(const DScene &sc, const IterParams &P, PtPath &pp, int localPath)
+template <class S>
+VCM_HD void pt_path_begin(const S &sc, const IterParams &P, PtPath &pp, int localPath)
 {
     const vcm_camera &cam = sc.camera;
     const int pathIdx = P.p0 + localPath;
@@ -3203,6 +3281,11 @@ VCM_HD void pt_path_begin(const DScene &sc, const IterParams &P, PtPath &pp, int
     const V3 worldRaster = transform_point(cam.rasterToWorld, mk3(pp.sx, pp.sy, 0.f));   /* camera.hxx:108-117 */
     pp.org = ld3(cam.position);
     pp.dir = normalize(worldRaster - pp.org);
+    if (VCM_LENS_ON(S, sc)) {   /* the thin lens: a kind-2 draw (camera_path_begin) */
+        float r[2];
+        lens_rnd(P, 2u, (uint32_t)pathIdx, 0u, r);
+        lens_ray(sc, pp.dir, r[0], r[1], pp.org, pp.dir);
+    }
     pp.weight = sp3(1.f);
     pp.color = sp3(0.f);
     pp.pathLength = 1;
@@ -3323,6 +3406,11 @@ VCM_HD bool eyelight_path(const SC &sc, const IterParams &P, int localPath, V3 &
     const V3 worldRaster = transform_point(cam.rasterToWorld, mk3(sx, sy, 0.f));
     ray.org = ld3(cam.position);
     ray.dir = normalize(worldRaster - ray.org);
+    if (VCM_LENS_ON(SC, sc)) {   /* the thin lens draws its kind-2 sample in every iteration, the first included */
+        float r[2];
+        lens_rnd(P, 2u, (uint32_t)pathIdx, 0u, r);
+        lens_ray(sc, ray.dir, r[0], r[1], ray.org, ray.dir);
+    }
     ray.tmin = 0;
     Isect isect; isect.dist = 1e36f; isect.matID = 0; isect.lightID = -1; isect.normal = sp3(0.f); isect.prim = -1;
     ls.cameraRays++;

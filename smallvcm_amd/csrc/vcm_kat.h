@@ -88,6 +88,20 @@ VCM_HD void kat_eval(const SC &sc, int op, const float *in, float *out)
         out[3] = ip.x; out[4] = ip.y;
         out[5] = (ip.x >= 0 && ip.y >= 0 && ip.x < cam.resolution[0] && ip.y < cam.resolution[1]) ? 1.f : 0.f;
     } break;
+    case VCM_KAT_LENS:   /* the thin lens: camera_path_begin's ray and connect_to_camera's projection (vcm_core.h) */
+        if constexpr (VCM_LENS_KIND(SC)) {
+            const vcm_camera &cam = sc.camera;
+            const V3 d0 = normalize(transform_point(cam.rasterToWorld, mk3(in[0], in[1], 0.f)) - ld3(cam.position));
+            V3 org, dir;
+            lens_ray(sc, d0, in[2], in[3], org, dir);
+            const float cosAtCamera = dot(ld3(cam.forward), dir);
+            const float imagePointToCameraDist = cam.imagePlaneDist / cosAtCamera;
+            out[0] = org.x; out[1] = org.y; out[2] = org.z; out[3] = dir.x; out[4] = dir.y; out[5] = dir.z;
+            out[6] = sqr(imagePointToCameraDist) / cosAtCamera;
+            V3 ip;
+            if (lens_project(sc, org, ld3(in + 4), ip)) { out[7] = ip.x; out[8] = ip.y; out[9] = 1.f; }
+        }
+        break;
     default: break;
     }
 }

@@ -10,7 +10,7 @@
 //              [--res W H] [--seed S] [--minlen A] [--maxlen B]
 //              [--renderers R] [--radius-factor F] [--radius-alpha A]
 //              [--device D] [--strict] [--warmup W] [-o out.pfm] [--json] [--scene-file f.vcmscene|f.obj]
-//              [--envmap f.hdr|f.pfm [--envmap-scale S]]
+//              [--envmap f.hdr|f.pfm [--envmap-scale S]] [--aperture R --focus D]
 //              [--gpus N [--shards S] [--inflight K] [--devices 0,1,..] [--collectives rccl|threads] [--same-window]]
 //
 // --gpus N: the multi-GPU host (vcm_farm.hpp): N ranks = N host threads, one per GPU, cut into N / S groups; a
@@ -21,6 +21,9 @@
 //
 // --envmap: the built-in scene's BackgroundLight (scene 3) replaced by an environment map (vcm_envmap_load,
 // radiance = texel * S, S = 1 by default) over the same geometry; a scene file names its map itself (`light envmap`).
+//
+// --aperture R --focus D: a thin lens of radius R focused at distance D along the camera's forward axis (world units;
+// vcm_scene_desc4), for a built-in scene or a scene file; they override a scene file's `lens` directive.
 //
 // -s / -a / -i keep the meaning they have in the reference's CLI
 // (src/config.hxx:246-395; scenes = g_SceneConfigs[0..3], :146-151).
@@ -74,6 +77,8 @@ int main(int argc, char **argv)
     float radiusFactor = 0.003f, radiusAlpha = 0.75f;
     std::string out, algoName = "vcm", sceneFile, envFile;
     float envScale = 1.f;
+    float aperture = 0.f, focus = 0.f;
+    bool haveAperture = false, haveFocus = false;
     for (int i = 1; i < argc; i++) {
         const std::string a(argv[i]);
         auto need = [&](int n) { if (i + n >= argc) { fprintf(stderr, "vcm_render: %s needs %d argument(s)\n", a.c_str(), n); exit(2); } };
@@ -99,6 +104,13 @@ int main(int argc, char **argv)
         else if (a == "--scene-file") { need(1); sceneFile = argv[++i]; }   // instead of -s: OBJ + MTL / .vcmscene (vcm_scene_load)
         else if (a == "--envmap") { need(1); envFile = argv[++i]; }
         else if (a == "--envmap-scale") { need(1); envScale = (float)atof(argv[++i]); }
+        else if (a == "--aperture" || a == "--focus") {
+            need(1);
+            char *e = NULL;
+            const float v = strtof(argv[++i], &e);
+            if (e == argv[i] || *e) { fprintf(stderr, "vcm_render: %s needs a number\n", a.c_str()); return 2; }
+            if (a == "--aperture") { aperture = v; haveAperture = true; } else { focus = v; haveFocus = true; }
+        }
         else if (a == "--strict") strict = 1;
         else if (a == "--json") json = 1;
         else { fprintf(stderr, "vcm_render: unknown option %s (see the header of vcm_render.cpp)\n", a.c_str()); return 2; }
@@ -107,6 +119,7 @@ int main(int argc, char **argv)
         fprintf(stderr, "vcm_render: invalid argument\n");
         return 2;
     }
+    if (haveAperture != haveFocus) { fprintf(stderr, "vcm_render: --aperture and --focus go together\n"); return 2; }
 
     vcm_scene_desc scene;
     if (vcm_scene_cornell(resX, resY, vcm_scene_config_mask(sceneID), &scene)) return die("vcm_scene_cornell");
@@ -142,8 +155,33 @@ int main(int argc, char **argv)
         envDesc.envmap = envmap;
         envScene = &envDesc;
     }
+    // a thin lens (--aperture / --focus, else a scene file's `lens`): the scene as a version-4 description
+    vcm_thin_lens flagLens;
+    flagLens.apertureRadius = aperture; flagLens.focusDistance = focus;
+    const vcm_thin_lens *lens = haveAperture ? &flagLens : loaded ? vcm_scene_file_desc4(loaded)->lens : NULL;
+    vcm_scene_desc4 lensDesc;
+    const vcm_scene_desc4 *lensScene = NULL;
+    if (lens) {
+        if (gpus > 0) { fprintf(stderr, "vcm_render: a lens with --gpus is not supported (the farm takes version-1 scenes)\n"); return 2; }
+        memset(&lensDesc, 0, sizeof(lensDesc));
+        if (envScene) lensDesc.base = *envScene;
+        else if (loaded) lensDesc.base = *vcm_scene_file_desc3(loaded);
+        else {   // the built-in scene as a version-2 description (the arrays stay in `scene`)
+            vcm_scene_desc2 &b = lensDesc.base.base;
+            b.nPrims = scene.nPrims; b.prims = scene.prims;
+            b.nMaterials = scene.nMaterials; b.materials = scene.materials; b.mat2light = scene.mat2light;
+            b.nLights = scene.nLights; b.lights = scene.lights;
+            b.backgroundLight = scene.backgroundLight;
+            memcpy(b.sceneCenter, scene.sceneCenter, sizeof(b.sceneCenter));
+            b.sceneRadius = scene.sceneRadius; b.invSceneRadiusSqr = scene.invSceneRadiusSqr;
+            b.camera = scene.camera;
+        }
+        lensDesc.lens = lens;
+        lensScene = &lensDesc;
+    }
     auto create = [&](int s) {
-        return envScene ? vcm_create_sharded3(envScene, algorithm, radiusFactor, radiusAlpha, s, device, 0, 1)
+        return lensScene ? vcm_create_sharded4(lensScene, algorithm, radiusFactor, radiusAlpha, s, device, 0, 1)
+             : envScene ? vcm_create_sharded3(envScene, algorithm, radiusFactor, radiusAlpha, s, device, 0, 1)
              : loaded ? vcm_create_sharded2(vcm_scene_file_desc(loaded), algorithm, radiusFactor, radiusAlpha, s, device, 0, 1)
                       : vcm_create_sharded(&scene, algorithm, radiusFactor, radiusAlpha, s, device, 0, 1);
     };

@@ -11,10 +11,11 @@ vcm_make_camera, ... each of which computes the derived members exactly as the r
     r = VertexCM(scene, VertexCM.kVcm, 0.003, 0.75)          # more than 32 primitives: traced through a BVH
 """
 import ctypes as C
+import math
 
 import numpy as np
 
-from ._abi import Camera, EnvMap, Light, Material, Prim, SceneDesc2, SceneDesc3
+from ._abi import Camera, EnvMap, Light, Material, Prim, SceneDesc2, SceneDesc3, SceneDesc4, ThinLens
 
 
 def _f3(v):
@@ -49,6 +50,7 @@ class SceneBuilder:
         self.prims, self.materials, self.mat2light, self.lights = [], [], [], []
         self.background = -1
         self.envmap = None
+        self.lens = None
 
     # ---- materials (materials.hxx:33-65) ----
     def material(self, diffuse=(0, 0, 0), phong=(0, 0, 0), exponent=1.0, mirror=(0, 0, 0), ior=-1.0):
@@ -114,6 +116,17 @@ class SceneBuilder:
         self.background = len(self.lights) - 1
         self.envmap = img
 
+    # ---- the camera's lens ----
+    def thin_lens(self, aperture_radius, focus_distance):
+        """a thin lens instead of the pinhole (include/smallvcm_amd.h vcm_thin_lens): aperture radius >= 0 and focus
+        distance > 0 along the camera's forward axis, world units.  build() then returns a SceneDesc4."""
+        r, f = float(aperture_radius), float(focus_distance)
+        if not (math.isfinite(r) and r >= 0.0):
+            raise ValueError("thin_lens: aperture_radius must be finite and >= 0")
+        if not (math.isfinite(f) and f > 0.0):
+            raise ValueError("thin_lens: focus_distance must be finite and > 0")
+        self.lens = (r, f)
+
     # ---- the description ----
     def build(self, position, forward, up, fov_deg, resx, resy):
         d = SceneDesc2()
@@ -131,13 +144,22 @@ class SceneBuilder:
         if self.L.vcm_make_camera(_f3(position), _f3(forward), _f3(up), float(fov_deg), int(resx), int(resy), C.byref(d.camera)) != 0:
             raise ValueError("bad camera")
         d._keep = (prims, mats, m2l, lights)   # the arrays live as long as the description
-        if self.envmap is None:
+        if self.envmap is None and self.lens is None:
             return d
         d3 = SceneDesc3()
         d3.base = d
-        m = EnvMap()
-        m.height, m.width = int(self.envmap.shape[0]), int(self.envmap.shape[1])
-        m.rgb = self.envmap.ctypes.data_as(C.POINTER(C.c_float))
-        d3.envmap = C.pointer(m)
-        d3._keep = (d._keep, self.envmap, m)
-        return d3
+        d3._keep = (d._keep,)
+        if self.envmap is not None:
+            m = EnvMap()
+            m.height, m.width = int(self.envmap.shape[0]), int(self.envmap.shape[1])
+            m.rgb = self.envmap.ctypes.data_as(C.POINTER(C.c_float))
+            d3.envmap = C.pointer(m)
+            d3._keep = (d._keep, self.envmap, m)
+        if self.lens is None:
+            return d3
+        d4 = SceneDesc4()
+        d4.base = d3
+        lens = ThinLens(*self.lens)
+        d4.lens = C.pointer(lens)
+        d4._keep = (d3._keep, lens)
+        return d4
