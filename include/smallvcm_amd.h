@@ -164,6 +164,32 @@ typedef struct vcm_scene_desc4 {
     const vcm_thin_lens *lens;
 } vcm_scene_desc4;
 
+/* How a light is chosen where a path samples one (DESIGN.md "Light selection").  UNIFORM: every light with probability
+ * 1 / nLights, as the reference does.  POWER: in proportion to the flux the light emits (area: pi lum(intensity) area;
+ * point: 4 pi lum; directional: pi R^2 lum; background: 4 pi^2 R^2 lum scale; environment map: pi R^2 x the integral of
+ * lum(texel scale) over the sphere; lum = the reference's Luminance, R = the scene sphere's radius).  CUSTOM: in proportion
+ * to `weights` (nLights floats, finite, >= 0, not all zero; a zero weight is accepted only for a light that emits
+ * nothing).  uniformMix a in [0, 1] blends the normalised weights with the uniform choice over the lights of non-zero
+ * weight: w_i <- (1 - a) w_i / sum w + a / n'.  The probabilities are whole multiples of 2^-23 that sum to 1, at least one
+ * multiple for every light of non-zero weight, so a path's random float picks light i with exactly pmf[i]. */
+enum {
+    VCM_LIGHT_PICK_UNIFORM = 0,
+    VCM_LIGHT_PICK_POWER = 1,
+    VCM_LIGHT_PICK_CUSTOM = 2
+};
+typedef struct vcm_light_pick {
+    int          mode;
+    float        uniformMix;
+    const float *weights;      /* nLights floats, CUSTOM only */
+} vcm_light_pick;
+
+/* Scene description, version 5: a version-4 scene and how its lights are chosen.  `pick` NULL, or mode UNIFORM, renders
+ * exactly what vcm_create4 renders.  The weights are copied. */
+typedef struct vcm_scene_desc5 {
+    vcm_scene_desc4       base;
+    const vcm_light_pick *pick;
+} vcm_scene_desc5;
+
 /* VertexCM::AlgorithmType (src/vertexcm.hxx:182-204) -- same values */
 enum {
     VCM_ALGO_LIGHT_TRACE = 0,
@@ -256,6 +282,15 @@ vcm_ctx *vcm_create_sharded3(const vcm_scene_desc3 *scene, int algorithm,
 vcm_ctx *vcm_create4(const vcm_scene_desc4 *scene, int algorithm,
                      float radiusFactor, float radiusAlpha, int seed);
 vcm_ctx *vcm_create_sharded4(const vcm_scene_desc4 *scene, int algorithm,
+                             float radiusFactor, float radiusAlpha, int seed,
+                             int device, int rank, int worldSize);
+
+/* The same for a version-5 scene description (light selection).  NULL with vcm_last_error() for a bad mode, a
+ * uniformMix outside [0, 1] or not finite, bad CUSTOM weights, more than 2^23 lights of non-zero weight, or a bad
+ * version-4 scene. */
+vcm_ctx *vcm_create5(const vcm_scene_desc5 *scene, int algorithm,
+                     float radiusFactor, float radiusAlpha, int seed);
+vcm_ctx *vcm_create_sharded5(const vcm_scene_desc5 *scene, int algorithm,
                              float radiusFactor, float radiusAlpha, int seed,
                              int device, int rank, int worldSize);
 
@@ -472,7 +507,7 @@ void vcm_make_scene_sphere(const vcm_prim *prims, int nPrims, float *center3, fl
  * scene.hxx:132-398, is the only way a scene comes into being).  vcm_scene_load reads a `.vcmscene` text file --
  * directives processed in order: `obj <file>` (Wavefront OBJ triangles with their MTL library: Kd / Ks+Ns / illum /
  * Ni -> Material, Ke -> one AreaLight per triangle as in scene.hxx:333-361), `sphere`, `camera`, `light
- * point|directional|background|envmap`, `lens`, `mtllib` -- or a bare `.obj` (default camera), and builds the version-2 description
+ * point|directional|background|envmap`, `lens`, `lightpick`, `mtllib` -- or a bare `.obj` (default camera), and builds the version-2 description
  * with the vcm_make_* constructors above; smallvcm_amd/csrc/scene_file.cpp documents the format.  The description
  * points into the handle: keep it until the renderers are created (vcm_create2 copies).  NULL on failure, with the
  * reason in vcm_scene_load_error(). */
@@ -487,6 +522,9 @@ const vcm_scene_desc3 *vcm_scene_file_desc3(const vcm_scene_file *scene);
 /* The scene as a version-4 description: lens set when the file has a `lens <apertureRadius> <focusDistance>`
  * directive, NULL otherwise; its base is vcm_scene_file_desc3's.  Points into the handle, like vcm_scene_file_desc. */
 const vcm_scene_desc4 *vcm_scene_file_desc4(const vcm_scene_file *scene);
+/* The scene as a version-5 description: pick set when the file has a `lightpick uniform|power [uniformMix]` directive,
+ * NULL otherwise; its base is vcm_scene_file_desc4's.  Points into the handle, like vcm_scene_file_desc. */
+const vcm_scene_desc5 *vcm_scene_file_desc5(const vcm_scene_file *scene);
 
 /* Environment maps from files: Radiance RGBE (.hdr: "#?RADIANCE" / "#?RGBE", FORMAT=32-bit_rle_rgbe, "-Y H +X W", flat
  * or new-style run-length scanlines) or PFM (.pfm: "PF", either byte order; its bottom-up rows are flipped), picked by

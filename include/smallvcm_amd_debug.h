@@ -60,7 +60,10 @@ enum {
     VCM_KAT_LENS = 8,             /* in: raster x, y, lens sample u1, u2, world point -> ray origin, ray dir, cameraPdfW, raster
                                      of the world point through that lens point, valid (1: in front of the lens); needs a
                                      context with a thin lens (vcm_create4)                       DESIGN.md "Thin lens" */
-    VCM_KAT_OPS = 9
+    VCM_KAT_LIGHT_PICK = 9,       /* in: the pick's random float -> light index, its pmf; in[1] = a light index -> out[2] = the
+                                     pmf the emitter-hit sites use for it (pick_light / light_pick_prob)
+                                                                                                  DESIGN.md "Light selection" */
+    VCM_KAT_OPS = 10
 };
 int vcm_debug_kat(vcm_ctx *ctx, int op, int n, const float *in, float *out);
 

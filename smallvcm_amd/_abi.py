@@ -107,6 +107,26 @@ class SceneDesc4(C.Structure):
         return self.base.base.camera
 
 
+LIGHT_PICK_UNIFORM, LIGHT_PICK_POWER, LIGHT_PICK_CUSTOM = 0, 1, 2
+LIGHT_PICK_MODES = {"uniform": LIGHT_PICK_UNIFORM, "power": LIGHT_PICK_POWER, "custom": LIGHT_PICK_CUSTOM}
+
+
+class LightPick(C.Structure):
+    """vcm_light_pick: how lights are chosen (LIGHT_PICK_UNIFORM / _POWER / _CUSTOM), the share of the uniform choice
+    mixed in, and CUSTOM's nLights weights (include/smallvcm_amd.h)"""
+    _fields_ = [("mode", C.c_int), ("uniformMix", C.c_float), ("weights", C.POINTER(C.c_float))]
+
+
+class SceneDesc5(C.Structure):
+    """vcm_scene_desc5: a version-4 scene and an optional light-selection setting.  Like SceneDesc2 the arrays are owned
+    by the Python object that built it."""
+    _fields_ = [("base", SceneDesc4), ("pick", C.POINTER(LightPick))]
+
+    @property
+    def camera(self):
+        return self.base.base.base.camera
+
+
 class Stats(C.Structure):
     _fields_ = [("lightVertices", C.c_longlong), ("gridVertices", C.c_longlong),
                 ("lightRays", C.c_longlong), ("cameraRays", C.c_longlong),

@@ -21,6 +21,10 @@
 //       lens apertureRadius focusDistance                a thin lens instead of the pinhole, at most one: radius >= 0
 //                                                        and focus distance > 0 in world units, both finite, nothing
 //                                                        after them (vcm_scene_desc4, vcm_scene_file_desc4)
+//       lightpick uniform|power [uniformMix]             how a light is chosen where a path samples one, at most once:
+//                                                        with equal probability (the default) or by emitted power,
+//                                                        mixed with the share uniformMix in [0, 1] of the uniform
+//                                                        choice (vcm_light_pick, vcm_scene_desc5, vcm_scene_file_desc5)
 //   .obj        v, f (triangles; polygons are fanned around their first vertex; v, v/vt, v/vt/vn, v//vn; negative
 //               = relative indices), usemtl, mtllib; everything else is skipped
 //   .mtl        newmtl, Kd -> mDiffuseReflectance, Ks + Ns -> mPhongReflectance / mPhongExponent (materials.hxx:54-65),
@@ -60,6 +64,9 @@ struct vcm_scene_file {
     bool haveLens = false;            /* `lens` */
     vcm_thin_lens lens;
     vcm_scene_desc4 desc4;
+    bool havePick = false;            /* `lightpick` */
+    vcm_light_pick pick;
+    vcm_scene_desc5 desc5;
     ~vcm_scene_file() { vcm_envmap_free(envmap); }
 };
 
@@ -424,6 +431,23 @@ struct Loader {
                 if (!std::isfinite(x[1]) || !(x[1] > 0.f)) { ok = fail(at + ": lens focusDistance must be finite and > 0"); break; }
                 out->lens.apertureRadius = x[0]; out->lens.focusDistance = x[1];
                 out->haveLens = true;
+            } else if (key == "lightpick") {
+                const std::string mode = word(p);
+                if (mode != "uniform" && mode != "power") { ok = fail(at + ": lightpick uniform|power [uniformMix]"); break; }
+                if (out->havePick) { ok = fail(at + ": a second lightpick"); break; }
+                float mix = 0.f;
+                std::string rest = word(p);
+                if (!rest.empty() && rest[0] != '#') {
+                    char *e = NULL;
+                    mix = strtof(rest.c_str(), &e);
+                    if (e == rest.c_str() || *e) { ok = fail(at + ": lightpick uniform|power [uniformMix]"); break; }
+                    rest = word(p);
+                    if (!rest.empty() && rest[0] != '#') { ok = fail(at + ": lightpick uniform|power [uniformMix]"); break; }
+                }
+                if (!std::isfinite(mix) || mix < 0.f || mix > 1.f) { ok = fail(at + ": lightpick uniformMix must be finite and in [0, 1]"); break; }
+                out->pick.mode = mode == "power" ? VCM_LIGHT_PICK_POWER : VCM_LIGHT_PICK_UNIFORM;
+                out->pick.uniformMix = mix; out->pick.weights = NULL;
+                out->havePick = true;
             } else if (key == "light") {
                 const std::string kind = word(p);
                 vcm_light l;
@@ -470,6 +494,8 @@ struct Loader {
         out->desc3.envmap = out->envmap;
         out->desc4.base = out->desc3;
         out->desc4.lens = out->haveLens ? &out->lens : NULL;
+        out->desc5.base = out->desc4;
+        out->desc5.pick = out->havePick ? &out->pick : NULL;
         return true;
     }
 };
@@ -509,6 +535,7 @@ void vcm_scene_file_free(vcm_scene_file *s) { delete s; }
 
 const vcm_scene_desc3 *vcm_scene_file_desc3(const vcm_scene_file *s) { return s ? &s->desc3 : NULL; }
 const vcm_scene_desc4 *vcm_scene_file_desc4(const vcm_scene_file *s) { return s ? &s->desc4 : NULL; }
+const vcm_scene_desc5 *vcm_scene_file_desc5(const vcm_scene_file *s) { return s ? &s->desc5 : NULL; }
 
 vcm_envmap *vcm_envmap_load(const char *path)
 {

@@ -15,7 +15,9 @@
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
+#include <queue>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "vcm_core.h"
@@ -48,6 +50,13 @@ struct SceneHost {
     std::vector<int> envMargGuide, envCondGuide;
     /* the thin lens (scene_host_set_lens; lensRadius == 0: the pinhole), DScene::lensRadius ... */
     float lensRadius = 0.f, lensFocus = 1.f, lensRight[3] = { 0.f, 0.f, 0.f }, lensUp[3] = { 0.f, 0.f, 0.f };
+    /* how lights are chosen (scene_host_set_pick; pickMode UNIFORM: no tables), DScene::pickMode ...; pickWeights are
+       the weights before the mix and pickQuanta the m_i of pmf[i] = m_i 2^-23 (for reports and tests) */
+    int pickMode = VCM_LIGHT_PICK_UNIFORM, pickGuide = 0;
+    std::vector<float> pickPmf, pickCdf;
+    std::vector<int> pickGuideTable;
+    std::vector<double> pickWeights;
+    std::vector<int> pickQuanta;
 
     /* the view the device functions take, filled IN PLACE: the arrays are addressed relative to the DScene object
        itself (vcm_core.h), so `d` must stay where it is while it is in use (host emulation) */
@@ -65,6 +74,8 @@ struct SceneHost {
         d.offEnvTexels = (const char *)envTexels.data() - base; d.offEnvMarg = (const char *)envMarg.data() - base;
         d.offEnvCond = (const char *)envCond.data() - base; d.offEnvMargGuide = (const char *)envMargGuide.data() - base;
         d.offEnvCondGuide = (const char *)envCondGuide.data() - base;
+        d.offPickPmf = (const char *)pickPmf.data() - base; d.offPickCdf = (const char *)pickCdf.data() - base;
+        d.offPickGuide = (const char *)pickGuideTable.data() - base;
     }
     void fill_scalars(DScene &d) const
     {
@@ -85,6 +96,7 @@ struct SceneHost {
         d.envW = envW; d.envH = envH; d.envGuideW = envGuideW; d.envGuideH = envGuideH;
         d.lensRadius = lensRadius; d.lensFocus = lensFocus;
         for (int k = 0; k < 3; k++) { d.lensRight[k] = lensRight[k]; d.lensUp[k] = lensUp[k]; }
+        d.pickMode = pickMode; d.pickGuide = pickGuide;
         { const char *e = getenv("SMALLVCM_AMD_NO_RECTS"); if (e && e[0] == '1') d.nFastRects[0] = d.nFastRects[1] = d.nFastRects[2] = 0; }   /* measurement switch */
     }
 };
@@ -269,6 +281,129 @@ inline bool scene_host_set_lens(SceneHost &s, const vcm_thin_lens *lens, std::st
 inline bool scene_host_from_desc4(const vcm_scene_desc4 &sc, SceneHost &s, std::string &err)
 {
     return scene_host_from_desc3(sc.base, s, err) && scene_host_set_lens(s, sc.lens, err);
+}
+
+/* ---- light selection (vcm_core.h pick_light / light_pick_prob) ----
+ * POWER's weight of a light: the flux its Emit estimator integrates to, in binary64 (include/smallvcm_amd.h
+ * vcm_light_pick has the table).  The environment map's is pi R^2 x the sum over the texels of lum(texel scale) x the
+ * texel's solid angle (2 pi / W) (cos theta_top - cos theta_bottom); a constant map gives the background's value. */
+inline double scene_host_light_power(const SceneHost &s, int i)
+{
+    const double PI = 3.14159265358979323846;
+    const vcm_light &l = s.lights[(size_t)i];
+    const double lum = 0.212671 * l.intensity[0] + 0.715160 * l.intensity[1] + 0.072169 * l.intensity[2];   /* utils.hxx:36-41 */
+    const double R = s.sceneRadius;
+    double w = 0.0;
+    switch (l.type) {
+    case VCM_LIGHT_AREA: w = l.invArea > 0.f ? PI * lum / (double)l.invArea : 0.0; break;
+    case VCM_LIGHT_POINT: w = 4.0 * PI * lum; break;
+    case VCM_LIGHT_DIRECTIONAL: w = PI * R * R * lum; break;
+    case VCM_LIGHT_BACKGROUND: w = 4.0 * PI * PI * R * R * lum * (double)l.scale; break;
+    case VCM_LIGHT_ENVMAP: {
+        double sum = 0.0;
+        for (int r = 0; r < s.envH; r++) {
+            const double omega = (2.0 * PI / s.envW) * (std::cos(PI * r / s.envH) - std::cos(PI * (r + 1) / s.envH));
+            double row = 0.0;
+            for (int c = 0; c < s.envW; c++) {
+                const F4 &t = s.envTexels[(size_t)r * s.envW + c];   /* rgb * scale */
+                row += 0.212671 * t.x + 0.715160 * t.y + 0.072169 * t.z;
+            }
+            sum += row * omega;
+        }
+        w = PI * R * R * sum;
+    } break;
+    default: break;
+    }
+    return (w > 0.0 && std::isfinite(w)) ? w : 0.0;
+}
+
+/* Largest-remainder apportionment of 2^23 quanta to the weights (>= 0, not all zero, at most 2^23 of them non-zero):
+ * m_i = floor(w_i / sum w x 2^23), the quanta left over go to the largest remainders (ties: the lower index); then every
+ * light of non-zero weight that got none takes one from the light that holds the most at that moment. */
+inline void scene_host_apportion(const std::vector<double> &w, std::vector<int> &m)
+{
+    const long long Q = 1ll << 23;
+    const size_t n = w.size();
+    double total = 0.0;
+    for (double x : w) total += x;
+    m.assign(n, 0);
+    std::vector<std::pair<double, size_t>> frac;
+    long long used = 0;
+    for (size_t i = 0; i < n; i++) {
+        if (!(w[i] > 0.0)) continue;
+        const double q = w[i] / total * (double)Q;
+        long long f = (long long)std::floor(q);
+        f = f > Q ? Q : f;
+        m[i] = (int)f; used += f;
+        frac.push_back(std::make_pair(q - (double)f, i));
+    }
+    std::stable_sort(frac.begin(), frac.end(), [](const std::pair<double, size_t> &a, const std::pair<double, size_t> &b) { return a.first > b.first; });
+    for (size_t k = 0; used < Q; k = (k + 1) % frac.size()) { m[frac[k].second]++; used++; }
+    std::priority_queue<std::pair<int, long long>> big;   /* (quanta, -index): the most quanta, then the lower index */
+    long long need = 0;
+    for (size_t i = 0; i < n; i++) {
+        if (m[i] >= 2) big.push(std::make_pair(m[i], -(long long)i));
+        if (w[i] > 0.0 && m[i] == 0) need++;
+    }
+    need += used - Q;   /* (rounding may have handed out a quantum too many: taken back the same way) */
+    for (size_t i = 0; i < n; i++) if (w[i] > 0.0 && m[i] == 0) m[i] = 1;
+    for (; need > 0; need--) {
+        std::pair<int, long long> t = big.top(); big.pop();
+        m[(size_t)-t.second]--; t.first--;
+        if (t.first >= 2) big.push(t);
+    }
+}
+
+inline bool scene_host_set_pick(SceneHost &s, const vcm_light_pick *pick, std::string &err)
+{
+    s.pickMode = VCM_LIGHT_PICK_UNIFORM; s.pickGuide = 0;
+    s.pickPmf.clear(); s.pickCdf.clear(); s.pickGuideTable.clear(); s.pickWeights.clear(); s.pickQuanta.clear();
+    if (!pick) return true;
+    if (pick->mode != VCM_LIGHT_PICK_UNIFORM && pick->mode != VCM_LIGHT_PICK_POWER && pick->mode != VCM_LIGHT_PICK_CUSTOM) {
+        err = "light pick: mode must be VCM_LIGHT_PICK_UNIFORM, _POWER or _CUSTOM"; return false;
+    }
+    const float a = pick->uniformMix;
+    if (!std::isfinite(a) || a < 0.f || a > 1.f) { err = "light pick: uniformMix must be finite and in [0, 1]"; return false; }
+    if (pick->mode == VCM_LIGHT_PICK_UNIFORM) return true;
+    const size_t n = s.lights.size();
+    std::vector<double> w(n);
+    for (size_t i = 0; i < n; i++) w[i] = scene_host_light_power(s, (int)i);
+    if (pick->mode == VCM_LIGHT_PICK_CUSTOM) {
+        if (!pick->weights) { err = "light pick: CUSTOM needs weights"; return false; }
+        for (size_t i = 0; i < n; i++) {
+            const float x = pick->weights[i];
+            if (!std::isfinite(x) || x < 0.f) { err = "light pick: weights must be finite and >= 0"; return false; }
+            if (x == 0.f && w[i] > 0.0) { err = "light pick: a zero weight on a light that is not black (light tracing would lose it)"; return false; }
+            w[i] = x;
+        }
+    }
+    double total = 0.0;
+    size_t nz = 0;
+    for (double x : w) { total += x; if (x > 0.0) nz++; }
+    if (nz == 0 || !(total > 0.0) || !std::isfinite(total)) { err = "light pick: all weights are zero"; return false; }
+    if (nz > ((size_t)1 << 23)) { err = "light pick: more than 2^23 lights with non-zero weight"; return false; }
+    s.pickWeights = w;
+    std::vector<double> mixed(n, 0.0);
+    for (size_t i = 0; i < n; i++) if (w[i] > 0.0) mixed[i] = (1.0 - (double)a) * w[i] / total + (double)a / (double)nz;
+    scene_host_apportion(mixed, s.pickQuanta);
+    s.pickPmf.resize(n); s.pickCdf.resize(n + 1);
+    long long acc = 0;
+    s.pickCdf[0] = 0.f;
+    for (size_t i = 0; i < n; i++) {   /* whole multiples of 2^-23 up to 1: exact in binary32 */
+        s.pickPmf[i] = (float)s.pickQuanta[i] * 1.1920928955078125e-07f;
+        acc += s.pickQuanta[i];
+        s.pickCdf[i + 1] = (float)acc * 1.1920928955078125e-07f;
+    }
+    s.pickGuide = scene_host_env_guide_size((int)n);
+    s.pickGuideTable.resize((size_t)s.pickGuide + 1);
+    scene_host_env_guide(s.pickCdf.data(), (int)n, s.pickGuide, s.pickGuideTable.data());
+    s.pickMode = pick->mode;
+    return true;
+}
+
+inline bool scene_host_from_desc5(const vcm_scene_desc5 &sc, SceneHost &s, std::string &err)
+{
+    return scene_host_from_desc4(sc.base, s, err) && scene_host_set_pick(s, sc.pick, err);
 }
 
 /* ---- brute-force list: consecutive triangles in pairs, fields interleaved (vcm_core.h TriPair) ---- */

@@ -143,6 +143,19 @@ template <class S> using Pinhole = S;
                                       else LAUNCH_SC_W(c, Pinhole, K, __VA_ARGS__); } while (0)
 #define LAUNCH_SC_MODE_CAM(c, K, M, ...) do { if ((c)->lens) LAUNCH_SC_MODE_W(c, WithLens, K, M, __VA_ARGS__); \
                                               else LAUNCH_SC_MODE_W(c, Pinhole, K, M, __VA_ARGS__); } while (0)
+/* The kernels that choose a light or weigh an emitter hit: a scene with a light-pick table (vcm_scene_desc5) takes their
+   WithPick instantiations (vcm_core.h), over the lens kinds where the kernel also holds the camera vertex. */
+template <class S> using PickLens = WithPick<WithLens<S>>;
+#define LAUNCH_SC_PICK(c, K, ...) do { if ((c)->pick) LAUNCH_SC_W(c, WithPick, K, __VA_ARGS__); \
+                                       else LAUNCH_SC_W(c, Pinhole, K, __VA_ARGS__); } while (0)
+#define LAUNCH_SC_MODE_PICK(c, K, M, ...) do { if ((c)->pick) LAUNCH_SC_MODE_W(c, WithPick, K, M, __VA_ARGS__); \
+                                               else LAUNCH_SC_MODE_W(c, Pinhole, K, M, __VA_ARGS__); } while (0)
+#define LAUNCH_SC_CAM_PICK(c, K, ...) do { if (!(c)->pick) LAUNCH_SC_CAM(c, K, __VA_ARGS__); \
+                                           else if ((c)->lens) LAUNCH_SC_W(c, PickLens, K, __VA_ARGS__); \
+                                           else LAUNCH_SC_W(c, WithPick, K, __VA_ARGS__); } while (0)
+#define LAUNCH_SC_MODE_CAM_PICK(c, K, M, ...) do { if (!(c)->pick) LAUNCH_SC_MODE_CAM(c, K, M, __VA_ARGS__); \
+                                                   else if ((c)->lens) LAUNCH_SC_MODE_W(c, PickLens, K, M, __VA_ARGS__); \
+                                                   else LAUNCH_SC_MODE_W(c, WithPick, K, M, __VA_ARGS__); } while (0)
 
 #ifndef VCM_MERGE_DEFAULT
 #define VCM_MERGE_DEFAULT VCM_MERGE_PAIRS
@@ -206,6 +219,7 @@ struct vcm_ctx : Scratch {
     bool sceneRects;                  /* ... and is an axis-aligned rectangle: the SceneRects kernels */
     bool envMap;                      /* the scene's background is an environment map: the SceneRectsE / SceneListE / SceneBvhE kernels */
     bool lens;                        /* the camera is a thin lens: the WithLens kernels for the camera vertex (LAUNCH_SC_CAM) */
+    bool pick;                        /* lights are chosen from a table: the WithPick kernels (LAUNCH_SC_PICK ...) */
     bool intPhong;                    /* every Phong exponent in use is an integer in [1, 65536]: the kernels whose pow is the binary
                                          exponentiation alone (detmath.h); otherwise the SceneList / SceneBvhG kernels and the general merge */
     IterParams P;
@@ -479,7 +493,7 @@ static int ensure_device(vcm_ctx *c)
         HIPCHK(hipEventCreateWithFlags(&c->evGrid, hipEventDisableTiming));
         {   /* the scene in ONE device allocation: the DScene header, then the arrays it addresses by offset */
             const SceneHost &h = *c->scene;
-            struct Part { const void *src; size_t bytes; size_t off; } parts[18] = {
+            struct Part { const void *src; size_t bytes; size_t off; } parts[21] = {
                 { h.prims.data(), h.prims.size() * sizeof(vcm_prim), 0 }, { h.materials.data(), h.materials.size() * sizeof(vcm_material), 0 },
                 { h.mat2light.data(), h.mat2light.size() * sizeof(int), 0 }, { h.lights.data(), h.lights.size() * sizeof(vcm_light), 0 },
                 { h.ops.data(), h.ops.size() * sizeof(PrimOp), 0 }, { h.pairs.data(), h.pairs.size() * sizeof(TriPair), 0 },
@@ -489,7 +503,9 @@ static int ensure_device(vcm_ctx *c)
                 { h.fastRects.data(), h.fastRects.size() * sizeof(FastRect), 0 },
                 { h.envTexels.data(), h.envTexels.size() * sizeof(F4), 0 }, { h.envMarg.data(), h.envMarg.size() * sizeof(float), 0 },
                 { h.envCond.data(), h.envCond.size() * sizeof(float), 0 }, { h.envMargGuide.data(), h.envMargGuide.size() * sizeof(int), 0 },
-                { h.envCondGuide.data(), h.envCondGuide.size() * sizeof(int), 0 } };
+                { h.envCondGuide.data(), h.envCondGuide.size() * sizeof(int), 0 },
+                { h.pickPmf.data(), h.pickPmf.size() * sizeof(float), 0 }, { h.pickCdf.data(), h.pickCdf.size() * sizeof(float), 0 },
+                { h.pickGuideTable.data(), h.pickGuideTable.size() * sizeof(int), 0 } };
             size_t total = (sizeof(DScene) + 255) & ~(size_t)255;
             for (Part &p : parts) { p.off = total; total += (p.bytes + 255) & ~(size_t)255; }
             if (dalloc(&c->dSceneBlob, total + 256)) return -1;
@@ -511,6 +527,7 @@ static int ensure_device(vcm_ctx *c)
             view.offWide = (long long)parts[10].off; view.offLeafData = (long long)parts[11].off; view.offFastRects = (long long)parts[12].off;
             view.offEnvTexels = (long long)parts[13].off; view.offEnvMarg = (long long)parts[14].off; view.offEnvCond = (long long)parts[15].off;
             view.offEnvMargGuide = (long long)parts[16].off; view.offEnvCondGuide = (long long)parts[17].off;
+            view.offPickPmf = (long long)parts[18].off; view.offPickCdf = (long long)parts[19].off; view.offPickGuide = (long long)parts[20].off;
             c->dScene = reinterpret_cast<DScene *>(c->dSceneBlob);
             HIPCHK(hipMemcpy(c->dScene, &view, sizeof(DScene), hipMemcpyHostToDevice));
         }
@@ -760,6 +777,7 @@ static vcm_ctx *create_from_host(SceneHost *h, int algorithm, float radiusFactor
     c->scene = h;
     c->envMap = h->envW > 0;
     c->lens = h->lensRadius > 0.f;
+    c->pick = h->pickMode != VCM_LIGHT_PICK_UNIFORM;
     scene_host_build_accel(*h, scene_host_force_bvh());
     /* VertexCM::VertexCM vertexcm.hxx:222-244 */
     switch (algorithm) {
@@ -852,6 +870,16 @@ vcm_ctx *vcm_create_sharded4(const vcm_scene_desc4 *scene, int algorithm, float 
     return create_from_host(h, algorithm, radiusFactor, radiusAlpha, seed, device, rank, worldSize);
 }
 
+vcm_ctx *vcm_create_sharded5(const vcm_scene_desc5 *scene, int algorithm, float radiusFactor, float radiusAlpha,
+                             int seed, int device, int rank, int worldSize)
+{
+    if (!scene) { fail("vcm_create5", "scene is NULL"); return NULL; }
+    SceneHost *h = new (std::nothrow) SceneHost();
+    std::string err;
+    if (!h || !scene_host_from_desc5(*scene, *h, err)) { delete h; fail("vcm_create5", err.c_str()); return NULL; }
+    return create_from_host(h, algorithm, radiusFactor, radiusAlpha, seed, device, rank, worldSize);
+}
+
 /* Which device a renderer-per-host-core host puts its next renderer on (vcm_next_device).  The reference's driver
  * builds one renderer per host core and runs them concurrently (smallvcm.cxx:61-72, :99-108): on a multi-GPU node the
  * drop-in deals them round-robin over the visible devices -- every GPU renders whole iterations of its renderers
@@ -905,6 +933,11 @@ vcm_ctx *vcm_create3(const vcm_scene_desc3 *scene, int algorithm, float radiusFa
 vcm_ctx *vcm_create4(const vcm_scene_desc4 *scene, int algorithm, float radiusFactor, float radiusAlpha, int seed)
 {
     return vcm_create_sharded4(scene, algorithm, radiusFactor, radiusAlpha, seed, next_device(true), 0, 1);
+}
+
+vcm_ctx *vcm_create5(const vcm_scene_desc5 *scene, int algorithm, float radiusFactor, float radiusAlpha, int seed)
+{
+    return vcm_create_sharded5(scene, algorithm, radiusFactor, radiusAlpha, seed, next_device(true), 0, 1);
 }
 
 void vcm_destroy(vcm_ctx *c)
@@ -1245,10 +1278,10 @@ static int vcm_trace_light_impl(vcm_ctx *c)
     const bool wf = !c->strictOrder;
     if (!wf && join_splats(c)) return -1;   /* the fused K1 splats straight into dFb: behind a K5 the last (aside) iteration left in flight */
     if (wf)
-        LAUNCH_SC_MODE(c, k_light_trace, 1, dim3(blocks), dim3(VCM_TRACE_BLOCK), 0, c->stream, c->dScene, c->P, c->store,
+        LAUNCH_SC_MODE_PICK(c, k_light_trace, 1, dim3(blocks), dim3(VCM_TRACE_BLOCK), 0, c->stream, c->dScene, c->P, c->store,
                            c->dFb, c->dRngLight, c->dStats, chunk, take_stamps(c, c->stream), c->vs.count + 16, c->dHdr);
     else
-        LAUNCH_SC_MODE_CAM(c, k_light_trace, 0, dim3(blocks), dim3(VCM_TRACE_BLOCK), 0, c->stream, c->dScene, c->P, c->store,
+        LAUNCH_SC_MODE_CAM_PICK(c, k_light_trace, 0, dim3(blocks), dim3(VCM_TRACE_BLOCK), 0, c->stream, c->dScene, c->P, c->store,
                            c->dFb, c->dRngLight, c->dStats, chunk, take_stamps(c, c->stream), c->vs.count + 16, c->dHdr);
     HIPCHK(hipGetLastError());
     c->bboxFromLight = c->world == 1;   /* K1 keeps the box of what it stores (k_bbox, a pass of its own over the vertices, serves imported records) */
@@ -1645,7 +1678,7 @@ static int vcm_trace_camera_impl(vcm_ctx *c)
     if (mark(c, EV_CAMERA_K0)) return -1;
     if (c->renderer) {   /* PathTracer / EyeLight: colour + jittered pixel per path; K5 adds them in path order */
         if (c->renderer == 1)
-            LAUNCH_SC_CAM(c, k_path_trace, dim3(blocks), dim3(VCM_TRACE_BLOCK), 0, c->stream, c->dScene, c->P, c->dCamOut,
+            LAUNCH_SC_CAM_PICK(c, k_path_trace, dim3(blocks), dim3(VCM_TRACE_BLOCK), 0, c->stream, c->dScene, c->P, c->dCamOut,
                                c->dRngCam, c->dStats, chunk, take_stamps(c, c->stream), c->vs.count + 8);
         else
             LAUNCH_SC_CAM(c, k_eye_light, dim3(2048), dim3(256), 0, c->stream, c->dScene, c->P, c->dCamOut, c->dRngCam,
@@ -1667,7 +1700,7 @@ static int vcm_trace_camera_impl(vcm_ctx *c)
             if (c->prezeroed) HIPCHK(hipStreamWaitEvent(c->stream, c->evZero, 0));
             else if (zero_ranges(c->stream, c->dQueryCount, ((size_t)c->P.nBuckets + 1) * sizeof(int))) return -1;
         }
-        LAUNCH_SC_MODE_CAM(c, k_camera_trace, 1, dim3(blocks), dim3(VCM_TRACE_BLOCK), 0, c->stream, c->dScene, c->P,
+        LAUNCH_SC_MODE_CAM_PICK(c, k_camera_trace, 1, dim3(blocks), dim3(VCM_TRACE_BLOCK), 0, c->stream, c->dScene, c->P,
                            c->store, grid_of(c), c->vs, c->dCamOut, c->dCamMask, c->dRngCam, c->dStats, chunk, take_stamps(c, c->stream));
         if (mark(c, EV_CAMERA_K1)) return -1;
         if (c->useVC) {   /* K3b, K3c: dense DI / VC tasks */
@@ -1718,14 +1751,14 @@ static int vcm_trace_camera_impl(vcm_ctx *c)
                 HIPCHK(hipEventRecord(c->evSplatDone, c->splat));   /* also behind the light splats: same stream */
                 c->splatInFlight = true;
             }
-            LAUNCH_SC(c, k_connect_di, dim3(task_blocks(c->nLocal)), dim3(VCM_TASK_BLOCK), 0, c->stream, c->dScene, c->P, c->vs,
+            LAUNCH_SC_PICK(c, k_connect_di, dim3(task_blocks(c->nLocal)), dim3(VCM_TASK_BLOCK), 0, c->stream, c->dScene, c->P, c->vs,
                                c->dStats, c->scatteredInDI ? (const int *)c->dQueryStart : (const int *)NULL,
                                c->scatteredInDI ? c->dSortedVertex : (int *)NULL, take_stamps(c, c->stream));
         }
         if (mark(c, EV_CONNECT_K1)) return -1;
     } else {
         if (c->useVM && !c->gridBuilt) return fail("vcm_trace_camera", "strict mode merges inside the camera pass: call vcm_build_grid first");
-        LAUNCH_SC_MODE_CAM(c, k_camera_trace, 0, dim3(blocks), dim3(VCM_TRACE_BLOCK), 0, c->stream, c->dScene, c->P,
+        LAUNCH_SC_MODE_CAM_PICK(c, k_camera_trace, 0, dim3(blocks), dim3(VCM_TRACE_BLOCK), 0, c->stream, c->dScene, c->P,
                            c->store, grid_of(c), c->vs, c->dCamOut, c->dCamMask, c->dRngCam, c->dStats, chunk, take_stamps(c, c->stream));
         if (mark(c, EV_CAMERA_K1)) return -1;
         if (mark(c, EV_CONNECT_K1)) return -1;
@@ -2337,6 +2370,7 @@ template <class SC>
 __global__ void k_kat(const DScene *__restrict__ scp, int op, int n, const float *in, float *out)
 {
     stage_scene_tables(*scp);   /* before any thread leaves: it holds a barrier */
+    stage_pick_tables(*static_cast<const SC *>(scp));
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     float a[VCM_KAT_FLOATS], r[VCM_KAT_FLOATS];
@@ -2381,7 +2415,7 @@ int vcm_debug_kat(vcm_ctx *c, int op, int n, const float *in, float *out)
     HIPCHK(hipMalloc((void **)&din, bytes));
     HIPCHK(hipMalloc((void **)&dout, bytes));
     HIPCHK(hipMemcpy(din, in, bytes, hipMemcpyHostToDevice));
-    LAUNCH_SC_CAM(c, k_kat, dim3((n + 63) / 64), dim3(64), 0, 0, (const DScene *)c->dScene, op, n, (const float *)din, dout);
+    LAUNCH_SC_CAM_PICK(c, k_kat, dim3((n + 63) / 64), dim3(64), 0, 0, (const DScene *)c->dScene, op, n, (const float *)din, dout);
     hipError_t e = hipGetLastError();
     if (e == hipSuccess) e = hipMemcpy(out, dout, bytes, hipMemcpyDeviceToHost);
     (void)hipFree(din); (void)hipFree(dout);

@@ -368,6 +368,7 @@ struct DScene {
     static constexpr bool kIntPhong = false;
     static constexpr bool kEnvMap = false;
     static constexpr bool kLens = false;
+    static constexpr bool kPick = false;
     int nPrims, nMaterials, nLights, backgroundLight;
     float sceneCenter[3], sceneRadius, invSceneRadiusSqr;
     vcm_camera camera;
@@ -388,6 +389,11 @@ struct DScene {
     /* the thin lens (lensRadius == 0: the pinhole), built by scene_host.h: aperture radius, focus distance along the
        camera's forward axis, and the lens disc's orthonormal basis (lensRight = the raster +x direction) */
     float lensRadius, lensFocus, lensRight[3], lensUp[3];
+    /* how a light is chosen (vcm_light_pick; pickMode == VCM_LIGHT_PICK_UNIFORM: int(r * nLights), no table), built by
+       scene_host.h: pmf (nLights floats, whole multiples of 2^-23), cdf (nLights + 1 floats, cdf[0] = 0, cdf[nLights] = 1)
+       and the guide of the cdf (pickGuide + 1 ints, pickGuide = the power of two >= nLights; env_search) */
+    int pickMode, pickGuide;
+    long long offPickPmf, offPickCdf, offPickGuide;
     template <class T> VCM_HD const T *at(long long off) const { return reinterpret_cast<const T *>(reinterpret_cast<const char *>(this) + off); }
     VCM_HD const vcm_prim *prims() const { return at<vcm_prim>(offPrims); }
     VCM_HD const vcm_material *materials() const { return at<vcm_material>(offMaterials); }
@@ -407,6 +413,9 @@ struct DScene {
     VCM_HD const float *envCond() const { return at<float>(offEnvCond); }
     VCM_HD const int *envMargGuide() const { return at<int>(offEnvMargGuide); }
     VCM_HD const int *envCondGuide() const { return at<int>(offEnvCondGuide); }
+    VCM_HD const float *pickPmf() const { return at<float>(offPickPmf); }
+    VCM_HD const float *pickCdf() const { return at<float>(offPickCdf); }
+    VCM_HD const int *pickGuideTable() const { return at<int>(offPickGuide); }
 };
 /* Which of the two a scene carries, as a TYPE: every kernel that casts rays exists once per kind (the launch picks by
  * nNodes), so the brute-force kernels hold no traversal code and the BVH kernels no list loop.  Compiled together the
@@ -451,6 +460,19 @@ template <class S> struct WithLens : S { static constexpr bool kLens = true; };
 #else
 #define VCM_LENS_KIND(S) true
 #define VCM_LENS_ON(S, sc) ((sc).lensRadius > 0.f)
+#endif
+
+/* kPick: lights are chosen from a table (DScene::pickMode != UNIFORM).  Only the kernels that choose a light or weigh
+   an emitter hit (K1, K3, k_connect_di, the path tracer) and the known-answer kernel exist in these kinds, over each
+   kind above and over its WithLens kind; a scene with a table launches them there.  The host builds carry the branch
+   in every kind and take it at run time. */
+template <class S> struct WithPick : S { static constexpr bool kPick = true; };
+#if defined(__HIP_DEVICE_COMPILE__)
+#define VCM_PICK_KIND(S) (S::kPick)
+#define VCM_PICK_ON(S, sc) (S::kPick)
+#else
+#define VCM_PICK_KIND(S) true
+#define VCM_PICK_ON(S, sc) ((sc).pickMode != 0)
 #endif
 
 /* ---- the scene's small tables in LDS ----
@@ -559,6 +581,32 @@ VCM_HD vcm_light scene_light(const DScene &sc, int index)
     }
 #endif
     return sc.lights()[index];
+}
+
+/* The light-pick tables of a kPick kind (pick_light below): up to VCM_LDS_PICK lights the cdf and the pmf are copied to
+ * LDS words of their own -- an array only these kinds refer to, so every other kernel's LDS size stays what it was --
+ * and the search is a plain bisection there; beyond that room it is the guided search in global memory.  A kernel of
+ * such a kind calls stage_pick_tables() after stage_scene_tables(). */
+#define VCM_LDS_PICK 256
+#if defined(__HIP_DEVICE_COMPILE__)
+__shared__ uint32_t g_ldsPick[2 * VCM_LDS_PICK + 1];   /* cdf[0 .. n], then pmf[0 .. n-1] at VCM_LDS_PICK + 1 */
+#endif
+template <class S>
+VCM_HD void stage_pick_tables(const S &sc)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    if constexpr (S::kPick) {
+        if (sc.nLights <= VCM_LDS_PICK) {   /* wave-uniform */
+            const int t = (int)threadIdx.x, nt = (int)blockDim.x;
+            const uint32_t *cdf = (const uint32_t *)sc.pickCdf(), *pmf = (const uint32_t *)sc.pickPmf();
+            for (int i = t; i <= sc.nLights; i += nt) g_ldsPick[i] = cdf[i];
+            for (int i = t; i < sc.nLights; i += nt) g_ldsPick[VCM_LDS_PICK + 1 + i] = pmf[i];
+            __syncthreads();
+        }
+    }
+#else
+    (void)sc;
+#endif
 }
 
 
@@ -1900,6 +1948,59 @@ VCM_HD int env_search(const float *cdf, const int *guide, int G, float x)
     }
     return lo;
 }
+/* ---- light selection (DESIGN.md "Light selection") ----
+ * UNIFORM is the reference's int(r * lightCount) and 1 / lightCount (vertexcm.hxx:624-625, 669-672, 819-822,
+ * pathtracer.hxx:48-49, 140).  With a table the light is the largest i with cdf[i] <= r: the entries are multiples of
+ * 2^-23 and r is an odd multiple of 2^-24 (philox.h), so no sample equals an entry and light i is drawn with exactly
+ * pmf[i] = cdf[i + 1] - cdf[i]; a light of pmf 0 has an empty interval and is never returned.  An emitter HIT weighs
+ * the same light with the same pmf (light_pick_prob), so every strategy uses the same bits. */
+VCM_HD float pick_table_pmf(const DScene &sc, int i)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    if (sc.nLights <= VCM_LDS_PICK) return u2f(((const __attribute__((address_space(3))) uint32_t *)g_ldsPick)[VCM_LDS_PICK + 1 + i]);
+#endif
+    return sc.pickPmf()[i];
+}
+VCM_HD int pick_table_search(const DScene &sc, float r)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    if (sc.nLights <= VCM_LDS_PICK) {   /* wave-uniform */
+        const __attribute__((address_space(3))) uint32_t *cdf = (const __attribute__((address_space(3))) uint32_t *)g_ldsPick;
+        int lo = 0, hi = sc.nLights - 1;
+        while (lo < hi) {
+            const int mid = (lo + hi + 1) >> 1;
+            if (u2f(cdf[mid]) <= r) lo = mid; else hi = mid - 1;
+        }
+        return lo;
+    }
+#endif
+    return env_search(sc.pickCdf(), sc.pickGuideTable(), sc.pickGuide, r);
+}
+/* Both take the uniform choice's probability 1.f / lightCount, which every site computes where the reference does (the
+   code of the kinds without a table is then, instruction for instruction, what it was before there were tables).
+   pick_light: the light for the float r; lightPickProb holds 1 / lightCount on entry and the light's pmf on return. */
+template <class S>
+VCM_HD int pick_light(const S &sc, float r, float &lightPickProb)
+{
+    if (VCM_PICK_ON(S, sc)) {
+        const int lightID = pick_table_search(sc, r);
+        lightPickProb = pick_table_pmf(sc, lightID);
+        return lightID;
+    }
+    const int lightCount = sc.nLights;
+    return int(r * lightCount);
+}
+/* the probability with which pick_light returns lightID (clamped as get_light clamps it) */
+template <class S>
+VCM_HD float light_pick_prob(const S &sc, int lightID, float uniformPickProb)
+{
+    if (VCM_PICK_ON(S, sc)) {
+        lightID = (sc.nLights - 1 < lightID) ? sc.nLights - 1 : lightID;
+        return pick_table_pmf(sc, lightID);
+    }
+    return uniformPickProb;
+}
+
 /* the direction of (u, v) = the sampled texel + the fractions of r0 (row) and r1 (column) inside it; 2 floats */
 VCM_HD V3 env_sample_dir(const DScene &sc, float r0, float r1)
 {
@@ -2159,11 +2260,11 @@ template <class S>
 VCM_HD void generate_light_sample(const S &sc, const IterParams &P, PathRng &rng, SubPathState &st)
 {
     const int lightCount = sc.nLights;
-    const float lightPickProb = 1.f / lightCount;
+    float lightPickProb = 1.f / lightCount;
     float rnd[5];   /* :822-824 */
     rng_peek(rng, rng.k, rnd, 5);
     rng.k += 5u;
-    const int lightID = int(rnd[0] * lightCount);
+    const int lightID = pick_light(sc, rnd[0], lightPickProb);
     const float dx = rnd[1];
     const float dy = rnd[2];
     const float px = rnd[3];
@@ -2398,11 +2499,11 @@ VCM_HD void connect_stored_vertex_to_camera(const SC &sc, const IterParams &P, c
 
 /* GetLightRadiance :617-658 */
 template <class S>
-VCM_HD V3 get_light_radiance(const S &sc, const IterParams &P, const vcm_light &light,
+VCM_HD V3 get_light_radiance(const S &sc, const IterParams &P, const vcm_light &light, int lightID,
                              const SubPathState &st, V3 rayDir)
-{
+{   /* lightID: the index of `light`; a light the table never picks (pmf 0) emits nothing and returns at iszero() */
     const int lightCount = sc.nLights;
-    const float lightPickProb = 1.f / lightCount;
+    const float lightPickProb = light_pick_prob(sc, lightID, 1.f / lightCount);
     float directPdfA = 0.f, emissionPdfW = 0.f;
     const V3 radiance = light_get_radiance(light, sc, rayDir, directPdfA, emissionPdfW);
     if (iszero(radiance)) return sp3(0.f);
@@ -2422,8 +2523,8 @@ VCM_HD V3 direct_illumination(const SC &sc, const IterParams &P, float rPick, fl
 {   /* rPick, rx, ry: the three floats drawn at :672-673 */
     RC_DECL;
     const int lightCount = sc.nLights;
-    const float lightPickProb = 1.f / lightCount;
-    const int lightID = int(rPick * lightCount);
+    float lightPickProb = 1.f / lightCount;
+    const int lightID = pick_light(sc, rPick, lightPickProb);
     const vcm_light &light = get_light(sc, lightID);
     V3 directionToLight;
     float distance, directPdfW, emissionPdfW, cosAtLight;
@@ -3004,7 +3105,7 @@ VCM_HD bool camera_path_step(const SC &sc, const IterParams &P, CameraPath &cp, 
     if (!hitSomething) {   /* :434-447 */
         if (sc.backgroundLight >= 0) {
             if (st.pathLength >= P.minLen)
-                cp.color = cp.color + st.throughput * get_light_radiance(sc, P, sc.lights()[sc.backgroundLight], st, ray.dir);
+                cp.color = cp.color + st.throughput * get_light_radiance(sc, P, sc.lights()[sc.backgroundLight], sc.backgroundLight, st, ray.dir);
         }
         return false;
     }
@@ -3022,7 +3123,7 @@ VCM_HD bool camera_path_step(const SC &sc, const IterParams &P, CameraPath &cp, 
     if (isect.lightID >= 0) {   /* :468-479 */
         const vcm_light &light = get_light(sc, isect.lightID);
         if (st.pathLength >= P.minLen)
-            cp.color = cp.color + st.throughput * get_light_radiance(sc, P, light, st, ray.dir);
+            cp.color = cp.color + st.throughput * get_light_radiance(sc, P, light, isect.lightID, st, ray.dir);
         return false;
     }
     if (st.pathLength >= P.maxLen) return false;   /* :482 */
@@ -3297,7 +3398,7 @@ template <class SC>
 VCM_HD bool pt_path_step(const SC &sc, const IterParams &P, PtPath &pp, LaneStats &ls)
 {
     const int lightCount = sc.nLights;
-    const float lightPickProb = 1.f / lightCount;   /* :48-49 */
+    const float uniformPickProb = 1.f / lightCount;   /* :48-49 */
     Ray ray; ray.org = pp.org; ray.dir = pp.dir; ray.tmin = 0;
     Isect isect; isect.dist = 1e36f; isect.matID = 0; isect.lightID = -1; isect.normal = sp3(0.f); isect.prim = -1;
     ls.cameraRays++;
@@ -3308,7 +3409,7 @@ VCM_HD bool pt_path_step(const SC &sc, const IterParams &P, PtPath &pp, LaneStat
         const V3 contrib = light_get_radiance(sc.lights()[sc.backgroundLight], sc, ray.dir, directPdfW, emissionPdfW);
         if (iszero(contrib)) return false;
         float misWeight = 1.f;
-        if (pp.pathLength > 1 && !pp.lastSpecular) misWeight = mis2(pp.lastPdfW, directPdfW * lightPickProb);
+        if (pp.pathLength > 1 && !pp.lastSpecular) misWeight = mis2(pp.lastPdfW, directPdfW * light_pick_prob(sc, sc.backgroundLight, uniformPickProb));
         pp.color = pp.color + pp.weight * misWeight * contrib;
         return false;
     }
@@ -3326,7 +3427,7 @@ VCM_HD bool pt_path_step(const SC &sc, const IterParams &P, PtPath &pp, LaneStat
         float misWeight = 1.f;
         if (pp.pathLength > 1 && !pp.lastSpecular) {
             const float directPdfW = pdf_a_to_w(directPdfA, isect.dist, bsdf.localDirFix.z);   /* CosThetaFix, bsdf.hxx:263 */
-            misWeight = mis2(pp.lastPdfW, directPdfW * lightPickProb);
+            misWeight = mis2(pp.lastPdfW, directPdfW * light_pick_prob(sc, isect.lightID, uniformPickProb));
         }
         pp.color = pp.color + pp.weight * misWeight * contrib;
         return false;
@@ -3337,7 +3438,8 @@ VCM_HD bool pt_path_step(const SC &sc, const IterParams &P, PtPath &pp, LaneStat
         float rnd[3];
         rng_peek(pp.rng, pp.rng.k, rnd, 3);
         pp.rng.k += 3u;
-        const int lightID = int(rnd[0] * lightCount);
+        float lightPickProb = uniformPickProb;
+        const int lightID = pick_light(sc, rnd[0], lightPickProb);
         const vcm_light &light = get_light(sc, lightID);
         V3 directionToLight;
         float distance, directPdfW, emissionPdfW, cosAtLight;

@@ -102,6 +102,14 @@ VCM_HD void kat_eval(const SC &sc, int op, const float *in, float *out)
             if (lens_project(sc, org, ld3(in + 4), ip)) { out[7] = ip.x; out[8] = ip.y; out[9] = 1.f; }
         }
         break;
+    case VCM_KAT_LIGHT_PICK: {   /* pick_light / light_pick_prob (vcm_core.h): the table of the scene, or int(r * n) and 1 / n */
+        const int lightCount = sc.nLights;
+        float pmf = 1.f / lightCount;
+        const int lightID = pick_light(sc, in[0], pmf);
+        out[0] = (float)lightID; out[1] = pmf;
+        const int asked = (int)in[1];
+        out[2] = light_pick_prob(sc, asked < 0 ? 0 : asked, 1.f / lightCount);
+    } break;
     default: break;
     }
 }

@@ -138,6 +138,7 @@ k_light_trace(const DScene *__restrict__ scp, IterParams P, LightStore store, fl
     stamp_entry(st);
     const SC &sc = *static_cast<const SC *>(scp);
     stage_scene_tables(sc);
+    stage_pick_tables(sc);
     const unsigned lane = lane_id();
     WaveWork ww; wave_work_init(ww, chunk, P.nLocal);
     LaneStats ls; lane_stats_zero(ls);
@@ -206,6 +207,7 @@ k_camera_trace(const DScene *__restrict__ scp, IterParams P, LightStore store, G
     stamp_entry(st);
     const SC &sc = *static_cast<const SC *>(scp);
     stage_scene_tables(sc);
+    stage_pick_tables(sc);
     const unsigned lane = lane_id();
     WaveWork ww; wave_work_init(ww, chunk, P.nLocal);
     int *work = vs.count + 8;   /* the chunk counter of this launch (zeroed with the queue counts) */
@@ -267,6 +269,7 @@ k_path_trace(const DScene *__restrict__ scp, IterParams P, F4 *camOut, unsigned 
     stamp_entry(st);
     const SC &sc = *static_cast<const SC *>(scp);
     stage_scene_tables(sc);
+    stage_pick_tables(sc);
     const unsigned lane = lane_id();
     WaveWork ww; wave_work_init(ww, chunk, P.nLocal);
     LaneStats ls; lane_stats_zero(ls);
@@ -335,6 +338,7 @@ k_connect_di(const DScene *__restrict__ scp, IterParams P, VertexStore vs, unsig
     stamp_entry(st);
     const SC &sc = *static_cast<const SC *>(scp);
     stage_scene_tables(sc);
+    stage_pick_tables(sc);
     const int n = vs.count[1];
     LaneStats ls; lane_stats_zero(ls);
     for (int t = blockIdx.x * VCM_TASK_BLOCK + threadIdx.x; t < n; t += gridDim.x * VCM_TASK_BLOCK) {

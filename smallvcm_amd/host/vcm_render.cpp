@@ -11,6 +11,7 @@
 //              [--renderers R] [--radius-factor F] [--radius-alpha A]
 //              [--device D] [--strict] [--warmup W] [-o out.pfm] [--json] [--scene-file f.vcmscene|f.obj]
 //              [--envmap f.hdr|f.pfm [--envmap-scale S]] [--aperture R --focus D]
+//              [--light-pick uniform|power [--light-pick-mix A] [--light-pick-report]]
 //              [--gpus N [--shards S] [--inflight K] [--devices 0,1,..] [--collectives rccl|threads] [--same-window]]
 //
 // --gpus N: the multi-GPU host (vcm_farm.hpp): N ranks = N host threads, one per GPU, cut into N / S groups; a
@@ -24,6 +25,11 @@
 //
 // --aperture R --focus D: a thin lens of radius R focused at distance D along the camera's forward axis (world units;
 // vcm_scene_desc4), for a built-in scene or a scene file; they override a scene file's `lens` directive.
+//
+// --light-pick uniform|power: how a light is chosen where a path samples one (vcm_light_pick, vcm_scene_desc5): with
+// equal probability (the default) or by emitted power, --light-pick-mix A in [0, 1] of the uniform choice mixed in; they
+// override a scene file's `lightpick` directive.  The mode in effect is printed when it is not the default, and with
+// --light-pick-report the five most probable lights and their probabilities.
 //
 // -s / -a / -i keep the meaning they have in the reference's CLI
 // (src/config.hxx:246-395; scenes = g_SceneConfigs[0..3], :146-151).
@@ -43,9 +49,11 @@
 #include <cstring>
 #include <algorithm>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "smallvcm_amd.h"
+#include "smallvcm_amd_debug.h"
 #include "vcm_farm.hpp"
 
 static int die(const char *what)
@@ -79,6 +87,9 @@ int main(int argc, char **argv)
     float envScale = 1.f;
     float aperture = 0.f, focus = 0.f;
     bool haveAperture = false, haveFocus = false;
+    std::string pickName;
+    float pickMix = 0.f;
+    bool havePickMix = false, pickReport = false;
     for (int i = 1; i < argc; i++) {
         const std::string a(argv[i]);
         auto need = [&](int n) { if (i + n >= argc) { fprintf(stderr, "vcm_render: %s needs %d argument(s)\n", a.c_str(), n); exit(2); } };
@@ -111,6 +122,15 @@ int main(int argc, char **argv)
             if (e == argv[i] || *e) { fprintf(stderr, "vcm_render: %s needs a number\n", a.c_str()); return 2; }
             if (a == "--aperture") { aperture = v; haveAperture = true; } else { focus = v; haveFocus = true; }
         }
+        else if (a == "--light-pick") { need(1); pickName = argv[++i]; }
+        else if (a == "--light-pick-mix") {
+            need(1);
+            char *e = NULL;
+            pickMix = strtof(argv[++i], &e);
+            if (e == argv[i] || *e) { fprintf(stderr, "vcm_render: %s needs a number\n", a.c_str()); return 2; }
+            havePickMix = true;
+        }
+        else if (a == "--light-pick-report") pickReport = true;
         else if (a == "--strict") strict = 1;
         else if (a == "--json") json = 1;
         else { fprintf(stderr, "vcm_render: unknown option %s (see the header of vcm_render.cpp)\n", a.c_str()); return 2; }
@@ -120,6 +140,8 @@ int main(int argc, char **argv)
         return 2;
     }
     if (haveAperture != haveFocus) { fprintf(stderr, "vcm_render: --aperture and --focus go together\n"); return 2; }
+    if (!pickName.empty() && pickName != "uniform" && pickName != "power") { fprintf(stderr, "vcm_render: --light-pick uniform|power\n"); return 2; }
+    if (havePickMix && pickName.empty()) { fprintf(stderr, "vcm_render: --light-pick-mix goes with --light-pick\n"); return 2; }
 
     vcm_scene_desc scene;
     if (vcm_scene_cornell(resX, resY, vcm_scene_config_mask(sceneID), &scene)) return die("vcm_scene_cornell");
@@ -179,8 +201,39 @@ int main(int argc, char **argv)
         lensDesc.lens = lens;
         lensScene = &lensDesc;
     }
+    // light selection (--light-pick, else a scene file's `lightpick`): the scene as a version-5 description
+    vcm_light_pick flagPick;
+    flagPick.mode = pickName == "power" ? VCM_LIGHT_PICK_POWER : VCM_LIGHT_PICK_UNIFORM;
+    flagPick.uniformMix = pickMix; flagPick.weights = NULL;
+    const vcm_light_pick *pick = !pickName.empty() ? &flagPick : loaded ? vcm_scene_file_desc5(loaded)->pick : NULL;
+    if (pick && pick->mode == VCM_LIGHT_PICK_UNIFORM && gpus > 0) pick = NULL;   // the uniform choice is what the farm does
+    vcm_scene_desc5 pickDesc;
+    const vcm_scene_desc5 *pickScene = NULL;
+    if (pick) {
+        if (gpus > 0) { fprintf(stderr, "vcm_render: --light-pick with --gpus is not supported (the farm takes version-1 scenes)\n"); return 2; }
+        memset(&pickDesc, 0, sizeof(pickDesc));
+        if (lensScene) pickDesc.base = *lensScene;
+        else {
+            if (envScene) pickDesc.base.base = *envScene;
+            else if (loaded) pickDesc.base.base = *vcm_scene_file_desc3(loaded);
+            else {   // the built-in scene as a version-2 description (the arrays stay in `scene`)
+                vcm_scene_desc2 &b = pickDesc.base.base.base;
+                b.nPrims = scene.nPrims; b.prims = scene.prims;
+                b.nMaterials = scene.nMaterials; b.materials = scene.materials; b.mat2light = scene.mat2light;
+                b.nLights = scene.nLights; b.lights = scene.lights;
+                b.backgroundLight = scene.backgroundLight;
+                memcpy(b.sceneCenter, scene.sceneCenter, sizeof(b.sceneCenter));
+                b.sceneRadius = scene.sceneRadius; b.invSceneRadiusSqr = scene.invSceneRadiusSqr;
+                b.camera = scene.camera;
+            }
+            pickDesc.base.lens = NULL;
+        }
+        pickDesc.pick = pick;
+        pickScene = &pickDesc;
+    }
     auto create = [&](int s) {
-        return lensScene ? vcm_create_sharded4(lensScene, algorithm, radiusFactor, radiusAlpha, s, device, 0, 1)
+        return pickScene ? vcm_create_sharded5(pickScene, algorithm, radiusFactor, radiusAlpha, s, device, 0, 1)
+             : lensScene ? vcm_create_sharded4(lensScene, algorithm, radiusFactor, radiusAlpha, s, device, 0, 1)
              : envScene ? vcm_create_sharded3(envScene, algorithm, radiusFactor, radiusAlpha, s, device, 0, 1)
              : loaded ? vcm_create_sharded2(vcm_scene_file_desc(loaded), algorithm, radiusFactor, radiusAlpha, s, device, 0, 1)
                       : vcm_create_sharded(&scene, algorithm, radiusFactor, radiusAlpha, s, device, 0, 1);
@@ -220,6 +273,19 @@ int main(int argc, char **argv)
         r[g] = create(seed + g);
         if (!r[g]) return die("vcm_create");
         if (strict && vcm_set_strict_order(r[g], 1)) return die("vcm_set_strict_order");
+    }
+    if (pick && (pick->mode != VCM_LIGHT_PICK_UNIFORM || pickReport) && !json) {
+        const int nLights = pickScene->base.base.base.nLights;
+        printf("light pick: %s, uniform mix %g, %d light(s)\n", pick->mode == VCM_LIGHT_PICK_POWER ? "power" : "uniform", pick->uniformMix, nLights);
+        if (pickReport) {   // every light's probability through the known-answer op, the five largest printed
+            std::vector<float> in((size_t)nLights * VCM_KAT_FLOATS, 0.f), res(in.size());
+            for (int l = 0; l < nLights; l++) { in[(size_t)l * VCM_KAT_FLOATS] = 0.5f; in[(size_t)l * VCM_KAT_FLOATS + 1] = (float)l; }
+            if (vcm_debug_kat(r[0], VCM_KAT_LIGHT_PICK, nLights, in.data(), res.data())) return die("vcm_debug_kat");
+            std::vector<std::pair<float, int>> top;
+            for (int l = 0; l < nLights; l++) top.push_back(std::make_pair(-res[(size_t)l * VCM_KAT_FLOATS + 2], l));
+            std::sort(top.begin(), top.end());
+            for (size_t k = 0; k < top.size() && k < 5; k++) printf("  light %d: pmf %.7g\n", top[k].second, -top[k].first);
+        }
     }
     // untimed warm-up on a throw-away renderer: allocations, first-launch costs
     if (warmup > 0) {

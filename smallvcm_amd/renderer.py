@@ -21,7 +21,7 @@ import os
 
 import numpy as np
 
-from ._abi import (SceneDesc, SceneDesc2, SceneDesc3, SceneDesc4, Stats, SCENE_CONFIGS, VCM_MERGE_RECORD_FLOATS, ALGO_LIGHT_TRACE, ALGO_PPM, ALGO_BPM,
+from ._abi import (SceneDesc, SceneDesc2, SceneDesc3, SceneDesc4, SceneDesc5, Stats, SCENE_CONFIGS, VCM_MERGE_RECORD_FLOATS, ALGO_LIGHT_TRACE, ALGO_PPM, ALGO_BPM,
                    ALGO_BPT, ALGO_VCM)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -62,6 +62,9 @@ def load_library(require_gpu=True):
                                           C.c_int, C.c_int]
         L.vcm_create_sharded4.restype = vp
         L.vcm_create_sharded4.argtypes = [C.POINTER(SceneDesc4), C.c_int, C.c_float, C.c_float, C.c_int, C.c_int,
+                                          C.c_int, C.c_int]
+        L.vcm_create_sharded5.restype = vp
+        L.vcm_create_sharded5.argtypes = [C.POINTER(SceneDesc5), C.c_int, C.c_float, C.c_float, C.c_int, C.c_int,
                                           C.c_int, C.c_int]
         L.vcm_destroy.argtypes = [vp]
         L.vcm_destroy.restype = None
@@ -141,7 +144,8 @@ class HipBackend:
         self.resx = int(scene.camera.resolution[0])
         self.resy = int(scene.camera.resolution[1])
         self.N = self.resx * self.resy
-        create = (self.L.vcm_create_sharded4 if isinstance(scene, SceneDesc4) else
+        create = (self.L.vcm_create_sharded5 if isinstance(scene, SceneDesc5) else
+                  self.L.vcm_create_sharded4 if isinstance(scene, SceneDesc4) else
                   self.L.vcm_create_sharded3 if isinstance(scene, SceneDesc3) else
                   self.L.vcm_create_sharded2 if isinstance(scene, SceneDesc2) else self.L.vcm_create_sharded)
         self.ctx = create(C.byref(scene), algorithm, radius_factor, radius_alpha, seed, device, rank, world)

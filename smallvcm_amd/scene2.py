@@ -15,7 +15,8 @@ import math
 
 import numpy as np
 
-from ._abi import Camera, EnvMap, Light, Material, Prim, SceneDesc2, SceneDesc3, SceneDesc4, ThinLens
+from ._abi import (Camera, EnvMap, Light, LightPick, Material, Prim, SceneDesc2, SceneDesc3, SceneDesc4, SceneDesc5, ThinLens,
+                   LIGHT_PICK_CUSTOM, LIGHT_PICK_MODES)
 
 
 def _f3(v):
@@ -51,6 +52,7 @@ class SceneBuilder:
         self.background = -1
         self.envmap = None
         self.lens = None
+        self.pick = None
 
     # ---- materials (materials.hxx:33-65) ----
     def material(self, diffuse=(0, 0, 0), phong=(0, 0, 0), exponent=1.0, mirror=(0, 0, 0), ior=-1.0):
@@ -127,6 +129,27 @@ class SceneBuilder:
             raise ValueError("thin_lens: focus_distance must be finite and > 0")
         self.lens = (r, f)
 
+    # ---- how lights are chosen ----
+    def light_pick(self, mode="power", uniform_mix=0.0, weights=None):
+        """how a light is chosen where a path samples one (include/smallvcm_amd.h vcm_light_pick): "uniform", "power"
+        (by emitted flux) or "custom" (by `weights`, one per light: finite, >= 0, not all zero), with the share
+        uniform_mix in [0, 1] of the uniform choice mixed in.  build() then returns a SceneDesc5."""
+        if mode not in LIGHT_PICK_MODES:
+            raise ValueError("light_pick: mode must be 'uniform', 'power' or 'custom'")
+        a = float(uniform_mix)
+        if not (math.isfinite(a) and 0.0 <= a <= 1.0):
+            raise ValueError("light_pick: uniform_mix must be finite and in [0, 1]")
+        w = None
+        if LIGHT_PICK_MODES[mode] == LIGHT_PICK_CUSTOM:
+            if weights is None:
+                raise ValueError("light_pick: mode 'custom' needs weights")
+            w = np.ascontiguousarray(weights, np.float32).reshape(-1)
+            if not (np.all(np.isfinite(w)) and np.all(w >= 0) and np.any(w > 0)):
+                raise ValueError("light_pick: weights must be finite, >= 0 and not all zero")
+        elif weights is not None:
+            raise ValueError("light_pick: weights go with mode 'custom'")
+        self.pick = (LIGHT_PICK_MODES[mode], a, w)
+
     # ---- the description ----
     def build(self, position, forward, up, fov_deg, resx, resy):
         d = SceneDesc2()
@@ -144,7 +167,7 @@ class SceneBuilder:
         if self.L.vcm_make_camera(_f3(position), _f3(forward), _f3(up), float(fov_deg), int(resx), int(resy), C.byref(d.camera)) != 0:
             raise ValueError("bad camera")
         d._keep = (prims, mats, m2l, lights)   # the arrays live as long as the description
-        if self.envmap is None and self.lens is None:
+        if self.envmap is None and self.lens is None and self.pick is None:
             return d
         d3 = SceneDesc3()
         d3.base = d
@@ -155,11 +178,23 @@ class SceneBuilder:
             m.rgb = self.envmap.ctypes.data_as(C.POINTER(C.c_float))
             d3.envmap = C.pointer(m)
             d3._keep = (d._keep, self.envmap, m)
-        if self.lens is None:
+        if self.lens is None and self.pick is None:
             return d3
         d4 = SceneDesc4()
         d4.base = d3
-        lens = ThinLens(*self.lens)
-        d4.lens = C.pointer(lens)
-        d4._keep = (d3._keep, lens)
-        return d4
+        d4._keep = (d3._keep,)
+        if self.lens is not None:
+            lens = ThinLens(*self.lens)
+            d4.lens = C.pointer(lens)
+            d4._keep = (d3._keep, lens)
+        if self.pick is None:
+            return d4
+        mode, mix, w = self.pick
+        if w is not None and len(w) != len(self.lights):
+            raise ValueError("light_pick: %d weights for %d lights" % (len(w), len(self.lights)))
+        d5 = SceneDesc5()
+        d5.base = d4
+        pick = LightPick(mode, mix, w.ctypes.data_as(C.POINTER(C.c_float)) if w is not None else None)
+        d5.pick = C.pointer(pick)
+        d5._keep = (d4._keep, pick, w)
+        return d5
