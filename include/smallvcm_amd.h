@@ -533,6 +533,43 @@ const vcm_scene_desc5 *vcm_scene_file_desc5(const vcm_scene_file *scene);
 vcm_envmap *vcm_envmap_load(const char *path);
 void vcm_envmap_free(vcm_envmap *map);
 
+/* ---- first-hit feature buffers and the edge-avoiding denoiser ----
+ * vcm_render_features casts one ray through the CENTRE of every pixel of the context's local path range -- from the
+ * pinhole, also where the scene has a thin lens -- and keeps, per pixel,
+ *   VCM_FEATURE_NORMAL  the hit's geometric normal as the closest-hit routine returns it; (0, 0, 0) on a miss
+ *   VCM_FEATURE_DEPTH   the distance along the ray; 0 on a miss (no hit has distance 0)
+ *   VCM_FEATURE_ALBEDO  clamp(diffuse + phong + mirror, 0, 1) of the hit's material; (1, 1, 1) where it refracts, on an
+ *                       emitter and on a miss; a component that comes out 0 becomes 1
+ * (mirror and glass chains are NOT followed to the first rough surface: what is seen in them is smoothed).  A sharded
+ * context fills its own pixel range and leaves the rest of the frame 0.
+ * vcm_denoise filters framebuffer * scale with the edge-avoiding a-trous wavelet of Dammertz et al. 2010: pass i of
+ * `passes` applies the 5 x 5 B3-spline kernel with taps 2^i pixels apart, a tap's weight multiplied by
+ *   max(0, n_p . n_q)^sigmaNormal,  f((|z_p - z_q| / (sigmaDepth max(z_p, z_q)))^2)  and  f(|c_p - c_q|^2 / sigmaColor_i^2),
+ * f(x) = 1 / (1 + x / 4)^4, sigmaColor_i = sigmaColor / 2^i; misses match only misses; a non-finite tap counts 0, a
+ * non-finite centre passes through.  demodulate: the input is divided by the albedo before the first pass and
+ * multiplied back after the last.  passes = 0 copies the input; passes outside [0, 12] and sigmas that are not finite
+ * and positive are refused.  It renders the features first if they are not there, and it leaves the framebuffer alone.
+ * Memory: a context keeps, from its first vcm_render_features / vcm_denoise to vcm_destroy, two float4 feature images
+ * and three float4 colour images (the two the passes ping-pong between and the result): 5 x 16 bytes per pixel, of
+ * which the ping-pong pair is 128 MB at 2048^2.
+ * vcm_denoise, vcm_read_denoised, vcm_denoised_device and vcm_read_denoised_image refuse a sharded context (its
+ * framebuffer is a shard of the image): such a host gathers the features, reduces the frame and calls
+ * vcm_denoise_buffers, which needs no context: float4 images on `device` (colour rgb?, albedo rgb1, guide
+ * normal.xyz|depth), asynchronous on `hipStream`; outDev must not be one of the inputs.  Its two scratch images come
+ * from hipMallocAsync / hipFreeAsync on that stream. */
+typedef struct vcm_denoise_params { int passes; float sigmaColor, sigmaNormal, sigmaDepth; int demodulate; } vcm_denoise_params;
+void vcm_denoise_defaults(vcm_denoise_params *out);               /* passes 5, demodulate 1, the sigmas DESIGN.md "Denoising" chose */
+enum { VCM_FEATURE_ALBEDO = 0, VCM_FEATURE_NORMAL = 1, VCM_FEATURE_DEPTH = 2 };
+int vcm_render_features(vcm_ctx *ctx);                            /* asynchronous on the context's stream; needs no iteration */
+int vcm_read_feature(vcm_ctx *ctx, int which, float *host);       /* W*H*3 floats (albedo, normal) or W*H (depth) */
+int vcm_features_device(vcm_ctx *ctx, void **albedoDev, void **guideDev);   /* the two W*H float4 images */
+int vcm_denoise(vcm_ctx *ctx, float scale, const vcm_denoise_params *p);
+int vcm_read_denoised(vcm_ctx *ctx, float *rgbHost);              /* W*H*3 floats */
+int vcm_denoised_device(vcm_ctx *ctx, void **devPtr);             /* W*H float4 */
+int vcm_read_denoised_image(vcm_ctx *ctx, int format, float gamma, unsigned char *outHost);  /* BGR8 / RGBE as vcm_read_image */
+int vcm_denoise_buffers(int device, int width, int height, const void *colorDev, const void *albedoDev,
+                        const void *guideDev, void *outDev, const vcm_denoise_params *p, void *hipStream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -127,6 +127,17 @@ class SceneDesc5(C.Structure):
         return self.base.base.base.camera
 
 
+class DenoiseParams(C.Structure):
+    """vcm_denoise_params: a-trous passes (0 .. 12), the three edge-stopping sigmas, and whether the albedo is divided
+    out before the first pass and multiplied back after the last (include/smallvcm_amd.h)"""
+    _fields_ = [("passes", C.c_int), ("sigmaColor", C.c_float), ("sigmaNormal", C.c_float), ("sigmaDepth", C.c_float),
+                ("demodulate", C.c_int)]
+
+
+FEATURE_ALBEDO, FEATURE_NORMAL, FEATURE_DEPTH = 0, 1, 2
+FEATURES = {"albedo": FEATURE_ALBEDO, "normal": FEATURE_NORMAL, "depth": FEATURE_DEPTH}
+
+
 class Stats(C.Structure):
     _fields_ = [("lightVertices", C.c_longlong), ("gridVertices", C.c_longlong),
                 ("lightRays", C.c_longlong), ("cameraRays", C.c_longlong),

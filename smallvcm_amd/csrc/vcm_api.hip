@@ -19,6 +19,7 @@
 #include "vcm_kernels.h"
 #include "vcm_kat.h"
 #include "scene_host.h"
+#include "vcm_denoise.h"
 
 using namespace vcm;
 
@@ -222,6 +223,10 @@ struct vcm_ctx : Scratch {
     bool pick;                        /* lights are chosen from a table: the WithPick kernels (LAUNCH_SC_PICK ...) */
     bool intPhong;                    /* every Phong exponent in use is an integer in [1, 65536]: the kernels whose pow is the binary
                                          exponentiation alone (detmath.h); otherwise the SceneList / SceneBvhG kernels and the general merge */
+    /* feature buffers and denoiser (vcm_denoise.h): allocated by the first vcm_render_features / vcm_denoise */
+    F4 *dGuide, *dAlbedo;             /* N each: normal.xyz | depth, albedo.rgb | 1 */
+    F4 *dDnA, *dDnB, *dDenoised;      /* N each: the two images the passes ping-pong between, the result */
+    bool featuresValid, denoisedValid;
     IterParams P;
     bool inIteration;
     hipEvent_t ev[EV_COUNT];
@@ -978,6 +983,7 @@ void vcm_destroy(vcm_ctx *c)
     if (c->deviceReady) {
         DFREE(c->dSpaceMatrix); DFREE(c->dSpaceScanned); DFREE(c->dSpaceTotals); DFREE(c->dSpaceHist); DFREE(c->dWhereDest); DFREE(c->dWherePos);
         DFREE(c->fQ); DFREE(c->fRes); DFREE(c->fKey); DFREE(c->fArrival); DFREE(c->fSorted); DFREE(c->fCount);
+        DFREE(c->dGuide); DFREE(c->dAlbedo); DFREE(c->dDnA); DFREE(c->dDnB); DFREE(c->dDenoised);
         c->dScene = NULL; DFREE(c->dSceneBlob); DFREE(c->dFb); DFREE(c->dRngLight); DFREE(c->dRngCam); DFREE(c->dHdr); DFREE(c->dStatsRing); DFREE(c->dStamps);
         for (int i = 0; i < EV_COUNT; i++) (void)hipEventDestroy(c->ev[i]);
         (void)hipStreamSynchronize(c->side);
@@ -2227,6 +2233,166 @@ int vcm_clear_framebuffer(vcm_ctx *c)
     if (use_device(c)) return -1;
     if (join_splats(c)) return -1;
     HIPCHK(hipMemsetAsync(c->dFb, 0, (size_t)c->N * 3 * sizeof(float), c->stream));
+    return 0;
+}
+
+/* ---- feature buffers and denoiser (kernels: vcm_denoise.hip) ---- */
+void vcm_denoise_defaults(vcm_denoise_params *out)
+{
+    if (!out) return;
+    out->passes = 5; out->sigmaColor = VCM_DN_DEFAULT_SIGMA_COLOR; out->sigmaNormal = VCM_DN_DEFAULT_SIGMA_NORMAL;
+    out->sigmaDepth = VCM_DN_DEFAULT_SIGMA_DEPTH; out->demodulate = 1;
+}
+
+static int ensure_feature_buffers(vcm_ctx *c)
+{
+    if (c->dGuide) return 0;
+    if (dalloc(&c->dGuide, (size_t)c->N) || dalloc(&c->dAlbedo, (size_t)c->N)) return -1;
+    HIPCHK(hipMemsetAsync(c->dGuide, 0, (size_t)c->N * sizeof(F4), c->stream));   /* a sharded context fills its own range only */
+    HIPCHK(hipMemsetAsync(c->dAlbedo, 0, (size_t)c->N * sizeof(F4), c->stream));
+    return 0;
+}
+
+int vcm_render_features(vcm_ctx *c)
+{
+    if (!c) return fail("vcm_render_features", "ctx is NULL");
+    g_hipFailed = false;
+    if (ensure_device(c)) return -1;
+    if (ensure_feature_buffers(c)) return -1;
+    const DnSceneKind kind = { c->envMap, !c->scene->nodes.empty(), c->intPhong, c->sceneRects, c->sceneQuads };
+    HIPCHK(dn_launch_features(c->dScene, kind, c->resX, c->p0, c->nLocal, c->dGuide, c->dAlbedo, c->stream));
+    c->featuresValid = true;
+    return 0;
+}
+
+/* n pixels x nComp floats of the float4 image `src`, from component comp0 on, to the host */
+static int read_f4_components(vcm_ctx *c, const char *who, const F4 *src, int comp0, int nComp, float *host)
+{
+    float *d = NULL;
+    if (dalloc(&d, (size_t)c->N * nComp)) return -1;
+    hipError_t e = dn_launch_unpack(c->N, src, comp0, nComp, d, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(host, d, (size_t)c->N * nComp * sizeof(float), hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    (void)hipFree(d);
+    if (e != hipSuccess) { g_hipFailed = true; return fail(who, hipGetErrorString(e)); }
+    return 0;
+}
+
+int vcm_read_feature(vcm_ctx *c, int which, float *host)
+{
+    if (!c || !host) return fail("vcm_read_feature", "NULL argument");
+    if (which != VCM_FEATURE_ALBEDO && which != VCM_FEATURE_NORMAL && which != VCM_FEATURE_DEPTH) return fail("vcm_read_feature", "unknown feature");
+    g_hipFailed = false;
+    if (!c->featuresValid && vcm_render_features(c)) return -1;
+    if (use_device(c)) return -1;
+    if (which == VCM_FEATURE_ALBEDO) return read_f4_components(c, "vcm_read_feature", c->dAlbedo, 0, 3, host);
+    if (which == VCM_FEATURE_NORMAL) return read_f4_components(c, "vcm_read_feature", c->dGuide, 0, 3, host);
+    return read_f4_components(c, "vcm_read_feature", c->dGuide, 3, 1, host);
+}
+
+int vcm_features_device(vcm_ctx *c, void **albedoDev, void **guideDev)
+{
+    if (!c || !albedoDev || !guideDev) return fail("vcm_features_device", "NULL argument");
+    g_hipFailed = false;
+    if (!c->featuresValid && vcm_render_features(c)) return -1;
+    *albedoDev = c->dAlbedo; *guideDev = c->dGuide;
+    return 0;
+}
+
+static int refuse_sharded(vcm_ctx *c, const char *who)
+{
+    if (c->world > 1) return fail(who, "sharded context: its framebuffer is a shard of the image; gather the features, reduce the "
+                                       "frame and call vcm_denoise_buffers");
+    return 0;
+}
+
+int vcm_denoise(vcm_ctx *c, float scale, const vcm_denoise_params *p)
+{
+    if (!c) return fail("vcm_denoise", "ctx is NULL");
+    if (refuse_sharded(c, "vcm_denoise")) return -1;
+    if (const char *why = dn_check_params(p)) return fail("vcm_denoise", why);
+    if (!dn_finite(scale)) return fail("vcm_denoise", "scale is not finite");
+    g_hipFailed = false;
+    if (!c->featuresValid && vcm_render_features(c)) return -1;
+    if (use_device(c)) return -1;
+    if (!c->dDenoised && (dalloc(&c->dDnA, (size_t)c->N) || dalloc(&c->dDnB, (size_t)c->N) || dalloc(&c->dDenoised, (size_t)c->N))) return -1;
+    if (join_splats(c)) return -1;   /* the light splats / K5 of the last iteration add to the framebuffer on a stream of their own */
+    HIPCHK(dn_launch_denoise(c->resX, c->resY, NULL, c->dFb, scale, c->dAlbedo, c->dGuide, c->dDenoised, c->dDnA, c->dDnB, *p, c->stream));
+    c->denoisedValid = true;
+    return 0;
+}
+
+static int need_denoised(vcm_ctx *c, const char *who)
+{
+    if (refuse_sharded(c, who)) return -1;
+    if (!c->denoisedValid) return fail(who, "vcm_denoise has not run");
+    return use_device(c);
+}
+
+int vcm_read_denoised(vcm_ctx *c, float *rgbHost)
+{
+    if (!c || !rgbHost) return fail("vcm_read_denoised", "NULL argument");
+    g_hipFailed = false;
+    if (need_denoised(c, "vcm_read_denoised")) return -1;
+    return read_f4_components(c, "vcm_read_denoised", c->dDenoised, 0, 3, rgbHost);
+}
+
+int vcm_denoised_device(vcm_ctx *c, void **devPtr)
+{
+    if (!c || !devPtr) return fail("vcm_denoised_device", "NULL argument");
+    if (need_denoised(c, "vcm_denoised_device")) return -1;
+    *devPtr = c->dDenoised;
+    return 0;
+}
+
+int vcm_read_denoised_image(vcm_ctx *c, int format, float gamma, unsigned char *outHost)
+{
+    if (!c || !outHost) return fail("vcm_read_denoised_image", "NULL argument");
+    if (format != VCM_IMAGE_BGR8 && format != VCM_IMAGE_RGBE) return fail("vcm_read_denoised_image", "unknown format");
+    if (!(gamma > 0.f)) return fail("vcm_read_denoised_image", "gamma must be positive");
+    g_hipFailed = false;
+    if (need_denoised(c, "vcm_read_denoised_image")) return -1;
+    const size_t bytes = (size_t)c->N * (format == VCM_IMAGE_BGR8 ? 3 : 4);
+    float *rgb = NULL; unsigned char *d = NULL;
+    if (dalloc(&rgb, (size_t)c->N * 3)) return -1;
+    if (dalloc(&d, bytes)) { (void)hipFree(rgb); return -1; }
+    hipError_t e = dn_launch_unpack(c->N, c->dDenoised, 0, 3, rgb, c->stream);
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(k_encode_image, dim3(1024), dim3(256), 0, c->stream, (const float *)rgb, c->resX, c->resY, format, 1.f, 1.f / gamma, d);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(outHost, d, bytes, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    (void)hipFree(d); (void)hipFree(rgb);
+    if (e != hipSuccess) { g_hipFailed = true; return fail("vcm_read_denoised_image", hipGetErrorString(e)); }
+    return 0;
+}
+
+int vcm_denoise_buffers(int device, int width, int height, const void *colorDev, const void *albedoDev, const void *guideDev,
+                        void *outDev, const vcm_denoise_params *p, void *hipStream)
+{
+    if (!colorDev || !albedoDev || !guideDev || !outDev) return fail("vcm_denoise_buffers", "NULL image");
+    if (width <= 0 || height <= 0 || (long long)width * height > 0x7fffffffll) return fail("vcm_denoise_buffers", "bad size");
+    if (outDev == colorDev || outDev == albedoDev || outDev == guideDev) return fail("vcm_denoise_buffers", "outDev is one of the inputs");
+    if (const char *why = dn_check_params(p)) return fail("vcm_denoise_buffers", why);
+    const int ndev = vcm_device_count();
+    if (ndev <= 0) return fail("vcm_denoise_buffers", "no HIP device available (this library has no CPU path)");
+    if (device < 0 || device >= ndev) return fail("vcm_denoise_buffers", "device index out of range");
+    g_hipFailed = false;
+    HIPCHK(hipSetDevice(device));
+    hipStream_t s = (hipStream_t)hipStream;
+    const size_t bytes = (size_t)width * height * sizeof(F4);
+    void *a = NULL, *b = NULL;
+    if (p->passes > 0) {   /* stream-ordered scratch: it is given back behind the last pass, the host does not wait */
+        HIPCHK(hipMallocAsync(&a, bytes, s));
+        hipError_t e = hipMallocAsync(&b, bytes, s);
+        if (e != hipSuccess) { (void)hipFreeAsync(a, s); g_hipFailed = true; return fail("vcm_denoise_buffers", hipGetErrorString(e)); }
+    }
+    hipError_t e = dn_launch_denoise(width, height, (const F4 *)colorDev, NULL, 1.f, (const F4 *)albedoDev, (const F4 *)guideDev, (F4 *)outDev,
+                                     (F4 *)a, (F4 *)b, *p, s);
+    if (a) (void)hipFreeAsync(a, s);
+    if (b) (void)hipFreeAsync(b, s);
+    if (e != hipSuccess) { g_hipFailed = true; return fail("vcm_denoise_buffers", hipGetErrorString(e)); }
     return 0;
 }
 

@@ -1,0 +1,175 @@
+// vcm_denoise.h -- first-hit feature buffers and the edge-avoiding a-trous filter (Dammertz et al. 2010), host+device:
+// the kernels of vcm_denoise.hip and the host emulation of the tests (tests/host_emul_denoise) run THESE functions, so
+// that a host build and a device build give the same bits.  Arithmetic: + - * /, comparisons and detmath.h's dm_powf,
+// compiled with -ffp-contract=off like the rest of vcm_core.h.
+//
+//   guide   float4 { isect.normal.xyz, distance along the ray }   (0, 0, 0, 0) on a miss: no hit has distance 0
+//   albedo  float4 { clamp(diffuse + phong + mirror, 0, 1), 1 }   (1, 1, 1) for glass, emitters and misses; a 0 becomes 1
+#ifndef SMALLVCM_AMD_VCM_DENOISE_H
+#define SMALLVCM_AMD_VCM_DENOISE_H
+
+#include "vcm_core.h"
+
+namespace vcm {
+
+#define VCM_DN_MAX_PASSES 12
+/* vcm_denoise_defaults: the set with the lowest mean relative MSE of the sweep in DESIGN.md "Denoising" */
+#define VCM_DN_DEFAULT_SIGMA_COLOR 16.0f
+#define VCM_DN_DEFAULT_SIGMA_NORMAL 32.0f
+#define VCM_DN_DEFAULT_SIGMA_DEPTH 0.05f
+
+/* ---------------- features ---------------- */
+VCM_HD float dn_albedo_component(float a)
+{
+    a = smin(smax(a, 0.f), 1.f);
+    return (a == 0.f) ? 1.f : a;   /* demodulation never divides by 0 */
+}
+
+/* One ray through the CENTRE of pixel `pixel` from the pinhole (a thin lens is ignored: guides stay sharp), the scene
+ * kind's own closest-hit routine. */
+template <class SC>
+VCM_HD void feature_pixel(const SC &sc, int resX, int pixel, F4 &guide, F4 &albedo)
+{
+    const vcm_camera &cam = sc.camera;
+    const float sx = float(pixel % resX) + 0.5f, sy = float(pixel / resX) + 0.5f;
+    Ray ray;
+    const V3 worldRaster = transform_point(cam.rasterToWorld, mk3(sx, sy, 0.f));   /* camera.hxx:108-117 */
+    ray.org = ld3(cam.position);
+    ray.dir = normalize(worldRaster - ray.org);
+    ray.tmin = 0;
+    Isect isect; isect.dist = 1e36f; isect.matID = 0; isect.lightID = -1; isect.normal = sp3(0.f); isect.prim = -1;
+    guide = mk4(0.f, 0.f, 0.f, 0.f);
+    albedo = mk4(1.f, 1.f, 1.f, 1.f);
+    if (!scene_intersect(sc, ray, isect)) return;
+    guide = mk4(isect.normal.x, isect.normal.y, isect.normal.z, isect.dist);
+    if (isect.lightID >= 0) return;   /* an emitter */
+    const vcm_material m = scene_material(sc, isect.matID);
+    if (m.ior > 0.f) return;          /* refracts: what is seen lies behind it */
+    const V3 a = ld3(m.diffuse) + ld3(m.phong) + ld3(m.mirror);
+    albedo = mk4(dn_albedo_component(a.x), dn_albedo_component(a.y), dn_albedo_component(a.z), 1.f);
+}
+
+/* ---------------- the filter ---------------- */
+VCM_HD bool dn_finite(float x) { return (f2u(x) & 0x7f800000u) != 0x7f800000u; }
+VCM_HD bool dn_finite3(F4 c) { return dn_finite(c.x) && dn_finite(c.y) && dn_finite(c.z); }
+
+/* what one pass needs; dn_pass() derives it from the caller's parameters on the host (the same code in the library
+   and in the emulation) */
+struct DnPass {
+    int resX, resY, step;
+    float invSigmaColorSqr;   /* 1 / (sigmaColor 2^-pass)^2: sigmaColor halves after every pass */
+    float sigmaNormal, sigmaDepth;
+    int remodulate;           /* the last pass of a demodulated run multiplies the albedo back */
+};
+
+/* NULL, or why the parameters are refused */
+inline const char *dn_check_params(const vcm_denoise_params *p)
+{
+    if (!p) return "params is NULL";
+    if (p->passes < 0 || p->passes > VCM_DN_MAX_PASSES) return "passes must be in [0, 12]";
+    const float s[3] = { p->sigmaColor, p->sigmaNormal, p->sigmaDepth };
+    for (int k = 0; k < 3; k++)
+        if (!dn_finite(s[k]) || !(s[k] > 0.f)) return "sigmaColor, sigmaNormal and sigmaDepth must be finite and positive";
+    return NULL;
+}
+inline DnPass dn_pass(const vcm_denoise_params &p, int resX, int resY, int pass)
+{
+    DnPass P;
+    P.resX = resX; P.resY = resY; P.step = 1 << pass;
+    float sc = p.sigmaColor;
+    for (int i = 0; i < pass; i++) sc = sc * 0.5f;
+    P.invSigmaColorSqr = 1.f / (sc * sc);
+    P.sigmaNormal = p.sigmaNormal; P.sigmaDepth = p.sigmaDepth;
+    P.remodulate = (p.demodulate && pass == p.passes - 1) ? 1 : 0;
+    return P;
+}
+
+/* the B3-spline weights 1/16, 1/4, 3/8, 1/4, 1/16 */
+VCM_HD float dn_b3(int i) { return (i == 2) ? 0.375f : ((i == 1 || i == 3) ? 0.25f : 0.0625f); }
+
+/* colour * scale, divided by the albedo where the run demodulates: what the first pass reads */
+VCM_HD F4 dn_prepare(float r, float g, float b, float scale, F4 albedo, int demodulate)
+{
+    r = r * scale; g = g * scale; b = b * scale;
+    if (demodulate) { r = r / albedo.x; g = g / albedo.y; b = b / albedo.z; }
+    return mk4(r, g, b, 1.f);
+}
+
+struct DnAcc { float r, g, b, w; };
+
+/* One tap q seen from the centre p.  weight = h w_n w_z w_c with
+ *   w_n = max(0, n_p . n_q)^sigmaNormal                       (dm_powf: the binary exponentiation for an integer sigma)
+ *   w_z = f((|z_p - z_q| / (sigmaDepth max(z_p, z_q)))^2)
+ *   w_c = f(|c_p - c_q|^2 / sigmaColor_pass^2)                f(x) = 1 / (1 + x / 4)^4, the rational stand-in of exp(-x)
+ * A miss matches only misses (and then on colour alone), a non-finite tap or weight counts 0.  The sum runs over the
+ * DIFFERENCES c_q - c_p: a tap of the centre's colour adds an exact 0, so a constant region stays what it is, bit for
+ * bit, and an edge whose weights are 0 stays two constants. */
+VCM_HD void dn_tap(DnAcc &a, const DnPass &P, F4 cp, F4 gp, F4 cq, F4 gq, float h)
+{
+    if (!dn_finite3(cq)) return;
+    const bool missP = gp.w == 0.f, missQ = gq.w == 0.f;
+    if (missP != missQ) return;
+    float w = h, az = 1.f;
+    if (!missP) {
+        const float d = dot(mk3(gp.x, gp.y, gp.z), mk3(gq.x, gq.y, gq.z));
+        if (!(d > 0.f)) return;
+        w = w * dm_powf(d, P.sigmaNormal);
+        const float t = fabsf(gp.w - gq.w) / (P.sigmaDepth * smax(gp.w, gq.w));
+        az = 1.f + 0.25f * (t * t);
+    }
+    const float dr = cq.x - cp.x, dg = cq.y - cp.y, db = cq.z - cp.z;
+    const float dist2 = (dr * dr + dg * dg) + db * db;
+    const float ac = 1.f + 0.25f * (dist2 * P.invSigmaColorSqr);
+    const float t1 = ac * az, t2 = t1 * t1, t4 = t2 * t2;
+    w = w / t4;
+    if (!(w > 0.f) || !dn_finite(w)) return;
+    a.r = a.r + w * dr; a.g = a.g + w * dg; a.b = a.b + w * db; a.w = a.w + w;
+}
+
+/* the filtered pixel (x, y): load(xq, yq, cq, gq) fetches a tap's colour and guide, rows first, columns inside */
+template <class Load>
+VCM_HD F4 dn_filter_pixel(const DnPass &P, int x, int y, F4 albedoP, Load &&load)
+{
+    F4 cp, gp;
+    load(x, y, cp, gp);
+    if (!dn_finite3(cp)) return mk4(cp.x, cp.y, cp.z, 1.f);   /* a non-finite centre passes through */
+    DnAcc a; a.r = a.g = a.b = a.w = 0.f;
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+#endif
+    for (int j = 0; j < 5; j++) {
+        const int yq = y + (j - 2) * P.step;
+        if (yq < 0 || yq >= P.resY) continue;
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+#endif
+        for (int i = 0; i < 5; i++) {
+            const int xq = x + (i - 2) * P.step;
+            if (xq < 0 || xq >= P.resX) continue;
+            F4 cq, gq;
+            load(xq, yq, cq, gq);
+            dn_tap(a, P, cp, gp, cq, gq, dn_b3(j) * dn_b3(i));
+        }
+    }
+    F4 o = mk4(cp.x, cp.y, cp.z, 1.f);
+    if (a.w > 0.f) { o.x = cp.x + a.r / a.w; o.y = cp.y + a.g / a.w; o.z = cp.z + a.b / a.w; }
+    if (P.remodulate) { o.x = o.x * albedoP.x; o.y = o.y * albedoP.y; o.z = o.z * albedoP.z; }
+    return o;
+}
+
+/* ---------------- launches (vcm_denoise.hip; the C-ABI of vcm_api.hip calls them) ---------------- */
+#if defined(__HIPCC__)
+struct DnSceneKind { bool envMap, bvh, intPhong, rects, quads; };
+/* guide / albedo of the pixels [p0, p0 + nLocal) */
+hipError_t dn_launch_features(const DScene *dScene, DnSceneKind kind, int resX, int p0, int nLocal, F4 *guide, F4 *albedo,
+                              hipStream_t stream);
+/* out = the filtered colour.  fb3 != NULL: the colour is a W*H*3 float image times `scale`, else the float4 image
+   `color`.  tmpA, tmpB: two W*H float4 images of scratch (unused when passes == 0).  Parameters already checked. */
+/* dst[p * nComp + k] = component comp0 + k of src[p] */
+hipError_t dn_launch_unpack(int n, const F4 *src, int comp0, int nComp, float *dst, hipStream_t stream);
+hipError_t dn_launch_denoise(int resX, int resY, const F4 *color, const float *fb3, float scale, const F4 *albedo,
+                             const F4 *guide, F4 *out, F4 *tmpA, F4 *tmpB, const vcm_denoise_params &p, hipStream_t stream);
+#endif
+
+} // namespace vcm
+#endif

@@ -12,6 +12,7 @@
 //              [--device D] [--strict] [--warmup W] [-o out.pfm] [--json] [--scene-file f.vcmscene|f.obj]
 //              [--envmap f.hdr|f.pfm [--envmap-scale S]] [--aperture R --focus D]
 //              [--light-pick uniform|power [--light-pick-mix A] [--light-pick-report]]
+//              [--denoise [passes]] [--denoise-sigma c,n,z] [--no-demodulate] [--features-out prefix]
 //              [--gpus N [--shards S] [--inflight K] [--devices 0,1,..] [--collectives rccl|threads] [--same-window]]
 //
 // --gpus N: the multi-GPU host (vcm_farm.hpp): N ranks = N host threads, one per GPU, cut into N / S groups; a
@@ -30,6 +31,11 @@
 // equal probability (the default) or by emitted power, --light-pick-mix A in [0, 1] of the uniform choice mixed in; they
 // override a scene file's `lightpick` directive.  The mode in effect is printed when it is not the default, and with
 // --light-pick-report the five most probable lights and their probabilities.
+//
+// --denoise [passes]: the image goes through the edge-avoiding a-trous filter (vcm_denoise: vcm_denoise_defaults with
+// `passes`, --denoise-sigma's sigmaColor,sigmaNormal,sigmaDepth and --no-demodulate applied) before it is written to
+// -o; the unfiltered image is written beside it as <name>.noisy.<ext>.  --features-out P writes the first-hit guide
+// images P.albedo.pfm, P.normal.pfm ("PF") and P.depth.pfm ("Pf", one channel).  Both want one renderer on one GPU.
 //
 // -s / -a / -i keep the meaning they have in the reference's CLI
 // (src/config.hxx:246-395; scenes = g_SceneConfigs[0..3], :146-151).
@@ -90,6 +96,10 @@ int main(int argc, char **argv)
     std::string pickName;
     float pickMix = 0.f;
     bool havePickMix = false, pickReport = false;
+    bool denoise = false;
+    vcm_denoise_params dn;
+    vcm_denoise_defaults(&dn);
+    std::string featuresOut;
     for (int i = 1; i < argc; i++) {
         const std::string a(argv[i]);
         auto need = [&](int n) { if (i + n >= argc) { fprintf(stderr, "vcm_render: %s needs %d argument(s)\n", a.c_str(), n); exit(2); } };
@@ -131,12 +141,26 @@ int main(int argc, char **argv)
             havePickMix = true;
         }
         else if (a == "--light-pick-report") pickReport = true;
+        else if (a == "--denoise") {
+            denoise = true;
+            if (i + 1 < argc && argv[i + 1][0] >= '0' && argv[i + 1][0] <= '9') dn.passes = atoi(argv[++i]);
+        }
+        else if (a == "--denoise-sigma") {
+            need(1);
+            if (sscanf(argv[++i], "%f,%f,%f", &dn.sigmaColor, &dn.sigmaNormal, &dn.sigmaDepth) != 3) { fprintf(stderr, "vcm_render: --denoise-sigma c,n,z\n"); return 2; }
+        }
+        else if (a == "--no-demodulate") dn.demodulate = 0;
+        else if (a == "--features-out") { need(1); featuresOut = argv[++i]; }
         else if (a == "--strict") strict = 1;
         else if (a == "--json") json = 1;
         else { fprintf(stderr, "vcm_render: unknown option %s (see the header of vcm_render.cpp)\n", a.c_str()); return 2; }
     }
     if (algorithm < 0 || sceneID < 0 || sceneID > 3 || iterations < 1 || resX < 1 || resY < 1 || renderers < 1) {
         fprintf(stderr, "vcm_render: invalid argument\n");
+        return 2;
+    }
+    if ((denoise || !featuresOut.empty()) && (renderers != 1 || gpus > 0)) {
+        fprintf(stderr, "vcm_render: --denoise and --features-out want one renderer on one GPU (a farm host denoises the reduced frame with vcm_denoise_buffers)\n");
         return 2;
     }
     if (haveAperture != haveFocus) { fprintf(stderr, "vcm_render: --aperture and --focus go together\n"); return 2; }
@@ -324,26 +348,48 @@ int main(int argc, char **argv)
     vcm_get_stats(r[0], &st);
     }
 
-    if (!out.empty()) {
-        const std::string ext = out.size() >= 4 ? out.substr(out.size() - 4) : "";
+    if (!featuresOut.empty()) {   // the guide images, rows top to bottom like SavePFM
+        const int which[3] = { VCM_FEATURE_ALBEDO, VCM_FEATURE_NORMAL, VCM_FEATURE_DEPTH };
+        const char *name[3] = { ".albedo.pfm", ".normal.pfm", ".depth.pfm" };
+        for (int k = 0; k < 3; k++) {
+            const size_t nf = (size_t)resX * resY * (k == 2 ? 1 : 3);
+            if (vcm_read_feature(r[0], which[k], tmp.data())) return die("vcm_read_feature");
+            FILE *f = fopen((featuresOut + name[k]).c_str(), "wb");
+            if (!f) { fprintf(stderr, "vcm_render: cannot write %s%s\n", featuresOut.c_str(), name[k]); return 2; }
+            fprintf(f, "%s\n%d %d\n-1\n", k == 2 ? "Pf" : "PF", resX, resY);
+            fwrite(tmp.data(), sizeof(float), nf, f);
+            fclose(f);
+        }
+    }
+    std::vector<float> clean;
+    if (denoise) {
+        if (vcm_denoise(r[0], 1.f / vcm_iterations(r[0]), &dn)) return die("vcm_denoise");
+        clean.resize(n3);
+        if (vcm_read_denoised(r[0], clean.data())) return die("vcm_read_denoised");
+    }
+    // img: the fp32 image; denoised: the 8-bit encodings come from the context's denoised image, else from its framebuffer
+    auto save = [&](const std::string &path, const std::vector<float> &img, bool denoised) -> int {
+        const std::string ext = path.size() >= 4 ? path.substr(path.size() - 4) : "";
         const bool bmp = ext == ".bmp", hdr = ext == ".hdr";
         std::vector<unsigned char> px;
         if (bmp || hdr) {
             px.resize((size_t)resX * resY * (bmp ? 3 : 4));
-            if (renderers == 1 && !r.empty()) {   // encoded on the device
+            if (denoised) {
+                if (vcm_read_denoised_image(r[0], bmp ? VCM_IMAGE_BGR8 : VCM_IMAGE_RGBE, 2.2f, px.data())) return die("vcm_read_denoised_image");
+            } else if (renderers == 1 && !r.empty()) {   // encoded on the device
                 if (vcm_read_image(r[0], bmp ? VCM_IMAGE_BGR8 : VCM_IMAGE_RGBE, 1.f / vcm_iterations(r[0]), 2.2f, px.data()))
                     return die("vcm_read_image");
             } else if (bmp) {       // Framebuffer::SaveBMP, framebuffer.hxx:194-214
                 const float invGamma = 1.f / 2.2f;
                 for (int y = 0; y < resY; y++) for (int x = 0; x < resX; x++) {
-                    const float *c = &fb[((size_t)x + (size_t)(resY - y - 1) * resX) * 3];
+                    const float *c = &img[((size_t)x + (size_t)(resY - y - 1) * resX) * 3];
                     unsigned char *o = &px[((size_t)y * resX + x) * 3];
                     for (int k = 0; k < 3; k++)
                         o[k] = (unsigned char)std::min(255.f, std::max(0.f, std::pow(c[2 - k], invGamma) * 255.f));
                 }
             } else {                // Framebuffer::SaveHDR, framebuffer.hxx:229-247
                 for (size_t p = 0; p < (size_t)resX * resY; p++) {
-                    const float *c = &fb[p * 3];
+                    const float *c = &img[p * 3];
                     unsigned char *o = &px[p * 4];
                     o[0] = o[1] = o[2] = o[3] = 0;
                     float v = std::max(c[0], std::max(c[1], c[2]));
@@ -356,11 +402,11 @@ int main(int argc, char **argv)
                 }
             }
         }
-        FILE *f = fopen(out.c_str(), "wb");
-        if (!f) { fprintf(stderr, "vcm_render: cannot write %s\n", out.c_str()); return 2; }
+        FILE *f = fopen(path.c_str(), "wb");
+        if (!f) { fprintf(stderr, "vcm_render: cannot write %s\n", path.c_str()); return 2; }
         if (bmp) {   // BmpHeader, framebuffer.hxx:150-168, :175-191
-            const uint32_t img = (uint32_t)resX * resY * 3;
-            uint32_t h[13] = { 54u + img, 0u, 54u, 40u, (uint32_t)resX, (uint32_t)resY, 1u | (24u << 16), 0u, img, 2953u, 2953u, 0u, 0u };
+            const uint32_t bytes = (uint32_t)resX * resY * 3;
+            uint32_t h[13] = { 54u + bytes, 0u, 54u, 40u, (uint32_t)resX, (uint32_t)resY, 1u | (24u << 16), 0u, bytes, 2953u, 2953u, 0u, 0u };
             fwrite("BM", 1, 2, f);
             fwrite(h, 4, 13, f);
             fwrite(px.data(), 1, px.size(), f);
@@ -369,9 +415,20 @@ int main(int argc, char **argv)
             fwrite(px.data(), 1, px.size(), f);
         } else {     // Framebuffer::SavePFM, framebuffer.hxx:137-146
             fprintf(f, "PF\n%d %d\n-1\n", resX, resY);
-            fwrite(fb.data(), sizeof(float), n3, f);
+            fwrite(img.data(), sizeof(float), n3, f);
         }
         fclose(f);
+        return 0;
+    };
+    if (!out.empty()) {
+        if (!denoise) { if (int rc = save(out, fb, false)) return rc; }
+        else {   // the denoised image under the name asked for, the noisy one beside it
+            const size_t dot = out.rfind('.');
+            const bool hasExt = dot != std::string::npos && out.find('/', dot) == std::string::npos;
+            const std::string noisy = hasExt ? out.substr(0, dot) + ".noisy" + out.substr(dot) : out + ".noisy";
+            if (int rc = save(noisy, fb, false)) return rc;
+            if (int rc = save(out, clean, true)) return rc;
+        }
     }
     for (size_t g = 0; g < r.size(); g++) vcm_destroy(r[g]);
     vcm_scene_file_free(loaded);

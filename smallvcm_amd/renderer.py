@@ -21,7 +21,7 @@ import os
 
 import numpy as np
 
-from ._abi import (SceneDesc, SceneDesc2, SceneDesc3, SceneDesc4, SceneDesc5, Stats, SCENE_CONFIGS, VCM_MERGE_RECORD_FLOATS, ALGO_LIGHT_TRACE, ALGO_PPM, ALGO_BPM,
+from ._abi import (DenoiseParams, FEATURES, SceneDesc, SceneDesc2, SceneDesc3, SceneDesc4, SceneDesc5, Stats, SCENE_CONFIGS, VCM_MERGE_RECORD_FLOATS, ALGO_LIGHT_TRACE, ALGO_PPM, ALGO_BPM,
                    ALGO_BPT, ALGO_VCM)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -112,6 +112,16 @@ def load_library(require_gpu=True):
         L.vcm_host_powf.restype = C.c_float
         L.vcm_host_path_float.argtypes = [C.c_uint] * 5
         L.vcm_host_path_float.restype = C.c_float
+        L.vcm_denoise_defaults.argtypes = [C.POINTER(DenoiseParams)]
+        L.vcm_denoise_defaults.restype = None
+        L.vcm_render_features.argtypes = [vp]
+        L.vcm_read_feature.argtypes = [vp, C.c_int, fp]
+        L.vcm_features_device.argtypes = [vp, C.POINTER(vp), C.POINTER(vp)]
+        L.vcm_denoise.argtypes = [vp, C.c_float, C.POINTER(DenoiseParams)]
+        L.vcm_read_denoised.argtypes = [vp, fp]
+        L.vcm_denoised_device.argtypes = [vp, C.POINTER(vp)]
+        L.vcm_read_denoised_image.argtypes = [vp, C.c_int, C.c_float, C.POINTER(C.c_ubyte)]
+        L.vcm_denoise_buffers.argtypes = [C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, C.POINTER(DenoiseParams), vp]
         L.vcm_sizeof_scene_desc.restype = C.c_uint
         L.vcm_sizeof_stats.restype = C.c_uint
         _lib = L
@@ -133,6 +143,36 @@ def cornell_scene(scene_id_or_mask, resx=512, resy=512, is_mask=False):
     d = SceneDesc()
     _check(L, L.vcm_scene_cornell(resx, resy, mask, C.byref(d)), "vcm_scene_cornell")
     return d
+
+
+def denoise_params(**kw):
+    """vcm_denoise_defaults with some members replaced: passes, sigmaColor, sigmaNormal, sigmaDepth, demodulate"""
+    L = load_library(require_gpu=False)
+    p = DenoiseParams()
+    L.vcm_denoise_defaults(C.byref(p))
+    for k, v in kw.items():
+        if k not in ("passes", "sigmaColor", "sigmaNormal", "sigmaDepth", "demodulate"):
+            raise TypeError("unknown denoise parameter %r" % k)
+        setattr(p, k, v)
+    return p
+
+
+def denoise_tensors(color, albedo, guide, out=None, **params):
+    """vcm_denoise_buffers over torch tensors: [H, W, 4] float32, contiguous, on one GPU (colour rgb?, albedo rgb1,
+    guide normal.xyz | depth); asynchronous on torch's current stream of that device.  Returns `out` (a new tensor when
+    None)."""
+    import torch
+    L = load_library()
+    for t in (color, albedo, guide):
+        if t.dtype != torch.float32 or not t.is_cuda or not t.is_contiguous() or t.dim() != 3 or t.shape != color.shape or t.shape[2] != 4:
+            raise ValueError("denoise_tensors wants contiguous float32 GPU tensors of one shape [H, W, 4]")
+    if out is None:
+        out = torch.empty_like(color)
+    dev = color.device.index if color.device.index is not None else torch.cuda.current_device()
+    p = denoise_params(**params)
+    _check(L, L.vcm_denoise_buffers(dev, int(color.shape[1]), int(color.shape[0]), color.data_ptr(), albedo.data_ptr(), guide.data_ptr(),
+                                    out.data_ptr(), C.byref(p), torch.cuda.current_stream(dev).cuda_stream), "vcm_denoise_buffers")
+    return out
 
 
 class HipBackend:
@@ -302,6 +342,39 @@ class HipBackend:
                "vcm_read_image")
         return out
 
+    # ---- feature buffers and denoiser --------------------------------------
+    def render_features(self):
+        """first-hit albedo / normal / depth of this context's pixels (asynchronous; needs no iteration)"""
+        _check(self.L, self.L.vcm_render_features(self.ctx), "vcm_render_features")
+
+    def feature(self, which):
+        """'albedo' / 'normal' -> [H, W, 3], 'depth' -> [H, W] (rendered first if they are not there)"""
+        w = FEATURES[which] if isinstance(which, str) else int(which)
+        out = np.zeros((self.resy, self.resx) if w == FEATURES["depth"] else (self.resy, self.resx, 3), np.float32)
+        _check(self.L, self.L.vcm_read_feature(self.ctx, w, out.ctypes.data_as(C.POINTER(C.c_float))), "vcm_read_feature")
+        return out
+
+    def features_device(self):
+        """device pointers of the (albedo, guide) float4 images"""
+        a, g = C.c_void_p(), C.c_void_p()
+        _check(self.L, self.L.vcm_features_device(self.ctx, C.byref(a), C.byref(g)), "vcm_features_device")
+        return a.value, g.value
+
+    def denoise(self, scale, **params):
+        """framebuffer * scale through the edge-avoiding filter -> [H, W, 3]; params: see denoise_params()"""
+        p = denoise_params(**params)
+        _check(self.L, self.L.vcm_denoise(self.ctx, scale, C.byref(p)), "vcm_denoise")
+        out = np.zeros((self.resy, self.resx, 3), np.float32)
+        _check(self.L, self.L.vcm_read_denoised(self.ctx, out.ctypes.data_as(C.POINTER(C.c_float))), "vcm_read_denoised")
+        return out
+
+    def read_denoised_image(self, fmt, gamma=2.2):
+        """the last denoised image in the encodings of read_image"""
+        out = np.zeros((self.resy, self.resx, 3 if fmt == 0 else 4), np.uint8)
+        _check(self.L, self.L.vcm_read_denoised_image(self.ctx, fmt, gamma, out.ctypes.data_as(C.POINTER(C.c_ubyte))),
+               "vcm_read_denoised_image")
+        return out
+
     def stats_at(self, ago):
         """counters and phase times of the iteration `ago` iterations before the last completed one (<= 63)"""
         st = Stats()
@@ -364,6 +437,11 @@ class VertexCM:
         if self.mIterations > 0:
             fb = fb * np.float32(1.0 / self.mIterations)
         return fb
+
+    def GetDenoised(self, **params):
+        """GetFramebuffer() through the edge-avoiding denoiser (the reference has no such call); params: see
+        denoise_params()"""
+        return self.backend.denoise(1.0 / self.mIterations if self.mIterations > 0 else 1.0, **params)
 
     def framebuffer_sum(self):
         return self.backend.framebuffer_sum()
