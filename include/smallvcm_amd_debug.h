@@ -67,6 +67,19 @@ enum {
 };
 int vcm_debug_kat(vcm_ctx *ctx, int op, int n, const float *in, float *out);
 
+/* Which code path a context takes, for tests that must assert it rather than infer it: out = VCM_INFO_COUNT ints.
+ * The kind flags are the ones the launches read -- rects / quads: the SceneRects(E) / SceneQuads kernels (both 0 on a
+ * list: SceneList(E)); nodes: a BVH (SceneBvh / SceneBvhG / SceneBvhE); intPhong 0: the general-pow kinds; envMap, lens,
+ * pick: the E kinds, WithLens, WithPick -- then the table sizes the LDS-or-global branches compare, and the merge kernel
+ * the LAST iteration launched (VCM_MERGE_WALK or VCM_MERGE_PAIRS after the fall-back above VCM_PAIR_MATERIALS; 0: it
+ * launched neither -- an algorithm without merging, or strict order, whose camera kernel merges in place). */
+enum {
+    VCM_INFO_RECTS = 0, VCM_INFO_QUADS = 1, VCM_INFO_NODES = 2, VCM_INFO_INT_PHONG = 3, VCM_INFO_ENVMAP = 4, VCM_INFO_LENS = 5,
+    VCM_INFO_PICK = 6, VCM_INFO_MATERIALS = 7, VCM_INFO_PRIMS = 8, VCM_INFO_LIGHTS = 9, VCM_INFO_MERGE_KERNEL = 10,
+    VCM_INFO_COUNT = 11
+};
+int vcm_debug_context_info(vcm_ctx *ctx, int *out);
+
 /* sizeof the PODs of smallvcm_amd.h as the library was compiled */
 unsigned vcm_sizeof_scene_desc(void);
 unsigned vcm_sizeof_stats(void);

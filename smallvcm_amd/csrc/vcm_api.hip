@@ -216,6 +216,7 @@ struct vcm_ctx : Scratch {
     bool bboxFinal;                   /* ... and k_compact_records has turned it into floats already */
     bool strictOrder;
     int mergeKind;                    /* VCM_MERGE_* */
+    int lastMergeKernel;              /* the VCM_MERGE_* kernel the last iteration launched, 0 if it merged nothing (vcm_debug_context_info) */
     bool sceneQuads;                  /* every triangle pair of the list shares its plane part: the SceneQuads kernels */
     bool sceneRects;                  /* ... and is an axis-aligned rectangle: the SceneRects kernels */
     bool envMap;                      /* the scene's background is an environment map: the SceneRectsE / SceneListE / SceneBvhE kernels */
@@ -832,6 +833,7 @@ static vcm_ctx *create_from_host(SceneHost *h, int algorithm, float radiusFactor
       c->sortedExchange = worldSize > 1 && worldSize <= VCM_SORTED_MAX_SHARDS && c->useVM && !(e && e[0] == '0'); }
     { const char *e = getenv("SMALLVCM_AMD_MERGE");
       c->mergeKind = (e && !strcmp(e, "walk")) ? VCM_MERGE_WALK : (e && !strcmp(e, "pairs")) ? VCM_MERGE_PAIRS : VCM_MERGE_DEFAULT; }
+    c->lastMergeKernel = 0;
     return c;
 }
 
@@ -1124,6 +1126,7 @@ static int vcm_begin_iteration_impl(vcm_ctx *c, int iteration, unsigned minLen, 
     c->gridBuilt = c->cameraTraced = c->merged = c->splatsPending = c->recordsValid = c->countedInCamera = c->scatteredInDI = c->gridInFlight = c->splatInFlight = c->bboxPreset = c->bboxFromLight = c->bboxFinal = c->prezeroed = c->sortInFlight = c->spaceSet = c->mergeImported = false;
     c->splatInFlight = c->resolveInFlight;   /* whoever reads the framebuffer still has the last iteration's K5 to wait for */
     c->inIteration = true;
+    c->lastMergeKernel = 0;
     c->evValid = false;
     return 0;
 }
@@ -1914,6 +1917,7 @@ static int vcm_space_merge_impl(vcm_ctx *c, const void *queriesDev, const long l
         const int blocks = merge_blocks(nLoc, c->N);
         int kind = c->mergeKind;
         if (kind == VCM_MERGE_PAIRS && (int)c->scene->materials.size() > VCM_PAIR_MATERIALS) kind = VCM_MERGE_WALK;
+        c->lastMergeKernel = kind;
         const int chunk = shape_knob("merge_chunk") ? shape_knob("merge_chunk") : 16;
         if (kind == VCM_MERGE_PAIRS) {
             if (c->intPhong) hipLaunchKernelGGL(k_merge_pairs<true>, dim3(blocks), dim3(VCM_MERGE_BLOCK), 0, c->stream, c->dScene, P2, grid_of(c), fvs, (const int *)c->fSorted, (const int *)(c->dQueryStart + nb), c->dStats, chunk, none);
@@ -2013,6 +2017,7 @@ static int vcm_merge_impl(vcm_ctx *c)
             int mergeStaged = c->mergeKind;
             /* k_merge_pairs keeps a material table of VCM_PAIR_MATERIALS rows in LDS */
             if (mergeStaged == VCM_MERGE_PAIRS && (int)c->scene->materials.size() > VCM_PAIR_MATERIALS) mergeStaged = VCM_MERGE_WALK;
+            c->lastMergeKernel = mergeStaged;
             if (mergeStaged == VCM_MERGE_PAIRS) {
                 if (c->intPhong)
                     hipLaunchKernelGGL(k_merge_pairs<true>, dim3(merge_blocks(c->nLocal, c->N)), dim3(VCM_MERGE_BLOCK), 0, ks, c->dScene, c->P, grid_of(c),
@@ -2586,6 +2591,26 @@ int vcm_debug_kat(vcm_ctx *c, int op, int n, const float *in, float *out)
     if (e == hipSuccess) e = hipMemcpy(out, dout, bytes, hipMemcpyDeviceToHost);
     (void)hipFree(din); (void)hipFree(dout);
     if (e != hipSuccess) return fail("vcm_debug_kat", hipGetErrorString(e));
+    return 0;
+}
+
+int vcm_debug_context_info(vcm_ctx *c, int *out)
+{
+    if (!c || !out) return fail("vcm_debug_context_info", "bad argument");
+    if (ensure_device(c)) return -1;   /* the kind flags are decided when the scene is uploaded */
+    const bool nodes = !c->scene->nodes.empty();
+    /* the flags as LAUNCH_SC_W reads them: a BVH comes before the list kinds, the general pow before rects / quads */
+    out[VCM_INFO_RECTS] = !nodes && c->intPhong && c->sceneRects;
+    out[VCM_INFO_QUADS] = !nodes && !c->envMap && c->intPhong && !c->sceneRects && c->sceneQuads;
+    out[VCM_INFO_NODES] = nodes;
+    out[VCM_INFO_INT_PHONG] = c->intPhong;
+    out[VCM_INFO_ENVMAP] = c->envMap;
+    out[VCM_INFO_LENS] = c->lens;
+    out[VCM_INFO_PICK] = c->pick;
+    out[VCM_INFO_MATERIALS] = (int)c->scene->materials.size();
+    out[VCM_INFO_PRIMS] = (int)c->scene->prims.size();
+    out[VCM_INFO_LIGHTS] = (int)c->scene->lights.size();
+    out[VCM_INFO_MERGE_KERNEL] = c->lastMergeKernel;
     return 0;
 }
 

@@ -6,8 +6,9 @@ import numpy as np
 from smallvcm_amd.scene2 import SceneBuilder
 
 
-def bumpy_room(grid=24, resx=64, resy=64, spheres=True, sun=False, background=False, seed=5, exponent=90.0):
-    """2 * grid^2 floor triangles + 8 wall / ceiling triangles + 2 emissive triangles (+ 2 spheres)"""
+def bumpy_room(grid=24, resx=64, resy=64, spheres=True, sun=False, background=False, seed=5, exponent=90.0, envmap=None):
+    """2 * grid^2 floor triangles + 8 wall / ceiling triangles + 2 emissive triangles (+ 2 spheres); envmap = (image,
+    scale): no ceiling and no lamp, the sky is that environment map (the description is then a SceneDesc3)"""
     rng = np.random.default_rng(seed)
     b = SceneBuilder()
     white = b.material(diffuse=(0.803922, 0.803922, 0.803922))
@@ -32,12 +33,14 @@ def bumpy_room(grid=24, resx=64, resy=64, spheres=True, sun=False, background=Fa
     b.triangle(c[0], c[1], c[2], white); b.triangle(c[2], c[3], c[0], white)       # back wall
     b.triangle(c[3], c[7], c[4], green); b.triangle(c[4], c[0], c[3], green)       # left
     b.triangle(c[1], c[5], c[6], red); b.triangle(c[6], c[2], c[1], red)           # right
-    if not background:
+    if not background and envmap is None:
         b.triangle(c[2], c[6], c[7], white); b.triangle(c[7], c[3], c[2], white)   # ceiling
     if spheres:
         b.sphere((-0.5, 0.3, -0.75), 0.4, mirror)
         b.sphere((0.55, -0.2, -0.8), 0.35, glass)
-    if sun:
+    if envmap is not None:
+        b.envmap_light(envmap[0], envmap[1])
+    elif sun:
         b.directional_light((-1.0, 1.5, -1.0), (10.0, 4.0, 0.0))
     elif background:
         b.background_light(1.0)
@@ -238,3 +241,124 @@ def random_scene(seed, resx=48, resy=48):
         b.background_light(float(u(0.5, 2.0)))
     return b.build((float(u(-0.3, 0.3)), -4.1, float(u(-0.2, 0.4))), (float(u(-0.05, 0.05)), 1.0, float(u(-0.08, 0.02))),
                    (3.7e-4, 0.054, 0.9985), float(u(35, 60)), resx, resy)
+
+
+def capacity_scene(n_materials, n_prims, n_area_lights, exponent_kind="int", resx=96, resy=96, n_point_lights=0, seed=0,
+                   only_light=None):
+    """A room whose three table sizes are chosen independently (TEST INPUT): exactly n_materials material rows,
+    n_prims primitives and n_point_lights + n_area_lights lights -- the counts the kernels compare with their LDS room
+    (vcm_core.h VCM_LDS_MATERIALS / VCM_LDS_PRIMS / VCM_LDS_LIGHTS / VCM_LDS_PICK, vcm_kernels.h VCM_PAIR_MATERIALS).
+
+    Materials may outnumber the primitives: unused rows are legal and count.  Row 0 (the walls) and the LAST row are
+    always in use.  The point lights come first in the light table and the area lights last, each area light a
+    triangle in front of the back wall facing the camera with a material row of its own, created last: the last
+    material's mat2light entry names the last light, in the top row of the grid, and camera rays hit it head-on.  The other rows mix diffuse / Phong / mirror / glass
+    as random_scene does; exponent_kind "int" keeps every exponent an integer (the binary-exponentiation kernels),
+    "frac" makes row 1 a Phong lobe of exponent 3.25 and draws from fractions as well (the general-pow kinds).
+    only_light = k: every other light emits nothing (what the frame holds then comes from light k alone)."""
+    assert exponent_kind in ("int", "frac")
+    n_plain = n_materials - n_area_lights
+    n_fill = n_prims - 10 - n_area_lights
+    assert n_plain >= 2 and n_fill >= 1 and n_area_lights + n_point_lights >= 1
+    rng = np.random.default_rng(7000 + seed)
+    b = SceneBuilder()
+
+    def u(lo, hi, n=None):
+        return (rng.random(n) * (hi - lo) + lo).astype(np.float32) if n else np.float32(rng.random() * (hi - lo) + lo)
+
+    expos = [1.0, 2.0, 7.0, 90.0, 500.0, 1024.0] if exponent_kind == "int" else [0.5, 3.25, 37.5, 90.0, 2.0, 70000.0]
+    mats = [b.material(diffuse=u(0.4, 0.8, 3))]
+    mats.append(b.material(diffuse=u(0.0, 0.3, 3), phong=u(0.2, 0.65, 3), exponent=3.25 if exponent_kind == "frac" else 90.0))
+    for k in range(2, n_plain):
+        kind = int(rng.integers(0, 6))
+        expo = float(rng.choice(expos))
+        if kind == 0:
+            mats.append(b.material(diffuse=u(0.1, 0.9, 3)))
+        elif kind == 1:
+            mats.append(b.material(diffuse=u(0.0, 0.3, 3), phong=u(0.2, 0.65, 3), exponent=expo))
+        elif kind == 2:
+            mats.append(b.material(mirror=u(0.5, 1.0, 3)))
+        elif kind == 3:
+            mats.append(b.material(mirror=(1, 1, 1), ior=float(u(1.1, 2.2))))
+        elif kind == 4:
+            mats.append(b.material(diffuse=u(0.05, 0.3, 3), phong=u(0.05, 0.3, 3), exponent=expo, mirror=u(0.05, 0.3, 3)))
+        else:
+            mats.append(b.material(phong=u(0.3, 0.9, 3), exponent=expo))
+    lo, hi = -1.25, 1.25
+    c = np.array([(lo, hi, lo), (hi, hi, lo), (hi, hi, hi), (lo, hi, hi), (lo, lo, lo), (hi, lo, lo), (hi, lo, hi), (lo, lo, hi)], np.float32)
+    c = c + u(-0.05, 0.05, c.size).reshape(c.shape)
+    for q, m in (((0, 1, 2, 3), mats[0]), ((3, 7, 4, 0), mats[0]), ((1, 5, 6, 2), mats[1]), ((0, 4, 5, 1), mats[0]), ((2, 6, 7, 3), mats[0])):
+        b.triangle(c[q[0]], c[q[1]], c[q[2]], m)           # back, left, right (glossy), floor, ceiling
+        b.triangle(c[q[2]], c[q[3]], c[q[0]], m)
+    for k in range(n_fill):   # small triangles and two spheres in the lower half; the highest plain rows are used first
+        m = mats[n_plain - 1 - k % (n_plain - 1)]
+        if k in (1, 2):
+            b.sphere((float(u(-0.8, 0.8)), float(u(-0.6, 0.8)), float(u(-0.9, -0.3))), float(u(0.15, 0.3)), m)
+            continue
+        p = np.float32([u(-1.0, 1.0), u(-0.9, 1.0), u(-1.1, 0.2)])
+        size = float(u(0.15, 0.45))
+        e1, e2 = u(-1, 1, 3) * np.float32(size), u(-1, 1, 3) * np.float32(size)
+        while np.linalg.norm(np.cross(e1, e2)) < 1e-3:
+            e2 = u(-1, 1, 3) * np.float32(size)
+        b.triangle(p, p + e1, p + e2, m)
+    n_lights = n_point_lights + n_area_lights
+
+    def power(k, v):
+        return v if only_light is None or only_light == k else np.zeros(3, np.float32)
+    for k in range(n_point_lights):
+        b.point_light(u(-0.9, 0.9, 3), power(k, u(0.05, 1.0, 3) * np.float32(10.0 ** float(u(-1.5, 0.5)))))
+    cols = max(1, int(np.ceil(np.sqrt(n_area_lights))))
+    step = 1.8 / cols
+    s = np.float32(min(0.5, 0.9 * step))
+    for k in range(n_area_lights):   # a grid in front of the back wall, rows going up, normal = e1 x e2 = -y: at the camera
+        p = np.float32([-0.9 + step * (k % cols) + 0.05 * step, 1.05 - 0.002 * k, -0.9 + step * (k // cols) + 0.05 * step])
+        col = u(0.2, 1.0, 3) * np.float32(20.0 * 10.0 ** float(u(-1.0, 0.3)))
+        b.emissive_triangle(p, p + np.float32([s, 0, s]), p + np.float32([0, 0, s]), power(n_point_lights + k, col))
+    d = b.build((0.02, -4.1, 0.1), (0.0, 1.0, 0.03), (3.7e-4, 0.054, 0.9985), 45.0, resx, resy)
+    assert (d.nMaterials, d.nPrims, d.nLights) == (n_materials, n_prims, n_lights)
+    return d
+
+
+def deep_bvh_scene(resx=96, resy=96, per_axis=16, ratio=32.0):
+    """A scene whose BVH (scene_host.h: binned SAH, 16 bins, leaves of two) is a chain deeper than the traversal stack
+    (vcm_core.h VCM_BVH_STACK = 32) -- TEST INPUT.  Three stacks of large triangles, in planes x = c_i, y = c_i, z = c_i
+    with c_i = 1.5 / ratio^i: the centroids of a stack are geometrically spaced along its axis and coincide on the other
+    two, so every split the builder finds puts the outermost plane alone in the upper bins and peels it off; one axis
+    would run out of binary32 range near 30 levels, three stacks chain.  Every triangle spans the room, so a ray that
+    crosses it meets every box, descends the near child first and leaves the far one pending at every level."""
+    b = SceneBuilder()
+    S = 1.5
+    mats = [b.material(diffuse=(0.7, 0.7, 0.7)), b.material(diffuse=(0.7, 0.25, 0.2)), b.material(diffuse=(0.2, 0.3, 0.7)),
+            b.material(diffuse=(0.1, 0.1, 0.1), phong=(0.6, 0.6, 0.6), exponent=90.0)]
+    for i in range(per_axis):
+        cpl = float(np.float32(1.5 / ratio ** i))
+        for axis in range(3):
+            v = []
+            for a, bb in ((-S, -S), (0.0, S), (S, -S)):   # spans [-S, S]^2 in the other two axes (box centre 0 there); the normal
+                                                          # points down the axis, at the camera and the lights: surfaces are one-sided
+                p = [0.0, 0.0, 0.0]
+                p[axis] = cpl
+                p[(axis + 1) % 3], p[(axis + 2) % 3] = a, bb
+                v.append(tuple(p))
+            b.triangle(v[0], v[1], v[2], mats[(i + axis) % 4])
+    b.sphere((-0.7, -0.7, -0.7), 0.3, b.material(mirror=(1, 1, 1)))
+    b.point_light((-1.0, -1.2, -0.6), (6.0, 5.0, 4.0))
+    b.emissive_triangle((-1.4, -1.4, -1.45), (-0.6, -1.4, -1.45), (-1.4, -0.6, -1.45), (20.0, 20.0, 20.0))   # normal +z
+    return b.build((-3.2, -3.4, -1.0), (0.66, 0.70, 0.25), (0.0, 0.0, 1.0), 40.0, resx, resy)
+
+
+def deep_bvh_rays(n, seed=1):
+    """rays for VCM_KAT_INTERSECT / VCM_KAT_OCCLUDED on deep_bvh_scene: origins in the octant the camera is in, aimed at
+    points near where the three stacks meet (so they cross every plane), and a share of random ones; in[6] = tmin 0
+    (intersect); for the any-hit op the caller sets tmax"""
+    rng = np.random.default_rng(seed)
+    a = np.zeros((n, 16), np.float32)
+    org = -(rng.random((n, 3)) * 1.2 + 0.2)
+    tgt = rng.random((n, 3)) * 1.2 + 0.05
+    k = n // 4
+    org[:k] = rng.random((k, 3)) * 2.8 - 1.4
+    tgt[:k] = rng.random((k, 3)) * 2.8 - 1.4
+    d = tgt - org
+    d /= np.linalg.norm(d, axis=1, keepdims=True)
+    a[:, 0:3], a[:, 3:6] = org, d
+    return np.ascontiguousarray(a)

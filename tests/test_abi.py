@@ -46,6 +46,22 @@ def test_every_exported_symbol_is_declared():
     assert not [n for n in _declared_symbols("smallvcm_amd.h") if n.startswith(("vcm_debug_", "vcm_host_", "vcm_sizeof_"))]
 
 
+def test_the_context_info_accessor_is_a_debug_entry_point():
+    """vcm_debug_context_info (which kernels a context takes, for tests) is declared in the debug header only, with as
+    many VCM_INFO_* indices as tests/capacity_lib.py names, and refuses NULL without touching a device"""
+    import capacity_lib
+    assert "vcm_debug_context_info" in _declared_symbols("smallvcm_amd_debug.h")
+    assert "vcm_debug_context_info" not in _declared_symbols("smallvcm_amd.h")
+    src = open(os.path.join(ROOT, "include", "smallvcm_amd_debug.h")).read()
+    assert int(re.search(r"VCM_INFO_COUNT\s*=\s*(\d+)", src).group(1)) == len(capacity_lib.INFO_KEYS)
+    names = re.findall(r"\b(VCM_INFO_[A-Z_]+)\s*=\s*(\d+)", src)
+    assert [int(v) for _, v in names] == list(range(len(names)))
+    L = load_library(require_gpu=False)
+    L.vcm_debug_context_info.argtypes = [C.c_void_p, C.POINTER(C.c_int)]
+    out = (C.c_int * len(capacity_lib.INFO_KEYS))()
+    assert L.vcm_debug_context_info(None, out) == -1
+
+
 def test_farm_library_exports_what_its_header_declares():
     """include/smallvcm_amd_farm.h = the multi-GPU host's boundary (smallvcm_amd/host/libsmallvcm_amd_farm.so); loads
     without a GPU, exports exactly the declared entry points, PODs as the ctypes mirror assumes"""
