@@ -570,6 +570,61 @@ int vcm_read_denoised_image(vcm_ctx *ctx, int format, float gamma, unsigned char
 int vcm_denoise_buffers(int device, int width, int height, const void *colorDev, const void *albedoDev,
                         const void *guideDev, void *outDev, const vcm_denoise_params *p, void *hipStream);
 
+/* ---- per-pixel variance of the running mean, and the noise statistic ----
+ * The framebuffer is a running sum S_k over iterations and the iterations are independent samples of the image, so the
+ * variance of the mean is accumulated BESIDE the framebuffer, without touching a rendering kernel: after iteration k's
+ * resolve one kernel recovers the iteration's own frame x = S_k - S_{k-1} and applies Welford's update
+ *   M2 += (x - S_{k-1} / (k - 1)) (x - S_k / k)      (M2 = 0 for k = 1)
+ * per pixel and channel; the variance of the mean is V = M2 / (k (k - 1)), defined for k >= 2.  A non-finite sample leaves
+ * M2 non-finite for that pixel and channel and nowhere else.
+ * vcm_track_variance(ctx, 1) switches this on for a context whose framebuffer holds no iteration: a new context, or one
+ * right after vcm_clear_framebuffer (which also resets the two images; k counts the iterations since then).  Off -- the
+ * default -- costs nothing: no launch, no allocation, no byte.  Memory when on: two float4 images, 32 bytes per pixel
+ * (134 MB at 2048^2), until vcm_destroy.  A sharded context is refused (its framebuffer is a shard of the image): such a
+ * host reduces the frames itself and calls vcm_variance_update_buffers -- the same kernel on caller-owned images, no
+ * context: sumDev3 = W*H*3 floats (the running sum after iteration k, k = 1, 2, ...), prevDev and momDev = n float4 each,
+ * zeroed before k = 1; asynchronous on `hipStream`.
+ * vcm_variance_device: the moments image { M2.rgb, 0 } (float4 per pixel); whoever reads it orders against the context's
+ * stream.  vcm_read_variance: W*H*3 floats of V; fails with k < 2.
+ * vcm_get_noise_stats reduces  noise = V / (mean^2 + 0.01),  mean = S_k / k,  over all pixels and channels: the
+ * expectation of the relative squared error (img - ref)^2 / (ref^2 + 0.01) against a converged reference, with no
+ * reference.  `above` counts the elements with noise > threshold; non-finite elements are counted in nonFinite and left
+ * out of mean, max and above.  The reduction has no floating-point atomics, a fixed grid and a fixed combination tree
+ * (binary64 sums): the same bits on every run.  It synchronises; it fails with k < 2.
+ * CAVEAT: the statistic normalises by the noisy mean where the error metric normalises by the reference.  The two agree
+ * where the mean is itself near converged (within 10 % on the sky-lit scene 3 after 16 iterations) and NOT where the
+ * error is carried by fireflies: one bright sample F in k gives its pixel V = mean^2, so its noise saturates just below 1
+ * whatever F is -- on scene 1 under path tracing the mean of the statistic is thirty times below the measured error
+ * (DESIGN.md "Variance").  A host that renders such scenes to a target should watch `max` and `above` as well.
+ *
+ * The variance-guided filter.  vcm_denoise_params2 = vcm_denoise_params + { varianceGuided, sigmaVariance };
+ * vcm_denoise2 / vcm_denoise_buffers2 with varianceGuided == 0 ARE vcm_denoise / vcm_denoise_buffers, bit for bit.  With
+ * varianceGuided == 1 the colour stop of a tap is  |c_p - c_q|^2 / (sigmaVariance^2 v~_p + 1e-10)  instead of
+ * |c_p - c_q|^2 / sigmaColor_i^2 (SVGF, Schied et al. 2017): v~_p is the 3 x 3 Gaussian of the centre's variance, which
+ * rides in the colour image's .w -- sum over channels of V (/ albedo^2 when demodulating) before the first pass,
+ * sum w_q^2 v_q / (sum w_q)^2 after every pass; sigmaColor then only serves pixels whose variance is not finite.
+ * vcm_denoise2 takes the variance from the context (vcm_track_variance on, at least two iterations, else refused);
+ * vcm_denoise_buffers2 takes a moments image { M2.rgb, 0 } and k, the colour being the mean S_k / k.
+ * vcm_denoise_defaults2: vcm_denoise_defaults, varianceGuided 1, sigmaVariance 4 -- in the sweep of DESIGN.md "Variance"
+ * the guided stop at 4 has a lower error than the fixed stop on all twelve cases, so the new call guides by default (and
+ * so wants a tracked context); vcm_denoise and vcm_denoise_defaults stay what they were. */
+typedef struct vcm_noise_stats { int iterations; long long elements, above, nonFinite; double mean, max; } vcm_noise_stats;
+int vcm_track_variance(vcm_ctx *ctx, int on);
+int vcm_variance_device(vcm_ctx *ctx, void **momDev);
+int vcm_read_variance(vcm_ctx *ctx, float *rgbHost);
+int vcm_get_noise_stats(vcm_ctx *ctx, float threshold, vcm_noise_stats *out);
+int vcm_variance_update_buffers(int device, long long n, const void *sumDev3, int k, void *prevDev, void *momDev, void *hipStream);
+int vcm_noise_stats_buffers(int device, long long n, const void *prevDev, const void *momDev, int k, float threshold,
+                            vcm_noise_stats *out, void *hipStream);
+typedef struct vcm_denoise_params2 {
+    int passes; float sigmaColor, sigmaNormal, sigmaDepth; int demodulate;   /* as vcm_denoise_params */
+    int varianceGuided; float sigmaVariance;
+} vcm_denoise_params2;
+void vcm_denoise_defaults2(vcm_denoise_params2 *out);
+int vcm_denoise2(vcm_ctx *ctx, float scale, const vcm_denoise_params2 *p);   /* the result: vcm_read_denoised and its kin */
+int vcm_denoise_buffers2(int device, int width, int height, const void *colorDev, const void *albedoDev, const void *guideDev,
+                         const void *momDev, int k, void *outDev, const vcm_denoise_params2 *p, void *hipStream);
+
 #ifdef __cplusplus
 }
 #endif

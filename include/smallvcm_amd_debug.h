@@ -80,6 +80,15 @@ enum {
 };
 int vcm_debug_context_info(vcm_ctx *ctx, int *out);
 
+/* The two images of a context with vcm_track_variance on, as they stand after the last iteration: W*H float4 each,
+ * prev = { S_{k-1}.rgb, 0 } and mom = { M2.rgb, 0 } (either may be NULL).  Synchronises. */
+int vcm_debug_read_variance_images(vcm_ctx *ctx, float *prevHost4, float *momHost4);
+
+/* The cap of the grid of k_var_update and k_var_stats (0 restores the default, 2048 workgroups of 256 lanes), so that a
+ * test reaches the grid-stride path and the second reduction level with a few hundred pixels.  Process-wide; the
+ * combination tree, and so the last bits of vcm_noise_stats.mean, depend on it: not for production hosts. */
+void vcm_debug_variance_max_blocks(int blocks);
+
 /* sizeof the PODs of smallvcm_amd.h as the library was compiled */
 unsigned vcm_sizeof_scene_desc(void);
 unsigned vcm_sizeof_stats(void);

@@ -134,8 +134,24 @@ class DenoiseParams(C.Structure):
                 ("demodulate", C.c_int)]
 
 
+class DenoiseParams2(C.Structure):
+    """vcm_denoise_params2: vcm_denoise_params, whether the colour stop follows the per-pixel variance, and the number of
+    standard deviations it spans (include/smallvcm_amd.h)"""
+    _fields_ = DenoiseParams._fields_ + [("varianceGuided", C.c_int), ("sigmaVariance", C.c_float)]
+
+
 FEATURE_ALBEDO, FEATURE_NORMAL, FEATURE_DEPTH = 0, 1, 2
 FEATURES = {"albedo": FEATURE_ALBEDO, "normal": FEATURE_NORMAL, "depth": FEATURE_DEPTH}
+
+
+class NoiseStats(C.Structure):
+    """vcm_noise_stats: the reduction of noise = V / (mean^2 + 0.01) over pixels and channels after `iterations`
+    iterations; non-finite elements are counted and left out of mean, max and above (include/smallvcm_amd.h)"""
+    _fields_ = [("iterations", C.c_int), ("elements", C.c_longlong), ("above", C.c_longlong), ("nonFinite", C.c_longlong),
+                ("mean", C.c_double), ("max", C.c_double)]
+
+    def asdict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
 
 
 class Stats(C.Structure):

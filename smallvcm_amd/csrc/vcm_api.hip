@@ -20,6 +20,7 @@
 #include "vcm_kat.h"
 #include "scene_host.h"
 #include "vcm_denoise.h"
+#include "vcm_variance.h"
 
 using namespace vcm;
 
@@ -228,6 +229,11 @@ struct vcm_ctx : Scratch {
     F4 *dGuide, *dAlbedo;             /* N each: normal.xyz | depth, albedo.rgb | 1 */
     F4 *dDnA, *dDnB, *dDenoised;      /* N each: the two images the passes ping-pong between, the result */
     bool featuresValid, denoisedValid;
+    /* per-pixel variance (vcm_variance.h): allocated by vcm_track_variance(ctx, 1) */
+    bool trackVariance;
+    F4 *dVarPrev, *dVarMom;           /* N each: the sum the last update saw, Welford's M2 */
+    int fbIterations;                 /* iterations the framebuffer holds: those since the last vcm_clear_framebuffer; while
+                                         tracking is on (it starts at 0 only) also the k of the two images */
     IterParams P;
     bool inIteration;
     hipEvent_t ev[EV_COUNT];
@@ -986,6 +992,7 @@ void vcm_destroy(vcm_ctx *c)
         DFREE(c->dSpaceMatrix); DFREE(c->dSpaceScanned); DFREE(c->dSpaceTotals); DFREE(c->dSpaceHist); DFREE(c->dWhereDest); DFREE(c->dWherePos);
         DFREE(c->fQ); DFREE(c->fRes); DFREE(c->fKey); DFREE(c->fArrival); DFREE(c->fSorted); DFREE(c->fCount);
         DFREE(c->dGuide); DFREE(c->dAlbedo); DFREE(c->dDnA); DFREE(c->dDnB); DFREE(c->dDenoised);
+        DFREE(c->dVarPrev); DFREE(c->dVarMom);
         c->dScene = NULL; DFREE(c->dSceneBlob); DFREE(c->dFb); DFREE(c->dRngLight); DFREE(c->dRngCam); DFREE(c->dHdr); DFREE(c->dStatsRing); DFREE(c->dStamps);
         for (int i = 0; i < EV_COUNT; i++) (void)hipEventDestroy(c->ev[i]);
         (void)hipStreamSynchronize(c->side);
@@ -2138,6 +2145,14 @@ static int vcm_end_iteration_impl(vcm_ctx *c)
     if (join_grid(c)) return -1;
     if (!c->resolveInFlight && join_splats(c)) return -1;   /* (a merge-free algorithm never waited; K5 aside: the next camera pass waits) */
     if (flush_stamps(c, c->stream) || (c->deviceReady && flush_stamps(c, c->side))) return -1;
+    if (c->trackVariance) {
+        /* behind this iteration's last write to the framebuffer: K5 on the splat stream (the next iteration's splats and K5
+           follow on that stream; every reader joins it through evSplatDone), else the main stream, which has joined */
+        hipStream_t s = c->resolveInFlight ? c->splat : c->stream;
+        HIPCHK(var_launch_update(c->N, c->dFb, c->fbIterations + 1, c->dVarPrev, c->dVarMom, s));
+        if (c->resolveInFlight) HIPCHK(hipEventRecord(c->evSplatDone, c->splat));
+    }
+    c->fbIterations++;
     c->iterations++;   /* :547 */
     c->inIteration = false;
     c->evValid = true;
@@ -2231,6 +2246,13 @@ int vcm_framebuffer_device(vcm_ctx *c, void **devPtr)
     return 0;
 }
 
+static int var_reset_images(vcm_ctx *c)
+{
+    HIPCHK(hipMemsetAsync(c->dVarPrev, 0, (size_t)c->N * sizeof(F4), c->stream));
+    HIPCHK(hipMemsetAsync(c->dVarMom, 0, (size_t)c->N * sizeof(F4), c->stream));
+    return 0;
+}
+
 int vcm_clear_framebuffer(vcm_ctx *c)
 {
     if (!c) return fail("vcm_clear_framebuffer", "ctx is NULL");
@@ -2238,6 +2260,8 @@ int vcm_clear_framebuffer(vcm_ctx *c)
     if (use_device(c)) return -1;
     if (join_splats(c)) return -1;
     HIPCHK(hipMemsetAsync(c->dFb, 0, (size_t)c->N * 3 * sizeof(float), c->stream));
+    c->fbIterations = 0;
+    if (c->trackVariance && var_reset_images(c)) return -1;
     return 0;
 }
 
@@ -2398,6 +2422,193 @@ int vcm_denoise_buffers(int device, int width, int height, const void *colorDev,
     if (a) (void)hipFreeAsync(a, s);
     if (b) (void)hipFreeAsync(b, s);
     if (e != hipSuccess) { g_hipFailed = true; return fail("vcm_denoise_buffers", hipGetErrorString(e)); }
+    return 0;
+}
+
+/* ---- per-pixel variance and the noise statistic (kernels: vcm_variance.hip) ---- */
+int vcm_track_variance(vcm_ctx *c, int on)
+{
+    if (!c) return fail("vcm_track_variance", "ctx is NULL");
+    if (refuse_sharded(c, "vcm_track_variance")) return -1;
+    if (c->inIteration) return fail("vcm_track_variance", "iteration in progress");
+    if (!on) { c->trackVariance = false; return 0; }   /* the images stay until vcm_destroy; switching on again wants a clear */
+    if (c->fbIterations != 0) return fail("vcm_track_variance", "the framebuffer holds iterations already: switch tracking on before the first "
+                                                                 "iteration or right after vcm_clear_framebuffer");
+    g_hipFailed = false;
+    if (ensure_device(c)) return -1;
+    if (!c->dVarPrev && (dalloc(&c->dVarPrev, (size_t)c->N) || dalloc(&c->dVarMom, (size_t)c->N))) return -1;
+    if (join_splats(c)) return -1;
+    if (var_reset_images(c)) return -1;
+    c->trackVariance = true;
+    return 0;
+}
+
+/* tracked, not sharded, and at least two iterations in the images */
+static int need_variance(vcm_ctx *c, const char *who)
+{
+    if (refuse_sharded(c, who)) return -1;
+    if (!c->trackVariance) return fail(who, "vcm_track_variance is off");
+    if (c->fbIterations < 2) return fail(who, "the variance needs at least two iterations");
+    if (use_device(c)) return -1;
+    return join_splats(c);   /* the last update runs behind K5 on the splat stream */
+}
+
+int vcm_variance_device(vcm_ctx *c, void **momDev)
+{
+    if (!c || !momDev) return fail("vcm_variance_device", "NULL argument");
+    if (refuse_sharded(c, "vcm_variance_device")) return -1;
+    if (!c->trackVariance) return fail("vcm_variance_device", "vcm_track_variance is off");
+    if (use_device(c) || join_splats(c)) return -1;
+    *momDev = c->dVarMom;
+    return 0;
+}
+
+int vcm_read_variance(vcm_ctx *c, float *rgbHost)
+{
+    if (!c || !rgbHost) return fail("vcm_read_variance", "NULL argument");
+    g_hipFailed = false;
+    if (need_variance(c, "vcm_read_variance")) return -1;
+    float *d = NULL;
+    if (dalloc(&d, (size_t)c->N * 3)) return -1;
+    hipError_t e = var_launch_read(c->N, c->dVarMom, c->fbIterations, d, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(rgbHost, d, (size_t)c->N * 3 * sizeof(float), hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    (void)hipFree(d);
+    if (e != hipSuccess) { g_hipFailed = true; return fail("vcm_read_variance", hipGetErrorString(e)); }
+    return 0;
+}
+
+int vcm_debug_read_variance_images(vcm_ctx *c, float *prevHost4, float *momHost4)
+{
+    if (!c) return fail("vcm_debug_read_variance_images", "ctx is NULL");
+    if (!c->trackVariance) return fail("vcm_debug_read_variance_images", "vcm_track_variance is off");
+    g_hipFailed = false;
+    if (use_device(c) || join_splats(c)) return -1;
+    if (prevHost4) HIPCHK(hipMemcpyAsync(prevHost4, c->dVarPrev, (size_t)c->N * sizeof(F4), hipMemcpyDeviceToHost, c->stream));
+    if (momHost4) HIPCHK(hipMemcpyAsync(momHost4, c->dVarMom, (size_t)c->N * sizeof(F4), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+/* the statistic of n pixels of (prev, mom) after k iterations, on stream s of the current device; synchronises s */
+static int noise_stats_of(const char *who, long long n, const F4 *prev, const F4 *mom, int k, float threshold, vcm_noise_stats *out,
+                          hipStream_t s)
+{
+    const int cap = var_max_blocks();
+    VarAcc *scratch = NULL, result;   /* cap partials and the result behind them */
+    HIPCHK(hipMallocAsync((void **)&scratch, (size_t)(cap + 1) * sizeof(VarAcc), s));
+    hipError_t e = var_launch_stats(n, prev, mom, k, threshold, cap, scratch, scratch + cap, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(&result, scratch + cap, sizeof(VarAcc), hipMemcpyDeviceToHost, s);
+    (void)hipFreeAsync(scratch, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (e != hipSuccess) { g_hipFailed = true; return fail(who, hipGetErrorString(e)); }
+    var_finish_stats(result, k, n, out);
+    return 0;
+}
+
+int vcm_get_noise_stats(vcm_ctx *c, float threshold, vcm_noise_stats *out)
+{
+    if (!c || !out) return fail("vcm_get_noise_stats", "NULL argument");
+    g_hipFailed = false;
+    if (need_variance(c, "vcm_get_noise_stats")) return -1;
+    return noise_stats_of("vcm_get_noise_stats", c->N, c->dVarPrev, c->dVarMom, c->fbIterations, threshold, out, c->stream);
+}
+
+static int var_buffers_device(const char *who, int device, long long n)
+{
+    if (n <= 0 || n > 0x7fffffffll) return fail(who, "bad size");
+    const int ndev = vcm_device_count();
+    if (ndev <= 0) return fail(who, "no HIP device available (this library has no CPU path)");
+    if (device < 0 || device >= ndev) return fail(who, "device index out of range");
+    g_hipFailed = false;
+    HIPCHK(hipSetDevice(device));
+    return 0;
+}
+
+int vcm_variance_update_buffers(int device, long long n, const void *sumDev3, int k, void *prevDev, void *momDev, void *hipStream)
+{
+    if (!sumDev3 || !prevDev || !momDev) return fail("vcm_variance_update_buffers", "NULL image");
+    if (k < 1) return fail("vcm_variance_update_buffers", "k counts the iterations from 1");
+    if (prevDev == momDev || prevDev == sumDev3 || momDev == sumDev3) return fail("vcm_variance_update_buffers", "the three images must differ");
+    if ((((uintptr_t)prevDev | (uintptr_t)momDev) & 15) || ((uintptr_t)sumDev3 & 3)) return fail("vcm_variance_update_buffers", "prevDev and momDev must be 16-byte aligned (float4 images), sumDev3 4-byte aligned");
+    if (var_buffers_device("vcm_variance_update_buffers", device, n)) return -1;
+    HIPCHK(var_launch_update(n, (const float *)sumDev3, k, (F4 *)prevDev, (F4 *)momDev, (hipStream_t)hipStream));
+    return 0;
+}
+
+int vcm_noise_stats_buffers(int device, long long n, const void *prevDev, const void *momDev, int k, float threshold,
+                            vcm_noise_stats *out, void *hipStream)
+{
+    if (!prevDev || !momDev || !out) return fail("vcm_noise_stats_buffers", "NULL argument");
+    if (k < 2) return fail("vcm_noise_stats_buffers", "the variance needs at least two iterations");
+    if (((uintptr_t)prevDev | (uintptr_t)momDev) & 15) return fail("vcm_noise_stats_buffers", "prevDev and momDev must be 16-byte aligned (float4 images)");
+    if (var_buffers_device("vcm_noise_stats_buffers", device, n)) return -1;
+    return noise_stats_of("vcm_noise_stats_buffers", n, (const F4 *)prevDev, (const F4 *)momDev, k, threshold, out, (hipStream_t)hipStream);
+}
+
+void vcm_debug_variance_max_blocks(int blocks) { var_set_max_blocks(blocks); }
+
+/* ---- the variance-guided filter (vcm_denoise.h "the variance-guided filter") ---- */
+void vcm_denoise_defaults2(vcm_denoise_params2 *out)
+{
+    if (!out) return;
+    vcm_denoise_params p;
+    vcm_denoise_defaults(&p);
+    out->passes = p.passes; out->sigmaColor = p.sigmaColor; out->sigmaNormal = p.sigmaNormal; out->sigmaDepth = p.sigmaDepth;
+    out->demodulate = p.demodulate;
+    out->varianceGuided = VCM_DN_DEFAULT_VARIANCE_GUIDED; out->sigmaVariance = VCM_DN_DEFAULT_SIGMA_VARIANCE;
+}
+
+int vcm_denoise2(vcm_ctx *c, float scale, const vcm_denoise_params2 *p)
+{
+    if (!c) return fail("vcm_denoise2", "ctx is NULL");
+    if (refuse_sharded(c, "vcm_denoise2")) return -1;
+    if (const char *why = dn_check_params2(p)) return fail("vcm_denoise2", why);
+    if (!dn_finite(scale)) return fail("vcm_denoise2", "scale is not finite");
+    if (!p->varianceGuided) { const vcm_denoise_params base = dn_base_params(*p); return vcm_denoise(c, scale, &base); }
+    g_hipFailed = false;
+    if (need_variance(c, "vcm_denoise2")) return -1;   /* tracking on, k >= 2; joins the splat stream */
+    if (!c->featuresValid && vcm_render_features(c)) return -1;
+    if (!c->dDenoised && (dalloc(&c->dDnA, (size_t)c->N) || dalloc(&c->dDnB, (size_t)c->N) || dalloc(&c->dDenoised, (size_t)c->N))) return -1;
+    /* the colour is S scale = mean (k scale): its variance is M2 / (k (k - 1)) (k scale)^2 = M2 scale^2 k / (k - 1) */
+    const float kf = (float)c->fbIterations, varFactor = (scale * scale) * (kf / (kf - 1.f));
+    HIPCHK(dn_launch_denoise2(c->resX, c->resY, NULL, c->dFb, scale, c->dAlbedo, c->dGuide, c->dVarMom, varFactor, c->dDenoised, c->dDnA,
+                              c->dDnB, *p, c->stream));
+    c->denoisedValid = true;
+    return 0;
+}
+
+int vcm_denoise_buffers2(int device, int width, int height, const void *colorDev, const void *albedoDev, const void *guideDev,
+                         const void *momDev, int k, void *outDev, const vcm_denoise_params2 *p, void *hipStream)
+{
+    if (const char *why = dn_check_params2(p)) return fail("vcm_denoise_buffers2", why);
+    if (!p->varianceGuided) {
+        const vcm_denoise_params base = dn_base_params(*p);
+        return vcm_denoise_buffers(device, width, height, colorDev, albedoDev, guideDev, outDev, &base, hipStream);
+    }
+    if (!colorDev || !albedoDev || !guideDev || !momDev || !outDev) return fail("vcm_denoise_buffers2", "NULL image");
+    if (k < 2) return fail("vcm_denoise_buffers2", "the variance needs at least two iterations");
+    if (width <= 0 || height <= 0 || (long long)width * height > 0x7fffffffll) return fail("vcm_denoise_buffers2", "bad size");
+    if (outDev == colorDev || outDev == albedoDev || outDev == guideDev || outDev == momDev) return fail("vcm_denoise_buffers2", "outDev is one of the inputs");
+    const int ndev = vcm_device_count();
+    if (ndev <= 0) return fail("vcm_denoise_buffers2", "no HIP device available (this library has no CPU path)");
+    if (device < 0 || device >= ndev) return fail("vcm_denoise_buffers2", "device index out of range");
+    g_hipFailed = false;
+    HIPCHK(hipSetDevice(device));
+    hipStream_t s = (hipStream_t)hipStream;
+    const size_t bytes = (size_t)width * height * sizeof(F4);
+    void *a = NULL, *b = NULL;
+    if (p->passes > 0) {
+        HIPCHK(hipMallocAsync(&a, bytes, s));
+        hipError_t e = hipMallocAsync(&b, bytes, s);
+        if (e != hipSuccess) { (void)hipFreeAsync(a, s); g_hipFailed = true; return fail("vcm_denoise_buffers2", hipGetErrorString(e)); }
+    }
+    const float varFactor = 1.f / (float)((double)k * (double)(k - 1));
+    hipError_t e = dn_launch_denoise2(width, height, (const F4 *)colorDev, NULL, 1.f, (const F4 *)albedoDev, (const F4 *)guideDev,
+                                      (const F4 *)momDev, varFactor, (F4 *)outDev, (F4 *)a, (F4 *)b, *p, s);
+    if (a) (void)hipFreeAsync(a, s);
+    if (b) (void)hipFreeAsync(b, s);
+    if (e != hipSuccess) { g_hipFailed = true; return fail("vcm_denoise_buffers2", hipGetErrorString(e)); }
     return 0;
 }
 

@@ -157,6 +157,151 @@ VCM_HD F4 dn_filter_pixel(const DnPass &P, int x, int y, F4 albedoP, Load &&load
     return o;
 }
 
+/* ---------------- the variance-guided filter (vcm_denoise2) ----------------
+ * The colour image's .w, which dn_prepare sets to 1 and no tap of the filter above reads, carries the total variance of
+ * the colour the passes see: a tap stays one 16-byte colour load and one guide load.  The colour stop of a tap becomes
+ *   x_c = |c_p - c_q|^2 / (sigmaVariance^2 v~_p + eps)
+ * with v~_p the 3 x 3 Gaussian (1/4, 1/8, 1/16) of .w around the centre at unit spacing in every pass (taps outside the
+ * image skipped, the rest renormalised); sigmaColor and its halving per pass play no part.  eps = 1e-10 is the square of
+ * 1e-5, about the rounding error of a colour near 1: a region without variance then treats any visible difference as an
+ * edge (x_c > 1e10 d^2, weight 0) while equal colours still divide 0 by eps and not by 0 -- every tap adds an exact 0 and
+ * the region comes back bit for bit.  The variance travels with the colour:
+ *   .w_out = sum w_q^2 .w_q / (sum w_q)^2   over the taps that counted, the centre included
+ * (the variance of the weighted mean of independent taps).  A non-finite v~_p falls back to the fixed stop of the pass for
+ * that pixel; a tap whose .w is not finite counts like a non-finite colour. */
+#define VCM_DN_VAR_EPS 1e-10f
+/* vcm_denoise_defaults2: DESIGN.md "Variance", the sweep of tests/variance_tune.py */
+#define VCM_DN_DEFAULT_SIGMA_VARIANCE 4.0f
+#define VCM_DN_DEFAULT_VARIANCE_GUIDED 1
+
+struct DnPass2 {
+    DnPass p;
+    float sigmaVarSqr;   /* sigmaVariance^2 */
+};
+
+inline vcm_denoise_params dn_base_params(const vcm_denoise_params2 &q)
+{
+    vcm_denoise_params p;
+    p.passes = q.passes; p.sigmaColor = q.sigmaColor; p.sigmaNormal = q.sigmaNormal; p.sigmaDepth = q.sigmaDepth; p.demodulate = q.demodulate;
+    return p;
+}
+inline const char *dn_check_params2(const vcm_denoise_params2 *q)
+{
+    if (!q) return "params is NULL";
+    const vcm_denoise_params p = dn_base_params(*q);
+    if (const char *why = dn_check_params(&p)) return why;
+    if (q->varianceGuided != 0 && q->varianceGuided != 1) return "varianceGuided must be 0 or 1";
+    if (!dn_finite(q->sigmaVariance) || !(q->sigmaVariance > 0.f)) return "sigmaVariance must be finite and positive";
+    return NULL;
+}
+inline DnPass2 dn_pass2(const vcm_denoise_params2 &q, int resX, int resY, int pass)
+{
+    DnPass2 P;
+    P.p = dn_pass(dn_base_params(q), resX, resY, pass);
+    P.sigmaVarSqr = q.sigmaVariance * q.sigmaVariance;
+    return P;
+}
+
+/* dn_prepare, and .w = sum_c M2_c varFactor (/ albedo_c^2 where the run demodulates): the total variance of that colour */
+VCM_HD F4 dn_prepare2(float r, float g, float b, float scale, F4 albedo, int demodulate, F4 mom, float varFactor)
+{
+    F4 o = dn_prepare(r, g, b, scale, albedo, demodulate);
+    float vr = mom.x * varFactor, vg = mom.y * varFactor, vb = mom.z * varFactor;
+    if (demodulate) { vr = vr / (albedo.x * albedo.x); vg = vg / (albedo.y * albedo.y); vb = vb / (albedo.z * albedo.z); }
+    o.w = (vr + vg) + vb;
+    return o;
+}
+
+VCM_HD float dn_gauss3(int i) { return (i == 1) ? 0.5f : 0.25f; }   /* products: 1/4, 1/8, 1/16 */
+
+/* v~_p: load(xq, yq, cq, gq) as in dn_filter_pixel */
+template <class Load>
+VCM_HD float dn_center_variance(const DnPass &P, int x, int y, Load &&load)
+{
+    float s = 0.f, n = 0.f;
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+#endif
+    for (int j = 0; j < 3; j++) {
+        const int yq = y + j - 1;
+        if (yq < 0 || yq >= P.resY) continue;
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+#endif
+        for (int i = 0; i < 3; i++) {
+            const int xq = x + i - 1;
+            if (xq < 0 || xq >= P.resX) continue;
+            F4 cq, gq;
+            load(xq, yq, cq, gq);
+            const float g = dn_gauss3(j) * dn_gauss3(i);
+            s = s + g * cq.w;
+            n = n + g;
+        }
+    }
+    return s / n;
+}
+
+struct DnAcc2 { float r, g, b, w, v; };
+
+/* dn_tap with the colour stop 1 / invStop given by the caller, and the tap's variance accumulated */
+VCM_HD void dn_tap2(DnAcc2 &a, const DnPass &P, float invStop, F4 cp, F4 gp, F4 cq, F4 gq, float h)
+{
+    if (!dn_finite3(cq) || !dn_finite(cq.w)) return;
+    const bool missP = gp.w == 0.f, missQ = gq.w == 0.f;
+    if (missP != missQ) return;
+    float w = h, az = 1.f;
+    if (!missP) {
+        const float d = dot(mk3(gp.x, gp.y, gp.z), mk3(gq.x, gq.y, gq.z));
+        if (!(d > 0.f)) return;
+        w = w * dm_powf(d, P.sigmaNormal);
+        const float t = fabsf(gp.w - gq.w) / (P.sigmaDepth * smax(gp.w, gq.w));
+        az = 1.f + 0.25f * (t * t);
+    }
+    const float dr = cq.x - cp.x, dg = cq.y - cp.y, db = cq.z - cp.z;
+    const float dist2 = (dr * dr + dg * dg) + db * db;
+    const float ac = 1.f + 0.25f * (dist2 * invStop);
+    const float t1 = ac * az, t2 = t1 * t1, t4 = t2 * t2;
+    w = w / t4;
+    if (!(w > 0.f) || !dn_finite(w)) return;
+    a.r = a.r + w * dr; a.g = a.g + w * dg; a.b = a.b + w * db; a.w = a.w + w;
+    a.v = a.v + (w * w) * cq.w;
+}
+
+/* the guided pixel (x, y): colour in .xyz, its propagated variance in .w */
+template <class Load>
+VCM_HD F4 dn_filter_pixel2(const DnPass2 &P2, int x, int y, F4 albedoP, Load &&load)
+{
+    const DnPass &P = P2.p;
+    F4 cp, gp;
+    load(x, y, cp, gp);
+    if (!dn_finite3(cp)) return cp;   /* a non-finite centre passes through, its variance with it */
+    float invStop = P.invSigmaColorSqr;
+    const float vt = dn_center_variance(P, x, y, load);
+    if (dn_finite(vt)) invStop = 1.f / (P2.sigmaVarSqr * smax(vt, 0.f) + VCM_DN_VAR_EPS);
+    DnAcc2 a; a.r = a.g = a.b = a.w = a.v = 0.f;
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+#endif
+    for (int j = 0; j < 5; j++) {
+        const int yq = y + (j - 2) * P.step;
+        if (yq < 0 || yq >= P.resY) continue;
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+#endif
+        for (int i = 0; i < 5; i++) {
+            const int xq = x + (i - 2) * P.step;
+            if (xq < 0 || xq >= P.resX) continue;
+            F4 cq, gq;
+            load(xq, yq, cq, gq);
+            dn_tap2(a, P, invStop, cp, gp, cq, gq, dn_b3(j) * dn_b3(i));
+        }
+    }
+    F4 o = cp;
+    if (a.w > 0.f) { o.x = cp.x + a.r / a.w; o.y = cp.y + a.g / a.w; o.z = cp.z + a.b / a.w; o.w = a.v / (a.w * a.w); }
+    if (P.remodulate) { o.x = o.x * albedoP.x; o.y = o.y * albedoP.y; o.z = o.z * albedoP.z; }
+    return o;
+}
+
 /* ---------------- launches (vcm_denoise.hip; the C-ABI of vcm_api.hip calls them) ---------------- */
 #if defined(__HIPCC__)
 struct DnSceneKind { bool envMap, bvh, intPhong, rects, quads; };
@@ -169,6 +314,11 @@ hipError_t dn_launch_features(const DScene *dScene, DnSceneKind kind, int resX, 
 hipError_t dn_launch_unpack(int n, const F4 *src, int comp0, int nComp, float *dst, hipStream_t stream);
 hipError_t dn_launch_denoise(int resX, int resY, const F4 *color, const float *fb3, float scale, const F4 *albedo,
                              const F4 *guide, F4 *out, F4 *tmpA, F4 *tmpB, const vcm_denoise_params &p, hipStream_t stream);
+/* the same with vcm_denoise_params2: varianceGuided == 0 IS dn_launch_denoise; else mom = the moments image and the
+   variance of a colour channel is M2 * varFactor.  tmpA, tmpB as above. */
+hipError_t dn_launch_denoise2(int resX, int resY, const F4 *color, const float *fb3, float scale, const F4 *albedo,
+                              const F4 *guide, const F4 *mom, float varFactor, F4 *out, F4 *tmpA, F4 *tmpB,
+                              const vcm_denoise_params2 &p, hipStream_t stream);
 #endif
 
 } // namespace vcm

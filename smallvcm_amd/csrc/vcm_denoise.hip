@@ -98,6 +98,64 @@ k_atrous(DnPass P, const F4 *__restrict__ color, const F4 *__restrict__ guide, c
     }
 }
 
+/* colour and its variance (dn_prepare2): the first guided pass's input */
+__global__ void __launch_bounds__(256)
+k_dn_prepare_var(int n, const F4 *__restrict__ color, const float *__restrict__ fb3, float scale, const F4 *__restrict__ albedo,
+                 int demodulate, const F4 *__restrict__ mom, float varFactor, F4 *__restrict__ out)
+{
+    for (int p = blockIdx.x * blockDim.x + threadIdx.x; p < n; p += gridDim.x * blockDim.x) {
+        float r, g, b;
+        if (fb3) { r = fb3[(size_t)p * 3]; g = fb3[(size_t)p * 3 + 1]; b = fb3[(size_t)p * 3 + 2]; }
+        else { const F4 c = color[p]; r = c.x; g = c.y; b = c.z; }
+        F4 a = mk4(1.f, 1.f, 1.f, 1.f);
+        if (demodulate) a = albedo[p];
+        out[p] = dn_prepare2(r, g, b, scale, a, demodulate, mom[p], varFactor);
+    }
+}
+
+/* k_atrous with the variance-guided colour stop (dn_filter_pixel2): a sibling, so that k_atrous itself compiles as before.
+   steps 1, 2: the 3 x 3 of the centre's variance lies inside the staged tile (halo >= 2); steps >= 4: nine more global loads */
+template <bool kLds>
+__global__ void __launch_bounds__(256)
+k_atrous_var(DnPass2 P2, const F4 *__restrict__ color, const F4 *__restrict__ guide, const F4 *__restrict__ albedo, F4 *__restrict__ out)
+{
+    const DnPass &P = P2.p;
+    const int tx = (int)threadIdx.x % VCM_DN_TILE_X, ty = (int)threadIdx.x / VCM_DN_TILE_X;
+    const int x0 = (int)blockIdx.x * VCM_DN_TILE_X, y0 = (int)blockIdx.y * VCM_DN_TILE_Y;
+    const int x = x0 + tx, y = y0 + ty;
+    const bool inside = x < P.resX && y < P.resY;
+    if constexpr (kLds) {
+        __shared__ F4 sC[VCM_DN_LDS_X * VCM_DN_LDS_Y], sG[VCM_DN_LDS_X * VCM_DN_LDS_Y];
+        const int halo = 2 * P.step;   /* 2 or 4: the launch picks this kernel for steps 1 and 2 only */
+        const int w = VCM_DN_TILE_X + 2 * halo, h = VCM_DN_TILE_Y + 2 * halo;
+        for (int i = (int)threadIdx.x; i < w * h; i += 256) {
+            const int lx = i % w, ly = i / w;
+            const int gx = x0 - halo + lx, gy = y0 - halo + ly;
+            if (gx >= 0 && gx < P.resX && gy >= 0 && gy < P.resY) {
+                const size_t q = (size_t)gy * P.resX + gx;
+                sC[ly * VCM_DN_LDS_X + lx] = color[q];
+                sG[ly * VCM_DN_LDS_X + lx] = guide[q];
+            }
+        }
+        __syncthreads();
+        if (!inside) return;
+        F4 a = mk4(1.f, 1.f, 1.f, 1.f);
+        if (P.remodulate) a = albedo[(size_t)y * P.resX + x];
+        out[(size_t)y * P.resX + x] = dn_filter_pixel2(P2, x, y, a, [&](int xq, int yq, F4 &cq, F4 &gq) {
+            const int s = (yq - y0 + halo) * VCM_DN_LDS_X + (xq - x0 + halo);
+            cq = sC[s]; gq = sG[s];
+        });
+    } else {
+        if (!inside) return;
+        F4 a = mk4(1.f, 1.f, 1.f, 1.f);
+        if (P.remodulate) a = albedo[(size_t)y * P.resX + x];
+        out[(size_t)y * P.resX + x] = dn_filter_pixel2(P2, x, y, a, [&](int xq, int yq, F4 &cq, F4 &gq) {
+            const size_t q = (size_t)yq * P.resX + xq;
+            cq = color[q]; gq = guide[q];
+        });
+    }
+}
+
 namespace vcm {
 
 hipError_t dn_launch_features(const DScene *dScene, DnSceneKind k, int resX, int p0, int nLocal, F4 *guide, F4 *albedo,
@@ -147,6 +205,28 @@ hipError_t dn_launch_denoise(int resX, int resY, const F4 *color, const float *f
         F4 *dst = (i == p.passes - 1) ? out : (src == tmpA ? tmpB : tmpA);
         if (2 * P.step <= VCM_DN_MAX_HALO) hipLaunchKernelGGL(k_atrous<true>, grid, dim3(256), 0, stream, P, src, guide, albedo, dst);
         else hipLaunchKernelGGL(k_atrous<false>, grid, dim3(256), 0, stream, P, src, guide, albedo, dst);
+        src = dst;
+    }
+    return hipGetLastError();
+}
+
+hipError_t dn_launch_denoise2(int resX, int resY, const F4 *color, const float *fb3, float scale, const F4 *albedo,
+                              const F4 *guide, const F4 *mom, float varFactor, F4 *out, F4 *tmpA, F4 *tmpB,
+                              const vcm_denoise_params2 &p, hipStream_t stream)
+{
+    if (!p.varianceGuided || p.passes == 0)   /* the fixed stop, bit for bit; no pass: the input itself */
+        return dn_launch_denoise(resX, resY, color, fb3, scale, albedo, guide, out, tmpA, tmpB, dn_base_params(p), stream);
+    const long long n = (long long)resX * resY;
+    int blocks = (int)((n + 255) / 256);
+    blocks = blocks > 2048 ? 2048 : blocks;
+    hipLaunchKernelGGL(k_dn_prepare_var, dim3(blocks), dim3(256), 0, stream, (int)n, color, fb3, scale, albedo, p.demodulate ? 1 : 0, mom, varFactor, tmpA);
+    const F4 *src = tmpA;
+    const dim3 grid((unsigned)((resX + VCM_DN_TILE_X - 1) / VCM_DN_TILE_X), (unsigned)((resY + VCM_DN_TILE_Y - 1) / VCM_DN_TILE_Y));
+    for (int i = 0; i < p.passes; i++) {
+        const DnPass2 P = dn_pass2(p, resX, resY, i);
+        F4 *dst = (i == p.passes - 1) ? out : (src == tmpA ? tmpB : tmpA);
+        if (2 * P.p.step <= VCM_DN_MAX_HALO) hipLaunchKernelGGL(k_atrous_var<true>, grid, dim3(256), 0, stream, P, src, guide, albedo, dst);
+        else hipLaunchKernelGGL(k_atrous_var<false>, grid, dim3(256), 0, stream, P, src, guide, albedo, dst);
         src = dst;
     }
     return hipGetLastError();

@@ -13,6 +13,7 @@
 //              [--envmap f.hdr|f.pfm [--envmap-scale S]] [--aperture R --focus D]
 //              [--light-pick uniform|power [--light-pick-mix A] [--light-pick-report]]
 //              [--denoise [passes]] [--denoise-sigma c,n,z] [--no-demodulate] [--features-out prefix]
+//              [--noise-target E [--check-every N] [--max-iterations M]] [--track-variance]
 //              [--gpus N [--shards S] [--inflight K] [--devices 0,1,..] [--collectives rccl|threads] [--same-window]]
 //
 // --gpus N: the multi-GPU host (vcm_farm.hpp): N ranks = N host threads, one per GPU, cut into N / S groups; a
@@ -36,6 +37,13 @@
 // `passes`, --denoise-sigma's sigmaColor,sigmaNormal,sigmaDepth and --no-demodulate applied) before it is written to
 // -o; the unfiltered image is written beside it as <name>.noisy.<ext>.  --features-out P writes the first-hit guide
 // images P.albedo.pfm, P.normal.pfm ("PF") and P.depth.pfm ("Pf", one channel).  Both want one renderer on one GPU.
+//
+// --noise-target E: render to a noise level instead of an iteration count.  The per-pixel variance is tracked
+// (vcm_track_variance) and the mean of the noise statistic (vcm_get_noise_stats: the expected relative squared error
+// V / (mean^2 + 0.01)) is looked at after every N iterations (--check-every, default 4) and after the last one, never
+// before the second; rendering stops at the first look at or below E or after M iterations (--max-iterations, default
+// 1024; -i is not used).  Every look and the iterations used are printed.  --track-variance alone tracks the variance
+// over the -i iterations and prints the statistic at the end.  Both want one renderer on one GPU.
 //
 // -s / -a / -i keep the meaning they have in the reference's CLI
 // (src/config.hxx:246-395; scenes = g_SceneConfigs[0..3], :146-151).
@@ -100,6 +108,9 @@ int main(int argc, char **argv)
     vcm_denoise_params dn;
     vcm_denoise_defaults(&dn);
     std::string featuresOut;
+    bool trackVariance = false, haveTarget = false, haveTargetOption = false;
+    float noiseTarget = 0.f;
+    int checkEvery = 4, maxIterations = 1024;
     for (int i = 1; i < argc; i++) {
         const std::string a(argv[i]);
         auto need = [&](int n) { if (i + n >= argc) { fprintf(stderr, "vcm_render: %s needs %d argument(s)\n", a.c_str(), n); exit(2); } };
@@ -151,6 +162,16 @@ int main(int argc, char **argv)
         }
         else if (a == "--no-demodulate") dn.demodulate = 0;
         else if (a == "--features-out") { need(1); featuresOut = argv[++i]; }
+        else if (a == "--noise-target") {
+            need(1);
+            char *e = NULL;
+            noiseTarget = strtof(argv[++i], &e);
+            if (e == argv[i] || *e || !(noiseTarget >= 0.f)) { fprintf(stderr, "vcm_render: --noise-target needs a number >= 0\n"); return 2; }
+            haveTarget = trackVariance = true;
+        }
+        else if (a == "--check-every") { need(1); checkEvery = atoi(argv[++i]); haveTargetOption = true; }
+        else if (a == "--max-iterations") { need(1); maxIterations = atoi(argv[++i]); haveTargetOption = true; }
+        else if (a == "--track-variance") trackVariance = true;
         else if (a == "--strict") strict = 1;
         else if (a == "--json") json = 1;
         else { fprintf(stderr, "vcm_render: unknown option %s (see the header of vcm_render.cpp)\n", a.c_str()); return 2; }
@@ -163,6 +184,12 @@ int main(int argc, char **argv)
         fprintf(stderr, "vcm_render: --denoise and --features-out want one renderer on one GPU (a farm host denoises the reduced frame with vcm_denoise_buffers)\n");
         return 2;
     }
+    if (trackVariance && (renderers != 1 || gpus > 0)) {
+        fprintf(stderr, "vcm_render: --noise-target and --track-variance want one renderer on one GPU (a farm host reduces the frames and calls vcm_variance_update_buffers)\n");
+        return 2;
+    }
+    if (haveTargetOption && !haveTarget) { fprintf(stderr, "vcm_render: --check-every and --max-iterations go with --noise-target\n"); return 2; }
+    if (haveTarget && (checkEvery < 1 || maxIterations < 2)) { fprintf(stderr, "vcm_render: --check-every >= 1, --max-iterations >= 2\n"); return 2; }
     if (haveAperture != haveFocus) { fprintf(stderr, "vcm_render: --aperture and --focus go together\n"); return 2; }
     if (!pickName.empty() && pickName != "uniform" && pickName != "power") { fprintf(stderr, "vcm_render: --light-pick uniform|power\n"); return 2; }
     if (havePickMix && pickName.empty()) { fprintf(stderr, "vcm_render: --light-pick-mix goes with --light-pick\n"); return 2; }
@@ -297,6 +324,7 @@ int main(int argc, char **argv)
         r[g] = create(seed + g);
         if (!r[g]) return die("vcm_create");
         if (strict && vcm_set_strict_order(r[g], 1)) return die("vcm_set_strict_order");
+        if (trackVariance && vcm_track_variance(r[g], 1)) return die("vcm_track_variance");
     }
     if (pick && (pick->mode != VCM_LIGHT_PICK_UNIFORM || pickReport) && !json) {
         const int nLights = pickScene->base.base.base.nLights;
@@ -323,8 +351,21 @@ int main(int argc, char **argv)
     const auto t0 = std::chrono::steady_clock::now();
     // static schedule of `#pragma omp parallel for` (smallvcm.cxx:98-108): contiguous blocks, the first
     // iterations % renderers threads get one more
+    if (haveTarget) {   // one renderer, iterations 0, 1, ... until the statistic is at or below the target
+        vcm_noise_stats ns;
+        for (iterations = 0; iterations < maxIterations;) {
+            if (vcm_run_iteration(r[0], iterations, minLen, maxLen)) return die("vcm_run_iteration");
+            iterations++;
+            if (iterations < 2 || (iterations % checkEvery != 0 && iterations != maxIterations)) continue;
+            if (vcm_get_noise_stats(r[0], noiseTarget, &ns)) return die("vcm_get_noise_stats");
+            if (!json) printf("noise after %d iteration(s): mean %.9g, max %.9g, %lld of %lld above the target, %lld non-finite\n",
+                              ns.iterations, ns.mean, ns.max, ns.above, ns.elements, ns.nonFinite);
+            if (ns.mean <= (double)noiseTarget) break;
+        }
+        if (!json) printf("noise target %g: %d iteration(s) used\n", noiseTarget, iterations);
+    }
     const int q = iterations / renderers, rem = iterations % renderers;
-    for (int g = 0; g < renderers; g++) {
+    for (int g = 0; g < renderers && !haveTarget; g++) {
         const int lo = g * q + (g < rem ? g : rem), n = q + (g < rem ? 1 : 0);
         for (int it = lo; it < lo + n; it++)
             if (vcm_run_iteration(r[g], it, minLen, maxLen)) return die("vcm_run_iteration");
@@ -346,6 +387,11 @@ int main(int argc, char **argv)
     const float su = 1.f / used;                      // Framebuffer::Scale, smallvcm.cxx:142
     for (size_t i = 0; i < n3; i++) fb[i] = fb[i] * su;
     vcm_get_stats(r[0], &st);
+    if (trackVariance && !haveTarget && !json && iterations >= 2) {
+        vcm_noise_stats ns;
+        if (vcm_get_noise_stats(r[0], 0.f, &ns)) return die("vcm_get_noise_stats");
+        printf("noise after %d iteration(s): mean %.9g, max %.9g, %lld non-finite\n", ns.iterations, ns.mean, ns.max, ns.nonFinite);
+    }
     }
 
     if (!featuresOut.empty()) {   // the guide images, rows top to bottom like SavePFM

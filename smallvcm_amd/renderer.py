@@ -21,7 +21,7 @@ import os
 
 import numpy as np
 
-from ._abi import (DenoiseParams, FEATURES, SceneDesc, SceneDesc2, SceneDesc3, SceneDesc4, SceneDesc5, Stats, SCENE_CONFIGS, VCM_MERGE_RECORD_FLOATS, ALGO_LIGHT_TRACE, ALGO_PPM, ALGO_BPM,
+from ._abi import (DenoiseParams, DenoiseParams2, FEATURES, NoiseStats, SceneDesc, SceneDesc2, SceneDesc3, SceneDesc4, SceneDesc5, Stats, SCENE_CONFIGS, VCM_MERGE_RECORD_FLOATS, ALGO_LIGHT_TRACE, ALGO_PPM, ALGO_BPM,
                    ALGO_BPT, ALGO_VCM)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -122,6 +122,18 @@ def load_library(require_gpu=True):
         L.vcm_denoised_device.argtypes = [vp, C.POINTER(vp)]
         L.vcm_read_denoised_image.argtypes = [vp, C.c_int, C.c_float, C.POINTER(C.c_ubyte)]
         L.vcm_denoise_buffers.argtypes = [C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, C.POINTER(DenoiseParams), vp]
+        L.vcm_track_variance.argtypes = [vp, C.c_int]
+        L.vcm_variance_device.argtypes = [vp, C.POINTER(vp)]
+        L.vcm_read_variance.argtypes = [vp, fp]
+        L.vcm_get_noise_stats.argtypes = [vp, C.c_float, C.POINTER(NoiseStats)]
+        L.vcm_variance_update_buffers.argtypes = [C.c_int, C.c_longlong, vp, C.c_int, vp, vp, vp]
+        L.vcm_noise_stats_buffers.argtypes = [C.c_int, C.c_longlong, vp, vp, C.c_int, C.c_float, C.POINTER(NoiseStats), vp]
+        L.vcm_debug_variance_max_blocks.argtypes = [C.c_int]
+        L.vcm_debug_variance_max_blocks.restype = None
+        L.vcm_denoise_defaults2.argtypes = [C.POINTER(DenoiseParams2)]
+        L.vcm_denoise_defaults2.restype = None
+        L.vcm_denoise2.argtypes = [vp, C.c_float, C.POINTER(DenoiseParams2)]
+        L.vcm_denoise_buffers2.argtypes = [C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, C.c_int, vp, C.POINTER(DenoiseParams2), vp]
         L.vcm_sizeof_scene_desc.restype = C.c_uint
         L.vcm_sizeof_stats.restype = C.c_uint
         _lib = L
@@ -157,6 +169,36 @@ def denoise_params(**kw):
     return p
 
 
+def denoise_params2(**kw):
+    """vcm_denoise_defaults2 with some members replaced: those of denoise_params(), varianceGuided, sigmaVariance"""
+    L = load_library(require_gpu=False)
+    p = DenoiseParams2()
+    L.vcm_denoise_defaults2(C.byref(p))
+    for k, v in kw.items():
+        if k not in [n for n, _ in DenoiseParams2._fields_]:
+            raise TypeError("unknown denoise parameter %r" % k)
+        setattr(p, k, v)
+    return p
+
+
+def denoise_tensors2(color, albedo, guide, mom, k, out=None, **params):
+    """vcm_denoise_buffers2 over torch tensors: denoise_tensors() with the moments image mom ([H, W, 4]: M2.rgb | 0, as
+    variance_update_tensors keeps it) after k iterations, `color` being the mean; params: see denoise_params2()"""
+    import torch
+    L = load_library()
+    for t in (color, albedo, guide, mom):
+        if t.dtype != torch.float32 or not t.is_cuda or not t.is_contiguous() or t.dim() != 3 or t.shape != color.shape or t.shape[2] != 4:
+            raise ValueError("denoise_tensors2 wants contiguous float32 GPU tensors of one shape [H, W, 4]")
+    if out is None:
+        out = torch.empty_like(color)
+    dev = color.device.index if color.device.index is not None else torch.cuda.current_device()
+    p = denoise_params2(**params)
+    _check(L, L.vcm_denoise_buffers2(dev, int(color.shape[1]), int(color.shape[0]), color.data_ptr(), albedo.data_ptr(), guide.data_ptr(),
+                                     mom.data_ptr(), int(k), out.data_ptr(), C.byref(p), torch.cuda.current_stream(dev).cuda_stream),
+           "vcm_denoise_buffers2")
+    return out
+
+
 def denoise_tensors(color, albedo, guide, out=None, **params):
     """vcm_denoise_buffers over torch tensors: [H, W, 4] float32, contiguous, on one GPU (colour rgb?, albedo rgb1,
     guide normal.xyz | depth); asynchronous on torch's current stream of that device.  Returns `out` (a new tensor when
@@ -173,6 +215,60 @@ def denoise_tensors(color, albedo, guide, out=None, **params):
     _check(L, L.vcm_denoise_buffers(dev, int(color.shape[1]), int(color.shape[0]), color.data_ptr(), albedo.data_ptr(), guide.data_ptr(),
                                     out.data_ptr(), C.byref(p), torch.cuda.current_stream(dev).cuda_stream), "vcm_denoise_buffers")
     return out
+
+
+def _variance_tensors(who, prev, mom):
+    import torch
+    for t in (prev, mom):
+        if t.dtype != torch.float32 or not t.is_cuda or not t.is_contiguous() or t.dim() < 2 or t.shape[-1] != 4 or t.shape != prev.shape:
+            raise ValueError("%s wants prev and mom as contiguous float32 GPU tensors of one shape [..., 4]" % who)
+    n = prev.numel() // 4
+    dev = prev.device.index if prev.device.index is not None else torch.cuda.current_device()
+    return n, dev, torch.cuda.current_stream(dev).cuda_stream
+
+
+def variance_update_tensors(sum3, k, prev, mom):
+    """vcm_variance_update_buffers over torch tensors: iteration k's (1, 2, ...) Welford update of prev = {S_{k-1}.rgb, 0}
+    and mom = {M2.rgb, 0} ([..., 4] float32, zero before k = 1) from the running sum sum3 ([..., 3] float32) of the same
+    pixels, in place; asynchronous on torch's current stream of that device.  Returns (prev, mom)."""
+    import torch
+    n, dev, stream = _variance_tensors("variance_update_tensors", prev, mom)
+    if sum3.dtype != torch.float32 or not sum3.is_cuda or not sum3.is_contiguous() or sum3.shape[-1] != 3 or sum3.numel() != 3 * n \
+            or sum3.device != prev.device:
+        raise ValueError("variance_update_tensors wants sum3 as a contiguous float32 GPU tensor [..., 3] of the same pixels")
+    L = load_library()
+    _check(L, L.vcm_variance_update_buffers(dev, n, sum3.data_ptr(), int(k), prev.data_ptr(), mom.data_ptr(), stream),
+           "vcm_variance_update_buffers")
+    return prev, mom
+
+
+def noise_stats_tensors(prev, mom, k, threshold=float("inf")):
+    """vcm_noise_stats_buffers over the tensors of variance_update_tensors after k >= 2 iterations -> the dict of
+    vcm_noise_stats; synchronises torch's current stream of that device"""
+    n, dev, stream = _variance_tensors("noise_stats_tensors", prev, mom)
+    L = load_library()
+    st = NoiseStats()
+    _check(L, L.vcm_noise_stats_buffers(dev, n, prev.data_ptr(), mom.data_ptr(), int(k), threshold, C.byref(st), stream),
+           "vcm_noise_stats_buffers")
+    return st.asdict()
+
+
+def render_until(renderer, noise, check_every=4, max_iterations=1024):
+    """Run iterations 0, 1, ... of `renderer` (RunIteration, mIterations, backend.noise_stats: VertexCM, or a stand-in)
+    until the mean of the noise statistic is <= `noise`: it is looked at after every `check_every` iterations and after the
+    last one, never before the second, and rendering stops at the first look at or below the target or at
+    `max_iterations`.  Returns the looks, in order: vcm_noise_stats dicts (`above` counts the elements over the target)."""
+    if check_every < 1 or max_iterations < 2:
+        raise ValueError("render_until wants check_every >= 1 and max_iterations >= 2")
+    history = []
+    while renderer.mIterations < max_iterations:
+        renderer.RunIteration(renderer.mIterations)
+        k = renderer.mIterations
+        if k >= 2 and (k % check_every == 0 or k == max_iterations):
+            history.append(renderer.backend.noise_stats(noise))
+            if history[-1]["mean"] <= noise:
+                break
+    return history
 
 
 class HipBackend:
@@ -368,12 +464,45 @@ class HipBackend:
         _check(self.L, self.L.vcm_read_denoised(self.ctx, out.ctypes.data_as(C.POINTER(C.c_float))), "vcm_read_denoised")
         return out
 
+    def denoise2(self, scale, **params):
+        """denoise() through vcm_denoise2; params: see denoise_params2() (varianceGuided=1 wants track_variance() and two
+        iterations)"""
+        p = denoise_params2(**params)
+        _check(self.L, self.L.vcm_denoise2(self.ctx, scale, C.byref(p)), "vcm_denoise2")
+        out = np.zeros((self.resy, self.resx, 3), np.float32)
+        _check(self.L, self.L.vcm_read_denoised(self.ctx, out.ctypes.data_as(C.POINTER(C.c_float))), "vcm_read_denoised")
+        return out
+
     def read_denoised_image(self, fmt, gamma=2.2):
         """the last denoised image in the encodings of read_image"""
         out = np.zeros((self.resy, self.resx, 3 if fmt == 0 else 4), np.uint8)
         _check(self.L, self.L.vcm_read_denoised_image(self.ctx, fmt, gamma, out.ctypes.data_as(C.POINTER(C.c_ubyte))),
                "vcm_read_denoised_image")
         return out
+
+    # ---- per-pixel variance and the noise statistic --------------------------
+    def track_variance(self, on=True):
+        """accumulate the per-pixel variance of the running mean beside the framebuffer from the next iteration on (before
+        the first iteration, or right after clear_framebuffer); 32 bytes per pixel"""
+        _check(self.L, self.L.vcm_track_variance(self.ctx, 1 if on else 0), "vcm_track_variance")
+
+    def variance(self):
+        """variance of the mean image, [H, W, 3]; needs two tracked iterations"""
+        out = np.zeros((self.resy, self.resx, 3), np.float32)
+        _check(self.L, self.L.vcm_read_variance(self.ctx, out.ctypes.data_as(C.POINTER(C.c_float))), "vcm_read_variance")
+        return out
+
+    def variance_device(self):
+        """device pointer of the moments image {M2.rgb, 0} (float4 per pixel)"""
+        m = C.c_void_p()
+        _check(self.L, self.L.vcm_variance_device(self.ctx, C.byref(m)), "vcm_variance_device")
+        return m.value
+
+    def noise_stats(self, threshold=float("inf")):
+        """vcm_get_noise_stats: {iterations, elements, above, nonFinite, mean, max} of V / (mean^2 + 0.01)"""
+        st = NoiseStats()
+        _check(self.L, self.L.vcm_get_noise_stats(self.ctx, threshold, C.byref(st)), "vcm_get_noise_stats")
+        return st.asdict()
 
     def stats_at(self, ago):
         """counters and phase times of the iteration `ago` iterations before the last completed one (<= 63)"""
@@ -442,6 +571,13 @@ class VertexCM:
         """GetFramebuffer() through the edge-avoiding denoiser (the reference has no such call); params: see
         denoise_params()"""
         return self.backend.denoise(1.0 / self.mIterations if self.mIterations > 0 else 1.0, **params)
+
+    def render_until(self, noise, check_every=4, max_iterations=1024):
+        """render_until() of this module on this renderer, which must be new: variance tracking is switched on first"""
+        if self.mIterations != 0:
+            raise RuntimeError("smallvcm_amd: render_until wants a renderer that has not run an iteration (variance tracking starts with the first)")
+        self.backend.track_variance()
+        return render_until(self, noise, check_every, max_iterations)
 
     def framebuffer_sum(self):
         return self.backend.framebuffer_sum()
