@@ -89,6 +89,11 @@ int vcm_debug_read_variance_images(vcm_ctx *ctx, float *prevHost4, float *momHos
  * combination tree, and so the last bits of vcm_noise_stats.mean, depend on it: not for production hosts. */
 void vcm_debug_variance_max_blocks(int blocks);
 
+/* The images of a context with vcm_track_robust on, as they stand after the last iteration: prev = { S_{k-1}.rgb, 0 }, W*H
+ * float4, and the M bucket planes, M*W*H float4 (either may be NULL).  Synchronises.  The grid of the robust kernels is
+ * that of the variance kernels: vcm_debug_variance_max_blocks caps both. */
+int vcm_debug_read_robust_images(vcm_ctx *ctx, float *prevHost4, float *bucketsHost4);
+
 /* sizeof the PODs of smallvcm_amd.h as the library was compiled */
 unsigned vcm_sizeof_scene_desc(void);
 unsigned vcm_sizeof_stats(void);

@@ -154,6 +154,20 @@ class NoiseStats(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+ROBUST_DEFAULT_BUCKETS = 7   # VCM_ROBUST_DEFAULT_BUCKETS
+
+
+class RobustStats(C.Structure):
+    """vcm_robust_stats: what the median-of-means rule decided over the image after `iterations` iterations in `buckets`
+    buckets: pixels with a trim t > 0, pixels with a dropped (non-finite) bucket, mean and maximum of the Gini coefficient
+    (include/smallvcm_amd.h)"""
+    _fields_ = [("iterations", C.c_int), ("buckets", C.c_int), ("pixels", C.c_longlong), ("trimmed", C.c_longlong),
+                ("nonFinite", C.c_longlong), ("meanGini", C.c_double), ("maxGini", C.c_double)]
+
+    def asdict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
 class Stats(C.Structure):
     _fields_ = [("lightVertices", C.c_longlong), ("gridVertices", C.c_longlong),
                 ("lightRays", C.c_longlong), ("cameraRays", C.c_longlong),

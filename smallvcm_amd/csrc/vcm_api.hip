@@ -21,6 +21,7 @@
 #include "scene_host.h"
 #include "vcm_denoise.h"
 #include "vcm_variance.h"
+#include "vcm_robust.h"
 
 using namespace vcm;
 
@@ -232,6 +233,9 @@ struct vcm_ctx : Scratch {
     /* per-pixel variance (vcm_variance.h): allocated by vcm_track_variance(ctx, 1) */
     bool trackVariance;
     F4 *dVarPrev, *dVarMom;           /* N each: the sum the last update saw, Welford's M2 */
+    /* the firefly-robust estimate (vcm_robust.h): allocated by vcm_track_robust(ctx, M) */
+    int robustBuckets, robustAlloc;   /* M while tracking is on, else 0; the M the planes were allocated for */
+    F4 *dRobPrev, *dRobBuckets, *dRobOut;   /* N, M x N, N: the sum the last update saw, the bucket planes, the resolved image */
     int fbIterations;                 /* iterations the framebuffer holds: those since the last vcm_clear_framebuffer; while
                                          tracking is on (it starts at 0 only) also the k of the two images */
     IterParams P;
@@ -993,6 +997,7 @@ void vcm_destroy(vcm_ctx *c)
         DFREE(c->fQ); DFREE(c->fRes); DFREE(c->fKey); DFREE(c->fArrival); DFREE(c->fSorted); DFREE(c->fCount);
         DFREE(c->dGuide); DFREE(c->dAlbedo); DFREE(c->dDnA); DFREE(c->dDnB); DFREE(c->dDenoised);
         DFREE(c->dVarPrev); DFREE(c->dVarMom);
+        DFREE(c->dRobPrev); DFREE(c->dRobBuckets); DFREE(c->dRobOut);
         c->dScene = NULL; DFREE(c->dSceneBlob); DFREE(c->dFb); DFREE(c->dRngLight); DFREE(c->dRngCam); DFREE(c->dHdr); DFREE(c->dStatsRing); DFREE(c->dStamps);
         for (int i = 0; i < EV_COUNT; i++) (void)hipEventDestroy(c->ev[i]);
         (void)hipStreamSynchronize(c->side);
@@ -2152,6 +2157,11 @@ static int vcm_end_iteration_impl(vcm_ctx *c)
         HIPCHK(var_launch_update(c->N, c->dFb, c->fbIterations + 1, c->dVarPrev, c->dVarMom, s));
         if (c->resolveInFlight) HIPCHK(hipEventRecord(c->evSplatDone, c->splat));
     }
+    if (c->robustBuckets) {   /* the same place on the same stream, behind the variance update when both are on */
+        hipStream_t s = c->resolveInFlight ? c->splat : c->stream;
+        HIPCHK(robust_launch_update(c->N, c->dFb, c->fbIterations + 1, c->robustBuckets, c->dRobPrev, c->dRobBuckets, s));
+        if (c->resolveInFlight) HIPCHK(hipEventRecord(c->evSplatDone, c->splat));
+    }
     c->fbIterations++;
     c->iterations++;   /* :547 */
     c->inIteration = false;
@@ -2253,6 +2263,13 @@ static int var_reset_images(vcm_ctx *c)
     return 0;
 }
 
+static int robust_reset_images(vcm_ctx *c)
+{
+    HIPCHK(hipMemsetAsync(c->dRobPrev, 0, (size_t)c->N * sizeof(F4), c->stream));
+    HIPCHK(hipMemsetAsync(c->dRobBuckets, 0, (size_t)c->N * (size_t)c->robustAlloc * sizeof(F4), c->stream));
+    return 0;
+}
+
 int vcm_clear_framebuffer(vcm_ctx *c)
 {
     if (!c) return fail("vcm_clear_framebuffer", "ctx is NULL");
@@ -2262,6 +2279,7 @@ int vcm_clear_framebuffer(vcm_ctx *c)
     HIPCHK(hipMemsetAsync(c->dFb, 0, (size_t)c->N * 3 * sizeof(float), c->stream));
     c->fbIterations = 0;
     if (c->trackVariance && var_reset_images(c)) return -1;
+    if (c->robustBuckets && robust_reset_images(c)) return -1;
     return 0;
 }
 
@@ -2610,6 +2628,139 @@ int vcm_denoise_buffers2(int device, int width, int height, const void *colorDev
     if (b) (void)hipFreeAsync(b, s);
     if (e != hipSuccess) { g_hipFailed = true; return fail("vcm_denoise_buffers2", hipGetErrorString(e)); }
     return 0;
+}
+
+/* ---- the firefly-robust estimate (kernels: vcm_robust.hip) ---- */
+int vcm_track_robust(vcm_ctx *c, int buckets)
+{
+    if (!c) return fail("vcm_track_robust", "ctx is NULL");
+    if (refuse_sharded(c, "vcm_track_robust")) return -1;
+    if (c->inIteration) return fail("vcm_track_robust", "iteration in progress");
+    if (!buckets) { c->robustBuckets = 0; return 0; }   /* the images stay until vcm_destroy; switching on again wants a clear */
+    if (!robust_buckets_ok(buckets)) return fail("vcm_track_robust", "buckets must be odd, 3 .. 15 (0 switches tracking off)");
+    if (c->fbIterations != 0) return fail("vcm_track_robust", "the framebuffer holds iterations already: switch tracking on before the first "
+                                                               "iteration or right after vcm_clear_framebuffer");
+    g_hipFailed = false;
+    if (ensure_device(c)) return -1;
+    if (join_splats(c)) return -1;
+    if (c->dRobBuckets && c->robustAlloc != buckets) {   /* another M than last time: the planes are allocated anew */
+        HIPCHK(hipStreamSynchronize(c->stream));
+        (void)hipFree(c->dRobBuckets);
+        c->dRobBuckets = NULL;
+    }
+    if (!c->dRobPrev && (dalloc(&c->dRobPrev, (size_t)c->N) || dalloc(&c->dRobOut, (size_t)c->N))) return -1;
+    if (!c->dRobBuckets && dalloc(&c->dRobBuckets, (size_t)c->N * (size_t)buckets)) return -1;
+    c->robustAlloc = buckets;
+    if (robust_reset_images(c)) return -1;
+    c->robustBuckets = buckets;
+    return 0;
+}
+
+/* tracked, not sharded, and at least M iterations in the buckets */
+static int need_robust(vcm_ctx *c, const char *who)
+{
+    if (refuse_sharded(c, who)) return -1;
+    if (!c->robustBuckets) return fail(who, "vcm_track_robust is off");
+    if (c->fbIterations < c->robustBuckets) return fail(who, "the robust estimate needs at least as many iterations as buckets");
+    if (use_device(c)) return -1;
+    return join_splats(c);   /* the last update runs behind K5 on the splat stream */
+}
+
+int vcm_robust_resolve(vcm_ctx *c)
+{
+    if (!c) return fail("vcm_robust_resolve", "ctx is NULL");
+    g_hipFailed = false;
+    if (need_robust(c, "vcm_robust_resolve")) return -1;
+    HIPCHK(robust_launch_resolve(c->N, c->dRobPrev, c->dRobBuckets, c->fbIterations, c->robustBuckets, c->dRobOut, c->stream));
+    return 0;
+}
+
+int vcm_read_robust(vcm_ctx *c, float *rgbHost)
+{
+    if (!c || !rgbHost) return fail("vcm_read_robust", "NULL argument");
+    if (vcm_robust_resolve(c)) return -1;
+    return read_f4_components(c, "vcm_read_robust", c->dRobOut, 0, 3, rgbHost);
+}
+
+int vcm_robust_device(vcm_ctx *c, void **devPtr)
+{
+    if (!c || !devPtr) return fail("vcm_robust_device", "NULL argument");
+    if (vcm_robust_resolve(c)) return -1;
+    *devPtr = c->dRobOut;
+    return 0;
+}
+
+int vcm_debug_read_robust_images(vcm_ctx *c, float *prevHost4, float *bucketsHost4)
+{
+    if (!c) return fail("vcm_debug_read_robust_images", "ctx is NULL");
+    if (!c->robustBuckets) return fail("vcm_debug_read_robust_images", "vcm_track_robust is off");
+    g_hipFailed = false;
+    if (use_device(c) || join_splats(c)) return -1;
+    if (prevHost4) HIPCHK(hipMemcpyAsync(prevHost4, c->dRobPrev, (size_t)c->N * sizeof(F4), hipMemcpyDeviceToHost, c->stream));
+    if (bucketsHost4) HIPCHK(hipMemcpyAsync(bucketsHost4, c->dRobBuckets, (size_t)c->N * (size_t)c->robustBuckets * sizeof(F4), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+/* the statistics of n pixels of (prev, buckets) after k iterations, on stream s of the current device; synchronises s */
+static int robust_stats_of(const char *who, long long n, const F4 *prev, const F4 *buckets, int k, int M, vcm_robust_stats *out, hipStream_t s)
+{
+    const int cap = var_max_blocks();
+    VarAcc *scratch = NULL, result;   /* cap partials and the result behind them */
+    HIPCHK(hipMallocAsync((void **)&scratch, (size_t)(cap + 1) * sizeof(VarAcc), s));
+    hipError_t e = robust_launch_stats(n, prev, buckets, k, M, cap, scratch, scratch + cap, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(&result, scratch + cap, sizeof(VarAcc), hipMemcpyDeviceToHost, s);
+    (void)hipFreeAsync(scratch, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (e != hipSuccess) { g_hipFailed = true; return fail(who, hipGetErrorString(e)); }
+    robust_finish_stats(result, k, M, n, out);
+    return 0;
+}
+
+int vcm_get_robust_stats(vcm_ctx *c, vcm_robust_stats *out)
+{
+    if (!c || !out) return fail("vcm_get_robust_stats", "NULL argument");
+    g_hipFailed = false;
+    if (need_robust(c, "vcm_get_robust_stats")) return -1;
+    return robust_stats_of("vcm_get_robust_stats", c->N, c->dRobPrev, c->dRobBuckets, c->fbIterations, c->robustBuckets, out, c->stream);
+}
+
+/* the checks the three _buffers calls share, in the order the header gives the refusals */
+static int robust_buffers_check(const char *who, int device, long long n, int k, int buckets, bool resolving)
+{
+    if (!robust_buckets_ok(buckets)) return fail(who, "buckets must be odd, 3 .. 15");
+    if (k < 1) return fail(who, "k counts the iterations from 1");
+    if (resolving && k < buckets) return fail(who, "the robust estimate needs at least as many iterations as buckets");
+    return var_buffers_device(who, device, n);
+}
+
+int vcm_robust_update_buffers(int device, long long n, const void *sumDev3, int k, int buckets, void *prevDev, void *bucketsDev, void *hipStream)
+{
+    if (!sumDev3 || !prevDev || !bucketsDev) return fail("vcm_robust_update_buffers", "NULL image");
+    if (prevDev == bucketsDev || prevDev == sumDev3 || bucketsDev == sumDev3) return fail("vcm_robust_update_buffers", "the three images must differ");
+    if ((((uintptr_t)prevDev | (uintptr_t)bucketsDev) & 15) || ((uintptr_t)sumDev3 & 3)) return fail("vcm_robust_update_buffers", "prevDev and bucketsDev must be 16-byte aligned (float4 images), sumDev3 4-byte aligned");
+    if (robust_buffers_check("vcm_robust_update_buffers", device, n, k, buckets, false)) return -1;
+    HIPCHK(robust_launch_update(n, (const float *)sumDev3, k, buckets, (F4 *)prevDev, (F4 *)bucketsDev, (hipStream_t)hipStream));
+    return 0;
+}
+
+int vcm_robust_resolve_buffers(int device, long long n, const void *prevDev, const void *bucketsDev, int k, int buckets, void *outDev, void *hipStream)
+{
+    if (!prevDev || !bucketsDev || !outDev) return fail("vcm_robust_resolve_buffers", "NULL image");
+    if (((uintptr_t)prevDev | (uintptr_t)bucketsDev | (uintptr_t)outDev) & 15) return fail("vcm_robust_resolve_buffers", "prevDev, bucketsDev and outDev must be 16-byte aligned (float4 images)");
+    if (robust_buffers_check("vcm_robust_resolve_buffers", device, n, k, buckets, true)) return -1;
+    const uintptr_t o = (uintptr_t)outDev, b = (uintptr_t)bucketsDev, bytes = (uintptr_t)n * sizeof(F4);
+    if (outDev == prevDev || (o + bytes > b && o < b + bytes * (uintptr_t)buckets)) return fail("vcm_robust_resolve_buffers", "outDev is one of the inputs");
+    HIPCHK(robust_launch_resolve(n, (const F4 *)prevDev, (const F4 *)bucketsDev, k, buckets, (F4 *)outDev, (hipStream_t)hipStream));
+    return 0;
+}
+
+int vcm_robust_stats_buffers(int device, long long n, const void *prevDev, const void *bucketsDev, int k, int buckets, vcm_robust_stats *out, void *hipStream)
+{
+    if (!prevDev || !bucketsDev || !out) return fail("vcm_robust_stats_buffers", "NULL argument");
+    if (((uintptr_t)prevDev | (uintptr_t)bucketsDev) & 15) return fail("vcm_robust_stats_buffers", "prevDev and bucketsDev must be 16-byte aligned (float4 images)");
+    if (robust_buffers_check("vcm_robust_stats_buffers", device, n, k, buckets, true)) return -1;
+    return robust_stats_of("vcm_robust_stats_buffers", n, (const F4 *)prevDev, (const F4 *)bucketsDev, k, buckets, out, (hipStream_t)hipStream);
 }
 
 int vcm_iterations(vcm_ctx *c) { return c ? c->iterations : 0; }

@@ -154,6 +154,16 @@ inline void var_finish_stats(const VarAcc &a, int k, long long n, vcm_noise_stat
 
 /* ---------------- launches (vcm_variance.hip; the C-ABI of vcm_api.hip calls them) ---------------- */
 #if defined(__HIPCC__)
+/* the tree over the LDS slots of a workgroup (vcm_robust.hip reduces with it too); v[0] holds the result for lane 0
+   afterwards */
+__device__ inline void var_block_tree(VarAcc *v, int lane)
+{
+    __syncthreads();
+    for (int s = 0; s < VCM_VAR_TREE_STEPS; s++) {
+        var_tree_step(v, s, lane);
+        __syncthreads();
+    }
+}
 /* the cap of the grid of the kernels (vcm_debug_variance_max_blocks) */
 int var_max_blocks();
 void var_set_max_blocks(int blocks);

@@ -27,16 +27,6 @@ k_var_update(long long n, const float *__restrict__ sum3, int k, float km1, floa
     }
 }
 
-/* the tree of vcm_variance.h over the workgroup's slots; v[0] holds the result for lane 0 afterwards */
-__device__ inline void var_block_tree(VarAcc *v, int lane)
-{
-    __syncthreads();
-    for (int s = 0; s < VCM_VAR_TREE_STEPS; s++) {
-        var_tree_step(v, s, lane);
-        __syncthreads();
-    }
-}
-
 __global__ void __launch_bounds__(VCM_VAR_BLOCK)
 k_var_stats(long long n, const F4 *__restrict__ prev, const F4 *__restrict__ mom, float kf, float kk, float threshold,
             VarAcc *__restrict__ partials)

@@ -13,7 +13,7 @@
 //              [--envmap f.hdr|f.pfm [--envmap-scale S]] [--aperture R --focus D]
 //              [--light-pick uniform|power [--light-pick-mix A] [--light-pick-report]]
 //              [--denoise [passes]] [--denoise-sigma c,n,z] [--no-demodulate] [--features-out prefix]
-//              [--noise-target E [--check-every N] [--max-iterations M]] [--track-variance]
+//              [--noise-target E [--check-every N] [--max-iterations M]] [--track-variance] [--robust [M]]
 //              [--gpus N [--shards S] [--inflight K] [--devices 0,1,..] [--collectives rccl|threads] [--same-window]]
 //
 // --gpus N: the multi-GPU host (vcm_farm.hpp): N ranks = N host threads, one per GPU, cut into N / S groups; a
@@ -44,6 +44,12 @@
 // before the second; rendering stops at the first look at or below E or after M iterations (--max-iterations, default
 // 1024; -i is not used).  Every look and the iterations used are printed.  --track-variance alone tracks the variance
 // over the -i iterations and prints the statistic at the end.  Both want one renderer on one GPU.
+//
+// --robust [M]: the image written to -o (and summed into image_mean) is the firefly-robust estimate instead of the mean:
+// the iterations go round-robin into M buckets (vcm_track_robust; odd, 3 .. 15, default VCM_ROBUST_DEFAULT_BUCKETS) and
+// every pixel averages the central bucket means, trimmed by their Gini coefficient (vcm_read_robust).  Wants -i >= M and
+// one renderer on one GPU.  What the rule decided (vcm_get_robust_stats) is printed, and is "robust" in --json.  With
+// --denoise it is refused: filtering the robust image is a host's own vcm_robust_device + vcm_denoise_buffers for now.
 //
 // -s / -a / -i keep the meaning they have in the reference's CLI
 // (src/config.hxx:246-395; scenes = g_SceneConfigs[0..3], :146-151).
@@ -111,6 +117,8 @@ int main(int argc, char **argv)
     bool trackVariance = false, haveTarget = false, haveTargetOption = false;
     float noiseTarget = 0.f;
     int checkEvery = 4, maxIterations = 1024;
+    int robust = 0;
+    vcm_robust_stats rs = {};
     for (int i = 1; i < argc; i++) {
         const std::string a(argv[i]);
         auto need = [&](int n) { if (i + n >= argc) { fprintf(stderr, "vcm_render: %s needs %d argument(s)\n", a.c_str(), n); exit(2); } };
@@ -172,6 +180,11 @@ int main(int argc, char **argv)
         else if (a == "--check-every") { need(1); checkEvery = atoi(argv[++i]); haveTargetOption = true; }
         else if (a == "--max-iterations") { need(1); maxIterations = atoi(argv[++i]); haveTargetOption = true; }
         else if (a == "--track-variance") trackVariance = true;
+        else if (a == "--robust") {
+            robust = VCM_ROBUST_DEFAULT_BUCKETS;
+            if (i + 1 < argc && argv[i + 1][0] >= '0' && argv[i + 1][0] <= '9') robust = atoi(argv[++i]);
+            if (robust < 3 || robust > 15 || robust % 2 == 0) { fprintf(stderr, "vcm_render: --robust takes an odd number of buckets, 3 .. 15\n"); return 2; }
+        }
         else if (a == "--strict") strict = 1;
         else if (a == "--json") json = 1;
         else { fprintf(stderr, "vcm_render: unknown option %s (see the header of vcm_render.cpp)\n", a.c_str()); return 2; }
@@ -186,6 +199,14 @@ int main(int argc, char **argv)
     }
     if (trackVariance && (renderers != 1 || gpus > 0)) {
         fprintf(stderr, "vcm_render: --noise-target and --track-variance want one renderer on one GPU (a farm host reduces the frames and calls vcm_variance_update_buffers)\n");
+        return 2;
+    }
+    if (robust && denoise) {
+        fprintf(stderr, "vcm_render: --robust and --denoise do not combine yet: the filter takes the mean (a host may feed vcm_robust_device to vcm_denoise_buffers)\n");
+        return 2;
+    }
+    if (robust && (renderers != 1 || gpus > 0)) {
+        fprintf(stderr, "vcm_render: --robust wants one renderer on one GPU (a farm host reduces the frames and calls vcm_robust_update_buffers)\n");
         return 2;
     }
     if (haveTargetOption && !haveTarget) { fprintf(stderr, "vcm_render: --check-every and --max-iterations go with --noise-target\n"); return 2; }
@@ -325,6 +346,7 @@ int main(int argc, char **argv)
         if (!r[g]) return die("vcm_create");
         if (strict && vcm_set_strict_order(r[g], 1)) return die("vcm_set_strict_order");
         if (trackVariance && vcm_track_variance(r[g], 1)) return die("vcm_track_variance");
+        if (robust && vcm_track_robust(r[g], robust)) return die("vcm_track_robust");
     }
     if (pick && (pick->mode != VCM_LIGHT_PICK_UNIFORM || pickReport) && !json) {
         const int nLights = pickScene->base.base.base.nLights;
@@ -392,6 +414,12 @@ int main(int argc, char **argv)
         if (vcm_get_noise_stats(r[0], 0.f, &ns)) return die("vcm_get_noise_stats");
         printf("noise after %d iteration(s): mean %.9g, max %.9g, %lld non-finite\n", ns.iterations, ns.mean, ns.max, ns.nonFinite);
     }
+    if (robust) {   // the estimate takes the mean's place in everything below
+        if (vcm_read_robust(r[0], fb.data())) return die("vcm_read_robust");
+        if (vcm_get_robust_stats(r[0], &rs)) return die("vcm_get_robust_stats");
+        if (!json) printf("robust estimate after %d iteration(s) in %d buckets: %lld of %lld pixels trimmed, %lld with a non-finite bucket, Gini mean %.9g, max %.9g\n",
+                          rs.iterations, rs.buckets, rs.trimmed, rs.pixels, rs.nonFinite, rs.meanGini, rs.maxGini);
+    }
     }
 
     if (!featuresOut.empty()) {   // the guide images, rows top to bottom like SavePFM
@@ -422,7 +450,7 @@ int main(int argc, char **argv)
             px.resize((size_t)resX * resY * (bmp ? 3 : 4));
             if (denoised) {
                 if (vcm_read_denoised_image(r[0], bmp ? VCM_IMAGE_BGR8 : VCM_IMAGE_RGBE, 2.2f, px.data())) return die("vcm_read_denoised_image");
-            } else if (renderers == 1 && !r.empty()) {   // encoded on the device
+            } else if (renderers == 1 && !r.empty() && !robust) {   // encoded on the device
                 if (vcm_read_image(r[0], bmp ? VCM_IMAGE_BGR8 : VCM_IMAGE_RGBE, 1.f / vcm_iterations(r[0]), 2.2f, px.data()))
                     return die("vcm_read_image");
             } else if (bmp) {       // Framebuffer::SaveBMP, framebuffer.hxx:194-214
@@ -483,6 +511,10 @@ int main(int argc, char **argv)
     for (size_t i = 0; i < n3; i++) mean[i % 3] += fb[i];
     const double paths = (algorithm == VCM_ALGO_PATH_TRACE || algorithm == VCM_ALGO_EYE_LIGHT ? 1.0 : 2.0) * resX * resY * iterations;
     if (json) {
+        char robustJson[320] = "";
+        if (robust) snprintf(robustJson, sizeof(robustJson), ", \"robust\": {\"iterations\": %d, \"buckets\": %d, \"pixels\": %lld, \"trimmed\": %lld, "
+                             "\"nonFinite\": %lld, \"meanGini\": %.17g, \"maxGini\": %.17g}", rs.iterations, rs.buckets, rs.pixels, rs.trimmed, rs.nonFinite,
+                             rs.meanGini, rs.maxGini);
         std::string ms = "[";
         for (size_t i = 0; i < rankMs.size(); i++) { char b[32]; snprintf(b, sizeof(b), "%s%.3f", i ? ", " : "", rankMs[i]); ms += b; }
         ms += "]";
@@ -491,12 +523,12 @@ int main(int argc, char **argv)
                "\"last_iteration_ms\": %.3f, \"rank_iteration_ms\": %s, \"library\": \"%s\", "
                "\"last_iteration_kernel_ms\": {\"light\": %.3f, \"camera\": %.3f, \"connect_di\": %.3f, \"merge\": %.3f, \"grid_side\": %.3f, \"light_phase\": %.3f, \"camera_phase\": %.3f}, "
                "\"last_iteration_counters\": {\"lightVertices\": %lld, \"lightRays\": %lld, \"cameraRays\": %lld, \"shadowRays\": %lld, "
-               "\"mergeQueries\": %lld, \"mergeCandidates\": %lld, \"mergeAccepted\": %lld, \"connections\": %lld, \"lightSplats\": %lld}}\n",
+               "\"mergeQueries\": %lld, \"mergeCandidates\": %lld, \"mergeAccepted\": %lld, \"connections\": %lld, \"lightSplats\": %lld}%s}\n",
                sceneID, algoName.c_str(), resX, resY, iterations, renderers, seed, gpus > 0 ? gpus : 1, rcclRanks, wall, paths / wall / 1e6,
                mean[0] / (n3 / 3), mean[1] / (n3 / 3), mean[2] / (n3 / 3), st.msTotal, ms.c_str(), vcm_build_tag(),
                st.msLightKernel, st.msCameraKernel, st.msConnectKernels, st.msMergeKernel, st.msGrid, st.msLight, st.msCamera,
                st.lightVertices, st.lightRays, st.cameraRays, st.shadowRays, st.mergeQueries, st.mergeCandidates, st.mergeAccepted,
-               st.connections, st.lightSplats);
+               st.connections, st.lightSplats, robustJson);
     }
     else
         printf("scene %d, %s, %dx%d, %d iteration(s) on %d renderer(s): %.3f s wall clock, %.2f Mpaths/s\n", sceneID,

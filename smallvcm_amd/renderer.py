@@ -21,7 +21,7 @@ import os
 
 import numpy as np
 
-from ._abi import (DenoiseParams, DenoiseParams2, FEATURES, NoiseStats, SceneDesc, SceneDesc2, SceneDesc3, SceneDesc4, SceneDesc5, Stats, SCENE_CONFIGS, VCM_MERGE_RECORD_FLOATS, ALGO_LIGHT_TRACE, ALGO_PPM, ALGO_BPM,
+from ._abi import (DenoiseParams, DenoiseParams2, FEATURES, NoiseStats, ROBUST_DEFAULT_BUCKETS, RobustStats, SceneDesc, SceneDesc2, SceneDesc3, SceneDesc4, SceneDesc5, Stats, SCENE_CONFIGS, VCM_MERGE_RECORD_FLOATS, ALGO_LIGHT_TRACE, ALGO_PPM, ALGO_BPM,
                    ALGO_BPT, ALGO_VCM)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -130,6 +130,14 @@ def load_library(require_gpu=True):
         L.vcm_noise_stats_buffers.argtypes = [C.c_int, C.c_longlong, vp, vp, C.c_int, C.c_float, C.POINTER(NoiseStats), vp]
         L.vcm_debug_variance_max_blocks.argtypes = [C.c_int]
         L.vcm_debug_variance_max_blocks.restype = None
+        L.vcm_track_robust.argtypes = [vp, C.c_int]
+        L.vcm_robust_resolve.argtypes = [vp]
+        L.vcm_read_robust.argtypes = [vp, fp]
+        L.vcm_robust_device.argtypes = [vp, C.POINTER(vp)]
+        L.vcm_get_robust_stats.argtypes = [vp, C.POINTER(RobustStats)]
+        L.vcm_robust_update_buffers.argtypes = [C.c_int, C.c_longlong, vp, C.c_int, C.c_int, vp, vp, vp]
+        L.vcm_robust_resolve_buffers.argtypes = [C.c_int, C.c_longlong, vp, vp, C.c_int, C.c_int, vp, vp]
+        L.vcm_robust_stats_buffers.argtypes = [C.c_int, C.c_longlong, vp, vp, C.c_int, C.c_int, C.POINTER(RobustStats), vp]
         L.vcm_denoise_defaults2.argtypes = [C.POINTER(DenoiseParams2)]
         L.vcm_denoise_defaults2.restype = None
         L.vcm_denoise2.argtypes = [vp, C.c_float, C.POINTER(DenoiseParams2)]
@@ -250,6 +258,59 @@ def noise_stats_tensors(prev, mom, k, threshold=float("inf")):
     st = NoiseStats()
     _check(L, L.vcm_noise_stats_buffers(dev, n, prev.data_ptr(), mom.data_ptr(), int(k), threshold, C.byref(st), stream),
            "vcm_noise_stats_buffers")
+    return st.asdict()
+
+
+def _robust_tensors(who, prev, buckets):
+    import torch
+    for t in (prev, buckets):
+        if t.dtype != torch.float32 or not t.is_cuda or not t.is_contiguous() or t.dim() < 2 or t.shape[-1] != 4:
+            raise ValueError("%s wants prev and buckets as contiguous float32 GPU tensors [..., 4] and [M, ..., 4]" % who)
+    if buckets.shape[1:] != prev.shape or buckets.device != prev.device:
+        raise ValueError("%s wants buckets as [M] + prev's shape on prev's device" % who)
+    dev = prev.device.index if prev.device.index is not None else torch.cuda.current_device()
+    return prev.numel() // 4, int(buckets.shape[0]), dev, torch.cuda.current_stream(dev).cuda_stream
+
+
+def robust_update_tensors(sum3, k, prev, buckets):
+    """vcm_robust_update_buffers over torch tensors: iteration k (1, 2, ...) adds its frame sum3 - prev to plane
+    (k - 1) mod M of buckets ([M, ..., 4] float32) and sets prev ([..., 4]) = {sum3, 0}; both zero before k = 1, sum3
+    ([..., 3] float32) the running sum of the same pixels; in place, asynchronous on torch's current stream of that device.
+    Returns (prev, buckets)."""
+    import torch
+    n, M, dev, stream = _robust_tensors("robust_update_tensors", prev, buckets)
+    if sum3.dtype != torch.float32 or not sum3.is_cuda or not sum3.is_contiguous() or sum3.shape[-1] != 3 or sum3.numel() != 3 * n \
+            or sum3.device != prev.device:
+        raise ValueError("robust_update_tensors wants sum3 as a contiguous float32 GPU tensor [..., 3] of the same pixels")
+    L = load_library()
+    _check(L, L.vcm_robust_update_buffers(dev, n, sum3.data_ptr(), int(k), M, prev.data_ptr(), buckets.data_ptr(), stream),
+           "vcm_robust_update_buffers")
+    return prev, buckets
+
+
+def robust_resolve_tensors(prev, buckets, k, out=None):
+    """vcm_robust_resolve_buffers over the tensors of robust_update_tensors after k >= M iterations -> the estimate
+    {rgb, 1}, a tensor of prev's shape (`out`, or a new one); asynchronous on torch's current stream of that device"""
+    import torch
+    n, M, dev, stream = _robust_tensors("robust_resolve_tensors", prev, buckets)
+    if out is None:
+        out = torch.empty_like(prev)
+    elif out.dtype != torch.float32 or not out.is_contiguous() or out.shape != prev.shape or out.device != prev.device:
+        raise ValueError("robust_resolve_tensors wants out like prev")
+    L = load_library()
+    _check(L, L.vcm_robust_resolve_buffers(dev, n, prev.data_ptr(), buckets.data_ptr(), int(k), M, out.data_ptr(), stream),
+           "vcm_robust_resolve_buffers")
+    return out
+
+
+def robust_stats_tensors(prev, buckets, k):
+    """vcm_robust_stats_buffers over the tensors of robust_update_tensors after k >= M iterations -> the dict of
+    vcm_robust_stats; synchronises torch's current stream of that device"""
+    n, M, dev, stream = _robust_tensors("robust_stats_tensors", prev, buckets)
+    L = load_library()
+    st = RobustStats()
+    _check(L, L.vcm_robust_stats_buffers(dev, n, prev.data_ptr(), buckets.data_ptr(), int(k), M, C.byref(st), stream),
+           "vcm_robust_stats_buffers")
     return st.asdict()
 
 
@@ -504,6 +565,24 @@ class HipBackend:
         _check(self.L, self.L.vcm_get_noise_stats(self.ctx, threshold, C.byref(st)), "vcm_get_noise_stats")
         return st.asdict()
 
+    # ---- the firefly-robust estimate ------------------------------------------
+    def track_robust(self, buckets=ROBUST_DEFAULT_BUCKETS):
+        """accumulate the iterations in `buckets` (odd, 3 .. 15; 0 = off) partial framebuffers beside the framebuffer from the
+        next iteration on (before the first iteration, or right after clear_framebuffer); (buckets + 2) * 16 bytes per pixel"""
+        _check(self.L, self.L.vcm_track_robust(self.ctx, int(buckets)), "vcm_track_robust")
+
+    def robust(self):
+        """the median-of-means estimate of the image (not of the sum), [H, W, 3]; needs as many tracked iterations as buckets"""
+        out = np.zeros((self.resy, self.resx, 3), np.float32)
+        _check(self.L, self.L.vcm_read_robust(self.ctx, out.ctypes.data_as(C.POINTER(C.c_float))), "vcm_read_robust")
+        return out
+
+    def robust_stats(self):
+        """vcm_get_robust_stats: {iterations, buckets, pixels, trimmed, nonFinite, meanGini, maxGini}"""
+        st = RobustStats()
+        _check(self.L, self.L.vcm_get_robust_stats(self.ctx, C.byref(st)), "vcm_get_robust_stats")
+        return st.asdict()
+
     def stats_at(self, ago):
         """counters and phase times of the iteration `ago` iterations before the last completed one (<= 63)"""
         st = Stats()
@@ -566,6 +645,11 @@ class VertexCM:
         if self.mIterations > 0:
             fb = fb * np.float32(1.0 / self.mIterations)
         return fb
+
+    def GetRobust(self):
+        """GetFramebuffer() by the firefly-robust estimate (the reference has no such call): wants backend.track_robust()
+        before the first iteration and as many iterations as buckets"""
+        return self.backend.robust()
 
     def GetDenoised(self, **params):
         """GetFramebuffer() through the edge-avoiding denoiser (the reference has no such call); params: see
