@@ -68,7 +68,7 @@ enum {
 int vcm_debug_kat(vcm_ctx *ctx, int op, int n, const float *in, float *out);
 
 /* Which code path a context takes, for tests that must assert it rather than infer it: out = VCM_INFO_COUNT ints.
- * The kind flags are the ones the launches read -- rects / quads: the SceneRects(E) / SceneQuads kernels (both 0 on a
+ * The kind flags are read off the one kind the context's launches use (csrc/scene_kind.h) -- rects / quads: the SceneRects(E) / SceneQuads kernels (both 0 on a
  * list: SceneList(E)); nodes: a BVH (SceneBvh / SceneBvhG / SceneBvhE); intPhong 0: the general-pow kinds; envMap, lens,
  * pick: the E kinds, WithLens, WithPick -- then the table sizes the LDS-or-global branches compare, and the merge kernel
  * the LAST iteration launched (VCM_MERGE_WALK or VCM_MERGE_PAIRS after the fall-back above VCM_PAIR_MATERIALS; 0: it
@@ -79,6 +79,11 @@ enum {
     VCM_INFO_COUNT = 11
 };
 int vcm_debug_context_info(vcm_ctx *ctx, int *out);
+
+/* The rule that picks a context's kind from the five facts about its scene (csrc/scene_kind.h, scene_kind_of), for a
+ * test of the rule itself: 0 SceneList, 1 SceneQuads, 2 SceneRects, 3 SceneBvh, 4 SceneBvhG, 5 SceneRectsE, 6 SceneListE,
+ * 7 SceneBvhE.  A pure host function: it touches no device. */
+int vcm_debug_scene_kind(int envMap, int bvh, int intPhong, int rects, int quads);
 
 /* The two images of a context with vcm_track_variance on, as they stand after the last iteration: W*H float4 each,
  * prev = { S_{k-1}.rgb, 0 } and mom = { M2.rgb, 0 } (either may be NULL).  Synchronises. */

@@ -1,0 +1,89 @@
+// scene_kind.h -- which instantiation of a ray-casting kernel a context launches, stated once.
+//
+// Kernels that cast rays exist once per kind of scene (vcm_core.h: SceneList ... SceneBvhE).  The kind follows from five
+// facts about the scene (scene_kind_of); a context computes it once, when its scene is uploaded, and every launch, the
+// feature kernel of the denoiser and vcm_debug_context_info read that value.  with_scene_kind turns it back into a type
+// and adds the wrappers a kernel has instantiations for: WithLens (the kernels that hold the camera vertex, for a scene
+// with a thin lens) and WithPick (the kernels that choose a light or weigh an emitter hit, for a scene with a light-pick
+// table), WithPick over WithLens where a kernel has both.
+#ifndef SMALLVCM_AMD_SCENE_KIND_H
+#define SMALLVCM_AMD_SCENE_KIND_H
+
+#include "vcm_core.h"
+
+namespace vcm {
+
+enum class SceneKind : int { List = 0, Quads, Rects, Bvh, BvhG, RectsE, ListE, BvhE };
+
+struct SceneFacts {
+    bool envMap;     /* the background is an environment map */
+    bool bvh;        /* the scene has BVH nodes */
+    bool intPhong;   /* every Phong exponent in use is an integer detmath.h's binary exponentiation takes */
+    bool rects;      /* the primitive list is one-plane triangle pairs, some of them axis-aligned rectangles */
+    bool quads;      /* the primitive list is one-plane triangle pairs */
+};
+
+/* The rule.  An environment map comes first (its kinds carry the general pow, except the rectangles'), then a BVH, then
+   the general pow, then rectangles before quads. */
+constexpr SceneKind scene_kind_of(SceneFacts f)
+{
+    if (f.envMap) return f.bvh ? SceneKind::BvhE : (f.intPhong && f.rects) ? SceneKind::RectsE : SceneKind::ListE;
+    if (f.bvh) return f.intPhong ? SceneKind::Bvh : SceneKind::BvhG;
+    if (!f.intPhong) return SceneKind::List;
+    if (f.rects) return SceneKind::Rects;
+    if (f.quads) return SceneKind::Quads;
+    return SceneKind::List;
+}
+
+/* { envMap, bvh, intPhong, rects, quads }: the rows of KIND_FLAGS in tests/capacity_lib.py ... */
+static_assert(scene_kind_of({ true, false, true, true, false }) == SceneKind::RectsE, "rects (with its environment map)");
+static_assert(scene_kind_of({ false, false, true, false, true }) == SceneKind::Quads, "quads");
+static_assert(scene_kind_of({ false, false, true, false, false }) == SceneKind::List, "list");
+static_assert(scene_kind_of({ false, true, true, false, false }) == SceneKind::Bvh, "bvh");
+static_assert(scene_kind_of({ false, true, false, false, false }) == SceneKind::BvhG, "bvhG");
+static_assert(scene_kind_of({ true, false, false, false, false }) == SceneKind::ListE, "listE");
+static_assert(scene_kind_of({ true, true, false, false, false }) == SceneKind::BvhE, "bvhE");
+/* ... and the two precedence cases: quads without rectangles have no E kind of their own, a BVH under an environment
+   map has one kind whatever the exponents */
+static_assert(scene_kind_of({ true, false, true, false, true }) == SceneKind::ListE, "env map + quads");
+static_assert(scene_kind_of({ true, true, true, false, false }) == SceneKind::BvhE, "env map + BVH + integer exponents");
+
+constexpr bool scene_kind_is_bvh(SceneKind k) { return k == SceneKind::Bvh || k == SceneKind::BvhG || k == SceneKind::BvhE; }
+constexpr bool scene_kind_is_rects(SceneKind k) { return k == SceneKind::Rects || k == SceneKind::RectsE; }
+
+/* what with_scene_kind hands its callable: `typename decltype(tag)::type` is the kernel's scene argument */
+template <class S> struct SceneTag { using type = S; };
+
+/* the wrappers a kernel is instantiated for */
+enum : unsigned { kWrapNone = 0, kWrapLens = 1, kWrapPick = 2 };
+
+template <unsigned Wrap, class S, class F> void with_wrappers(bool lens, bool pick, F &f)
+{
+    if constexpr (Wrap & kWrapLens) {
+        if (lens) with_wrappers<Wrap & ~kWrapLens, WithLens<S>>(lens, pick, f);
+        else with_wrappers<Wrap & ~kWrapLens, S>(lens, pick, f);
+    } else if constexpr (Wrap & kWrapPick) {
+        if (pick) f(SceneTag<WithPick<S>>{});
+        else f(SceneTag<S>{});
+    } else f(SceneTag<S>{});
+}
+
+/* Calls f once, with the tag of the instantiation a scene of `kind` takes.  Only the wrappers named in Wrap are ever
+   applied, so f is instantiated for exactly the types the kernel exists for. */
+template <unsigned Wrap, class F> void with_scene_kind(SceneKind kind, bool lens, bool pick, F &&f)
+{
+    switch (kind) {
+    case SceneKind::List:   return with_wrappers<Wrap, SceneList>(lens, pick, f);
+    case SceneKind::Quads:  return with_wrappers<Wrap, SceneQuads>(lens, pick, f);
+    case SceneKind::Rects:  return with_wrappers<Wrap, SceneRects>(lens, pick, f);
+    case SceneKind::Bvh:    return with_wrappers<Wrap, SceneBvh>(lens, pick, f);
+    case SceneKind::BvhG:   return with_wrappers<Wrap, SceneBvhG>(lens, pick, f);
+    case SceneKind::RectsE: return with_wrappers<Wrap, SceneRectsE>(lens, pick, f);
+    case SceneKind::ListE:  return with_wrappers<Wrap, SceneListE>(lens, pick, f);
+    case SceneKind::BvhE:   return with_wrappers<Wrap, SceneBvhE>(lens, pick, f);
+    }
+}
+
+} // namespace vcm
+
+#endif

@@ -19,6 +19,7 @@
 #include "vcm_kernels.h"
 #include "vcm_kat.h"
 #include "scene_host.h"
+#include "scene_kind.h"
 #include "vcm_denoise.h"
 #include "vcm_variance.h"
 #include "vcm_robust.h"
@@ -117,49 +118,6 @@ static std::atomic<unsigned long long> g_threadCounter{0};
 static thread_local unsigned long long g_threadId = 0;
 static unsigned long long this_thread_id() { if (!g_threadId) g_threadId = ++g_threadCounter; return g_threadId; }
 
-/* Kernels that cast rays exist once per kind of scene (vcm_core.h SceneList / SceneBvh); the launch picks.  A scene with
-   an environment map takes the kinds that carry its branch (SceneRectsE / SceneListE / SceneBvhE).  W wraps the kind:
-   Pinhole is the kind itself, WithLens (vcm_core.h) the thin-lens instantiation of the kernels that hold the camera
-   vertex, which LAUNCH_SC_CAM / LAUNCH_SC_MODE_CAM pick for a scene with a lens. */
-template <class S> using Pinhole = S;
-#define LAUNCH_SC_W(c, W, K, ...) do { if ((c)->envMap) { if (!(c)->scene->nodes.empty()) hipLaunchKernelGGL((K<W<SceneBvhE>>), __VA_ARGS__); \
-                                                     else if ((c)->intPhong && (c)->sceneRects) hipLaunchKernelGGL((K<W<SceneRectsE>>), __VA_ARGS__); \
-                                                     else hipLaunchKernelGGL((K<W<SceneListE>>), __VA_ARGS__); } \
-                                  else if (!(c)->scene->nodes.empty()) { if ((c)->intPhong) hipLaunchKernelGGL((K<W<SceneBvh>>), __VA_ARGS__); \
-                                                                     else hipLaunchKernelGGL((K<W<SceneBvhG>>), __VA_ARGS__); } \
-                                  else if (!(c)->intPhong) hipLaunchKernelGGL((K<W<SceneList>>), __VA_ARGS__); \
-                                  else if ((c)->sceneRects) hipLaunchKernelGGL((K<W<SceneRects>>), __VA_ARGS__); \
-                                  else if ((c)->sceneQuads) hipLaunchKernelGGL((K<W<SceneQuads>>), __VA_ARGS__); \
-                                  else hipLaunchKernelGGL((K<W<SceneList>>), __VA_ARGS__); } while (0)
-#define LAUNCH_SC_MODE_W(c, W, K, M, ...) do { if ((c)->envMap) { if (!(c)->scene->nodes.empty()) hipLaunchKernelGGL((K<M, W<SceneBvhE>>), __VA_ARGS__); \
-                                                             else if ((c)->intPhong && (c)->sceneRects) hipLaunchKernelGGL((K<M, W<SceneRectsE>>), __VA_ARGS__); \
-                                                             else hipLaunchKernelGGL((K<M, W<SceneListE>>), __VA_ARGS__); } \
-                                          else if (!(c)->scene->nodes.empty()) { if ((c)->intPhong) hipLaunchKernelGGL((K<M, W<SceneBvh>>), __VA_ARGS__); \
-                                                                             else hipLaunchKernelGGL((K<M, W<SceneBvhG>>), __VA_ARGS__); } \
-                                          else if (!(c)->intPhong) hipLaunchKernelGGL((K<M, W<SceneList>>), __VA_ARGS__); \
-                                          else if ((c)->sceneRects) hipLaunchKernelGGL((K<M, W<SceneRects>>), __VA_ARGS__); \
-                                          else if ((c)->sceneQuads) hipLaunchKernelGGL((K<M, W<SceneQuads>>), __VA_ARGS__); \
-                                          else hipLaunchKernelGGL((K<M, W<SceneList>>), __VA_ARGS__); } while (0)
-#define LAUNCH_SC(c, K, ...) LAUNCH_SC_W(c, Pinhole, K, __VA_ARGS__)
-#define LAUNCH_SC_MODE(c, K, M, ...) LAUNCH_SC_MODE_W(c, Pinhole, K, M, __VA_ARGS__)
-#define LAUNCH_SC_CAM(c, K, ...) do { if ((c)->lens) LAUNCH_SC_W(c, WithLens, K, __VA_ARGS__); \
-                                      else LAUNCH_SC_W(c, Pinhole, K, __VA_ARGS__); } while (0)
-#define LAUNCH_SC_MODE_CAM(c, K, M, ...) do { if ((c)->lens) LAUNCH_SC_MODE_W(c, WithLens, K, M, __VA_ARGS__); \
-                                              else LAUNCH_SC_MODE_W(c, Pinhole, K, M, __VA_ARGS__); } while (0)
-/* The kernels that choose a light or weigh an emitter hit: a scene with a light-pick table (vcm_scene_desc5) takes their
-   WithPick instantiations (vcm_core.h), over the lens kinds where the kernel also holds the camera vertex. */
-template <class S> using PickLens = WithPick<WithLens<S>>;
-#define LAUNCH_SC_PICK(c, K, ...) do { if ((c)->pick) LAUNCH_SC_W(c, WithPick, K, __VA_ARGS__); \
-                                       else LAUNCH_SC_W(c, Pinhole, K, __VA_ARGS__); } while (0)
-#define LAUNCH_SC_MODE_PICK(c, K, M, ...) do { if ((c)->pick) LAUNCH_SC_MODE_W(c, WithPick, K, M, __VA_ARGS__); \
-                                               else LAUNCH_SC_MODE_W(c, Pinhole, K, M, __VA_ARGS__); } while (0)
-#define LAUNCH_SC_CAM_PICK(c, K, ...) do { if (!(c)->pick) LAUNCH_SC_CAM(c, K, __VA_ARGS__); \
-                                           else if ((c)->lens) LAUNCH_SC_W(c, PickLens, K, __VA_ARGS__); \
-                                           else LAUNCH_SC_W(c, WithPick, K, __VA_ARGS__); } while (0)
-#define LAUNCH_SC_MODE_CAM_PICK(c, K, M, ...) do { if (!(c)->pick) LAUNCH_SC_MODE_CAM(c, K, M, __VA_ARGS__); \
-                                                   else if ((c)->lens) LAUNCH_SC_MODE_W(c, PickLens, K, M, __VA_ARGS__); \
-                                                   else LAUNCH_SC_MODE_W(c, WithPick, K, M, __VA_ARGS__); } while (0)
-
 #ifndef VCM_MERGE_DEFAULT
 #define VCM_MERGE_DEFAULT VCM_MERGE_PAIRS
 #endif
@@ -219,11 +177,10 @@ struct vcm_ctx : Scratch {
     bool strictOrder;
     int mergeKind;                    /* VCM_MERGE_* */
     int lastMergeKernel;              /* the VCM_MERGE_* kernel the last iteration launched, 0 if it merged nothing (vcm_debug_context_info) */
-    bool sceneQuads;                  /* every triangle pair of the list shares its plane part: the SceneQuads kernels */
-    bool sceneRects;                  /* ... and is an axis-aligned rectangle: the SceneRects kernels */
+    SceneKind kind;                   /* the instantiation the ray-casting kernels are launched in (scene_kind.h); set by ensure_device */
     bool envMap;                      /* the scene's background is an environment map: the SceneRectsE / SceneListE / SceneBvhE kernels */
-    bool lens;                        /* the camera is a thin lens: the WithLens kernels for the camera vertex (LAUNCH_SC_CAM) */
-    bool pick;                        /* lights are chosen from a table: the WithPick kernels (LAUNCH_SC_PICK ...) */
+    bool lens;                        /* the camera is a thin lens: the WithLens kernels for the camera vertex */
+    bool pick;                        /* lights are chosen from a table: the WithPick kernels */
     bool intPhong;                    /* every Phong exponent in use is an integer in [1, 65536]: the kernels whose pow is the binary
                                          exponentiation alone (detmath.h); otherwise the SceneList / SceneBvhG kernels and the general merge */
     /* feature buffers and denoiser (vcm_denoise.h): allocated by the first vcm_render_features / vcm_denoise */
@@ -245,6 +202,18 @@ struct vcm_ctx : Scratch {
     unsigned long long *pend[2][4]; int nPend[2];   /* stamp slots waiting for the next kernel on [0] main, [1] side stream */
     vcm_stats lastStats;
 };
+
+/* A ray-casting kernel is launched in the instantiation of the context's kind, under the wrappers it exists for (Wrap:
+   scene_kind.h): f(tag) launches it with S = typename decltype(tag)::type.  What f evaluates, it evaluates once. */
+template <unsigned Wrap, class F> static void launch_kind(const vcm_ctx *c, F &&f) { with_scene_kind<Wrap>(c->kind, c->lens, c->pick, f); }
+
+/* K4 of a context: k_merge_pairs or k_merge_walk (VCM_MERGE_*), with the pow its exponents allow */
+typedef void (*MergeKernel)(const DScene *, IterParams, GridStore, VertexStore, const int *, const int *, unsigned long long *, int, StampArgs);
+static MergeKernel merge_kernel(int mergeKind, bool intPhong)
+{
+    if (mergeKind == VCM_MERGE_PAIRS) return intPhong ? k_merge_pairs<true> : k_merge_pairs<false>;
+    return intPhong ? k_merge_walk<true> : k_merge_walk<false>;
+}
 
 static int use_device(vcm_ctx *c) { HIPCHK(hipSetDevice(c->device)); return 0; }
 
@@ -529,12 +498,15 @@ static int ensure_device(vcm_ctx *c)
                 if (p.bytes) HIPCHK(hipMemcpy(c->dSceneBlob + p.off, p.src, p.bytes, hipMemcpyHostToDevice));
             DScene view;
             h.fill_scalars(view);
-            c->sceneQuads = h.nodes.empty() && view.fastOnePlane != 0;
-            c->sceneRects = c->sceneQuads && (view.nFastRects[0] + view.nFastRects[1] + view.nFastRects[2]) > 0;
             c->intPhong = true;
             for (const vcm_material &m : h.materials)
                 if ((m.phong[0] != 0.f || m.phong[1] != 0.f || m.phong[2] != 0.f) && !dm_pow_is_int_case(m.phongExp)) c->intPhong = false;
             { const char *e = getenv("SMALLVCM_AMD_GENERAL_POW"); if (e && e[0] == '1') c->intPhong = false; }   /* tests: the general kernels on the reference's scenes */
+            {   /* every triangle pair of the list shares its plane part (SceneQuads), some are axis-aligned rectangles (SceneRects) */
+                const bool quads = h.nodes.empty() && view.fastOnePlane != 0;
+                const bool rects = quads && (view.nFastRects[0] + view.nFastRects[1] + view.nFastRects[2]) > 0;
+                c->kind = scene_kind_of({ c->envMap, !h.nodes.empty(), c->intPhong, rects, quads });
+            }
             view.offPrims = (long long)parts[0].off; view.offMaterials = (long long)parts[1].off;
             view.offMat2light = (long long)parts[2].off; view.offLights = (long long)parts[3].off;
             view.offOps = (long long)parts[4].off; view.offPairs = (long long)parts[5].off;
@@ -1243,9 +1215,12 @@ static int flush_light_splats(vcm_ctx *c)
         F4 *list = c->dSplatList;
         if (c->prezeroed) HIPCHK(hipStreamWaitEvent(q, c->evZero, 0));
         else if (zero_ranges(q, pixCount, ((size_t)c->N + 1) * sizeof(int))) return -1;
-        LAUNCH_SC_CAM(c, k_connect_camera, dim3(task_blocks(c->nLocal)), dim3(256), 0, q, c->dScene, c->P, c->store,
-                           (const int *)c->dSlotOfVertex, (const int *)c->dLocalTotal, c->dFb, c->dSplat, pixCount,
-                           arrival, c->dStats);
+        launch_kind<kWrapLens>(c, [&](auto tag) {
+            using S = typename decltype(tag)::type;
+            hipLaunchKernelGGL((k_connect_camera<S>), dim3(task_blocks(c->nLocal)), dim3(256), 0, q, c->dScene, c->P, c->store,
+                               (const int *)c->dSlotOfVertex, (const int *)c->dLocalTotal, c->dFb, c->dSplat, pixCount,
+                               arrival, c->dStats);
+        });
         if (launch_scan_on<int>(c, overlap ? 2 : 0, q, pixCount, c->N, pixStart, NULL, 1, overlap ? none : take_stamps(c, q))) return -1;
         hipLaunchKernelGGL(k_splat_scatter, dim3(aux_blocks(c->nLocal)), dim3(256), 0, q, (const F4 *)c->dSplat,
                            (const int *)c->dLocalTotal, (const int *)pixStart, (const int *)arrival, list, pixCount);
@@ -1299,11 +1274,17 @@ static int vcm_trace_light_impl(vcm_ctx *c)
     const bool wf = !c->strictOrder;
     if (!wf && join_splats(c)) return -1;   /* the fused K1 splats straight into dFb: behind a K5 the last (aside) iteration left in flight */
     if (wf)
-        LAUNCH_SC_MODE_PICK(c, k_light_trace, 1, dim3(blocks), dim3(VCM_TRACE_BLOCK), 0, c->stream, c->dScene, c->P, c->store,
-                           c->dFb, c->dRngLight, c->dStats, chunk, take_stamps(c, c->stream), c->vs.count + 16, c->dHdr);
+        launch_kind<kWrapPick>(c, [&](auto tag) {
+            using S = typename decltype(tag)::type;
+            hipLaunchKernelGGL((k_light_trace<1, S>), dim3(blocks), dim3(VCM_TRACE_BLOCK), 0, c->stream, c->dScene, c->P, c->store,
+                               c->dFb, c->dRngLight, c->dStats, chunk, take_stamps(c, c->stream), c->vs.count + 16, c->dHdr);
+        });
     else
-        LAUNCH_SC_MODE_CAM_PICK(c, k_light_trace, 0, dim3(blocks), dim3(VCM_TRACE_BLOCK), 0, c->stream, c->dScene, c->P, c->store,
-                           c->dFb, c->dRngLight, c->dStats, chunk, take_stamps(c, c->stream), c->vs.count + 16, c->dHdr);
+        launch_kind<kWrapLens | kWrapPick>(c, [&](auto tag) {
+            using S = typename decltype(tag)::type;
+            hipLaunchKernelGGL((k_light_trace<0, S>), dim3(blocks), dim3(VCM_TRACE_BLOCK), 0, c->stream, c->dScene, c->P, c->store,
+                               c->dFb, c->dRngLight, c->dStats, chunk, take_stamps(c, c->stream), c->vs.count + 16, c->dHdr);
+        });
     HIPCHK(hipGetLastError());
     c->bboxFromLight = c->world == 1;   /* K1 keeps the box of what it stores (k_bbox, a pass of its own over the vertices, serves imported records) */
     if (mark(c, EV_LIGHT_K1)) return -1;
@@ -1699,11 +1680,17 @@ static int vcm_trace_camera_impl(vcm_ctx *c)
     if (mark(c, EV_CAMERA_K0)) return -1;
     if (c->renderer) {   /* PathTracer / EyeLight: colour + jittered pixel per path; K5 adds them in path order */
         if (c->renderer == 1)
-            LAUNCH_SC_CAM_PICK(c, k_path_trace, dim3(blocks), dim3(VCM_TRACE_BLOCK), 0, c->stream, c->dScene, c->P, c->dCamOut,
-                               c->dRngCam, c->dStats, chunk, take_stamps(c, c->stream), c->vs.count + 8);
+            launch_kind<kWrapLens | kWrapPick>(c, [&](auto tag) {
+                using S = typename decltype(tag)::type;
+                hipLaunchKernelGGL((k_path_trace<S>), dim3(blocks), dim3(VCM_TRACE_BLOCK), 0, c->stream, c->dScene, c->P, c->dCamOut,
+                                   c->dRngCam, c->dStats, chunk, take_stamps(c, c->stream), c->vs.count + 8);
+            });
         else
-            LAUNCH_SC_CAM(c, k_eye_light, dim3(2048), dim3(256), 0, c->stream, c->dScene, c->P, c->dCamOut, c->dRngCam,
-                               c->dStats, take_stamps(c, c->stream));
+            launch_kind<kWrapLens>(c, [&](auto tag) {
+                using S = typename decltype(tag)::type;
+                hipLaunchKernelGGL((k_eye_light<S>), dim3(2048), dim3(256), 0, c->stream, c->dScene, c->P, c->dCamOut, c->dRngCam,
+                                   c->dStats, take_stamps(c, c->stream));
+            });
         HIPCHK(hipGetLastError());
         if (mark(c, EV_CAMERA_K1)) return -1;
         if (mark(c, EV_CONNECT_K1)) return -1;
@@ -1721,8 +1708,11 @@ static int vcm_trace_camera_impl(vcm_ctx *c)
             if (c->prezeroed) HIPCHK(hipStreamWaitEvent(c->stream, c->evZero, 0));
             else if (zero_ranges(c->stream, c->dQueryCount, ((size_t)c->P.nBuckets + 1) * sizeof(int))) return -1;
         }
-        LAUNCH_SC_MODE_CAM_PICK(c, k_camera_trace, 1, dim3(blocks), dim3(VCM_TRACE_BLOCK), 0, c->stream, c->dScene, c->P,
-                           c->store, grid_of(c), c->vs, c->dCamOut, c->dCamMask, c->dRngCam, c->dStats, chunk, take_stamps(c, c->stream));
+        launch_kind<kWrapLens | kWrapPick>(c, [&](auto tag) {
+            using S = typename decltype(tag)::type;
+            hipLaunchKernelGGL((k_camera_trace<1, S>), dim3(blocks), dim3(VCM_TRACE_BLOCK), 0, c->stream, c->dScene, c->P,
+                               c->store, grid_of(c), c->vs, c->dCamOut, c->dCamMask, c->dRngCam, c->dStats, chunk, take_stamps(c, c->stream));
+        });
         if (mark(c, EV_CAMERA_K1)) return -1;
         if (c->useVC) {   /* K3b, K3c: dense DI / VC tasks */
             /* K3c reads what K3 appended and the light store, and only K5 reads what it writes: it runs on the splat
@@ -1767,20 +1757,29 @@ static int vcm_trace_camera_impl(vcm_ctx *c)
                    critical path (profiles/archive/r07f_timeline1024.txt) */
                 HIPCHK(hipEventRecord(c->evSplatFork, c->stream));
                 HIPCHK(hipStreamWaitEvent(c->splat, c->evSplatFork, 0));
-                LAUNCH_SC(c, k_connect_vc, dim3(task_blocks(c->nLocal)), dim3(VCM_TASK_BLOCK), 0, c->splat, c->dScene, c->P, c->vs,
-                                   c->store, c->dStats);
+                launch_kind<kWrapNone>(c, [&](auto tag) {
+                    using S = typename decltype(tag)::type;
+                    hipLaunchKernelGGL((k_connect_vc<S>), dim3(task_blocks(c->nLocal)), dim3(VCM_TASK_BLOCK), 0, c->splat, c->dScene, c->P, c->vs,
+                                       c->store, c->dStats);
+                });
                 HIPCHK(hipEventRecord(c->evSplatDone, c->splat));   /* also behind the light splats: same stream */
                 c->splatInFlight = true;
             }
-            LAUNCH_SC_PICK(c, k_connect_di, dim3(task_blocks(c->nLocal)), dim3(VCM_TASK_BLOCK), 0, c->stream, c->dScene, c->P, c->vs,
-                               c->dStats, c->scatteredInDI ? (const int *)c->dQueryStart : (const int *)NULL,
-                               c->scatteredInDI ? c->dSortedVertex : (int *)NULL, take_stamps(c, c->stream));
+            launch_kind<kWrapPick>(c, [&](auto tag) {
+                using S = typename decltype(tag)::type;
+                hipLaunchKernelGGL((k_connect_di<S>), dim3(task_blocks(c->nLocal)), dim3(VCM_TASK_BLOCK), 0, c->stream, c->dScene, c->P, c->vs,
+                                   c->dStats, c->scatteredInDI ? (const int *)c->dQueryStart : (const int *)NULL,
+                                   c->scatteredInDI ? c->dSortedVertex : (int *)NULL, take_stamps(c, c->stream));
+            });
         }
         if (mark(c, EV_CONNECT_K1)) return -1;
     } else {
         if (c->useVM && !c->gridBuilt) return fail("vcm_trace_camera", "strict mode merges inside the camera pass: call vcm_build_grid first");
-        LAUNCH_SC_MODE_CAM_PICK(c, k_camera_trace, 0, dim3(blocks), dim3(VCM_TRACE_BLOCK), 0, c->stream, c->dScene, c->P,
-                           c->store, grid_of(c), c->vs, c->dCamOut, c->dCamMask, c->dRngCam, c->dStats, chunk, take_stamps(c, c->stream));
+        launch_kind<kWrapLens | kWrapPick>(c, [&](auto tag) {
+            using S = typename decltype(tag)::type;
+            hipLaunchKernelGGL((k_camera_trace<0, S>), dim3(blocks), dim3(VCM_TRACE_BLOCK), 0, c->stream, c->dScene, c->P,
+                               c->store, grid_of(c), c->vs, c->dCamOut, c->dCamMask, c->dRngCam, c->dStats, chunk, take_stamps(c, c->stream));
+        });
         if (mark(c, EV_CAMERA_K1)) return -1;
         if (mark(c, EV_CONNECT_K1)) return -1;
     }
@@ -1931,13 +1930,7 @@ static int vcm_space_merge_impl(vcm_ctx *c, const void *queriesDev, const long l
         if (kind == VCM_MERGE_PAIRS && (int)c->scene->materials.size() > VCM_PAIR_MATERIALS) kind = VCM_MERGE_WALK;
         c->lastMergeKernel = kind;
         const int chunk = shape_knob("merge_chunk") ? shape_knob("merge_chunk") : 16;
-        if (kind == VCM_MERGE_PAIRS) {
-            if (c->intPhong) hipLaunchKernelGGL(k_merge_pairs<true>, dim3(blocks), dim3(VCM_MERGE_BLOCK), 0, c->stream, c->dScene, P2, grid_of(c), fvs, (const int *)c->fSorted, (const int *)(c->dQueryStart + nb), c->dStats, chunk, none);
-            else hipLaunchKernelGGL(k_merge_pairs<false>, dim3(blocks), dim3(VCM_MERGE_BLOCK), 0, c->stream, c->dScene, P2, grid_of(c), fvs, (const int *)c->fSorted, (const int *)(c->dQueryStart + nb), c->dStats, chunk, none);
-        } else {
-            if (c->intPhong) hipLaunchKernelGGL(k_merge_walk<true>, dim3(blocks), dim3(VCM_MERGE_BLOCK), 0, c->stream, c->dScene, P2, grid_of(c), fvs, (const int *)c->fSorted, (const int *)(c->dQueryStart + nb), c->dStats, chunk, none);
-            else hipLaunchKernelGGL(k_merge_walk<false>, dim3(blocks), dim3(VCM_MERGE_BLOCK), 0, c->stream, c->dScene, P2, grid_of(c), fvs, (const int *)c->fSorted, (const int *)(c->dQueryStart + nb), c->dStats, chunk, none);
-        }
+        hipLaunchKernelGGL(merge_kernel(kind, c->intPhong), dim3(blocks), dim3(VCM_MERGE_BLOCK), 0, c->stream, c->dScene, P2, grid_of(c), fvs, (const int *)c->fSorted, (const int *)(c->dQueryStart + nb), c->dStats, chunk, none);
         HIPCHK(hipGetLastError());
     }
     at = 0;
@@ -2030,22 +2023,8 @@ static int vcm_merge_impl(vcm_ctx *c)
             /* k_merge_pairs keeps a material table of VCM_PAIR_MATERIALS rows in LDS */
             if (mergeStaged == VCM_MERGE_PAIRS && (int)c->scene->materials.size() > VCM_PAIR_MATERIALS) mergeStaged = VCM_MERGE_WALK;
             c->lastMergeKernel = mergeStaged;
-            if (mergeStaged == VCM_MERGE_PAIRS) {
-                if (c->intPhong)
-                    hipLaunchKernelGGL(k_merge_pairs<true>, dim3(merge_blocks(c->nLocal, c->N)), dim3(VCM_MERGE_BLOCK), 0, ks, c->dScene, c->P, grid_of(c),
-                                       c->vs, (const int *)c->dSortedVertex, (const int *)(c->dQueryStart + nb), c->dStats, mergeChunk, take_stamps(c, c->stream));
-                else
-                    hipLaunchKernelGGL(k_merge_pairs<false>, dim3(merge_blocks(c->nLocal, c->N)), dim3(VCM_MERGE_BLOCK), 0, ks, c->dScene, c->P, grid_of(c),
-                                       c->vs, (const int *)c->dSortedVertex, (const int *)(c->dQueryStart + nb), c->dStats, mergeChunk, take_stamps(c, c->stream));
-            }
-            else {
-                if (c->intPhong)
-                    hipLaunchKernelGGL(k_merge_walk<true>, dim3(merge_blocks(c->nLocal, c->N)), dim3(VCM_MERGE_BLOCK), 0, ks, c->dScene, c->P, grid_of(c),
-                                       c->vs, (const int *)c->dSortedVertex, (const int *)(c->dQueryStart + nb), c->dStats, mergeChunk, take_stamps(c, c->stream));
-                else
-                    hipLaunchKernelGGL(k_merge_walk<false>, dim3(merge_blocks(c->nLocal, c->N)), dim3(VCM_MERGE_BLOCK), 0, ks, c->dScene, c->P, grid_of(c),
-                                       c->vs, (const int *)c->dSortedVertex, (const int *)(c->dQueryStart + nb), c->dStats, mergeChunk, take_stamps(c, c->stream));
-            }
+            hipLaunchKernelGGL(merge_kernel(mergeStaged, c->intPhong), dim3(merge_blocks(c->nLocal, c->N)), dim3(VCM_MERGE_BLOCK), 0, ks, c->dScene, c->P, grid_of(c),
+                               c->vs, (const int *)c->dSortedVertex, (const int *)(c->dQueryStart + nb), c->dStats, mergeChunk, take_stamps(c, c->stream));
         } else {
             if (mark(c, EV_SORT_K1)) return -1;
         }
@@ -2306,8 +2285,7 @@ int vcm_render_features(vcm_ctx *c)
     g_hipFailed = false;
     if (ensure_device(c)) return -1;
     if (ensure_feature_buffers(c)) return -1;
-    const DnSceneKind kind = { c->envMap, !c->scene->nodes.empty(), c->intPhong, c->sceneRects, c->sceneQuads };
-    HIPCHK(dn_launch_features(c->dScene, kind, c->resX, c->p0, c->nLocal, c->dGuide, c->dAlbedo, c->stream));
+    HIPCHK(dn_launch_features(c->dScene, c->kind, c->resX, c->p0, c->nLocal, c->dGuide, c->dAlbedo, c->stream));
     c->featuresValid = true;
     return 0;
 }
@@ -2948,7 +2926,10 @@ int vcm_debug_kat(vcm_ctx *c, int op, int n, const float *in, float *out)
     HIPCHK(hipMalloc((void **)&din, bytes));
     HIPCHK(hipMalloc((void **)&dout, bytes));
     HIPCHK(hipMemcpy(din, in, bytes, hipMemcpyHostToDevice));
-    LAUNCH_SC_CAM_PICK(c, k_kat, dim3((n + 63) / 64), dim3(64), 0, 0, (const DScene *)c->dScene, op, n, (const float *)din, dout);
+    launch_kind<kWrapLens | kWrapPick>(c, [&](auto tag) {
+        using S = typename decltype(tag)::type;
+        hipLaunchKernelGGL((k_kat<S>), dim3((n + 63) / 64), dim3(64), 0, 0, (const DScene *)c->dScene, op, n, (const float *)din, dout);
+    });
     hipError_t e = hipGetLastError();
     if (e == hipSuccess) e = hipMemcpy(out, dout, bytes, hipMemcpyDeviceToHost);
     (void)hipFree(din); (void)hipFree(dout);
@@ -2959,12 +2940,11 @@ int vcm_debug_kat(vcm_ctx *c, int op, int n, const float *in, float *out)
 int vcm_debug_context_info(vcm_ctx *c, int *out)
 {
     if (!c || !out) return fail("vcm_debug_context_info", "bad argument");
-    if (ensure_device(c)) return -1;   /* the kind flags are decided when the scene is uploaded */
-    const bool nodes = !c->scene->nodes.empty();
-    /* the flags as LAUNCH_SC_W reads them: a BVH comes before the list kinds, the general pow before rects / quads */
-    out[VCM_INFO_RECTS] = !nodes && c->intPhong && c->sceneRects;
-    out[VCM_INFO_QUADS] = !nodes && !c->envMap && c->intPhong && !c->sceneRects && c->sceneQuads;
-    out[VCM_INFO_NODES] = nodes;
+    if (ensure_device(c)) return -1;   /* the kind is decided when the scene is uploaded */
+    /* read off the kind the launches use, not recomputed */
+    out[VCM_INFO_RECTS] = scene_kind_is_rects(c->kind);
+    out[VCM_INFO_QUADS] = c->kind == SceneKind::Quads;
+    out[VCM_INFO_NODES] = scene_kind_is_bvh(c->kind);
     out[VCM_INFO_INT_PHONG] = c->intPhong;
     out[VCM_INFO_ENVMAP] = c->envMap;
     out[VCM_INFO_LENS] = c->lens;
@@ -2974,6 +2954,11 @@ int vcm_debug_context_info(vcm_ctx *c, int *out)
     out[VCM_INFO_LIGHTS] = (int)c->scene->lights.size();
     out[VCM_INFO_MERGE_KERNEL] = c->lastMergeKernel;
     return 0;
+}
+
+int vcm_debug_scene_kind(int envMap, int bvh, int intPhong, int rects, int quads)
+{
+    return (int)scene_kind_of({ envMap != 0, bvh != 0, intPhong != 0, rects != 0, quads != 0 });
 }
 
 int vcm_debug_philox_spec(unsigned seed, unsigned iter, unsigned kind, int nPaths, int nFloats, float *out)

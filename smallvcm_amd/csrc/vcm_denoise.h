@@ -9,6 +9,7 @@
 #define SMALLVCM_AMD_VCM_DENOISE_H
 
 #include "vcm_core.h"
+#include "scene_kind.h"
 
 namespace vcm {
 
@@ -304,9 +305,8 @@ VCM_HD F4 dn_filter_pixel2(const DnPass2 &P2, int x, int y, F4 albedoP, Load &&l
 
 /* ---------------- launches (vcm_denoise.hip; the C-ABI of vcm_api.hip calls them) ---------------- */
 #if defined(__HIPCC__)
-struct DnSceneKind { bool envMap, bvh, intPhong, rects, quads; };
-/* guide / albedo of the pixels [p0, p0 + nLocal) */
-hipError_t dn_launch_features(const DScene *dScene, DnSceneKind kind, int resX, int p0, int nLocal, F4 *guide, F4 *albedo,
+/* guide / albedo of the pixels [p0, p0 + nLocal), by the k_features of the context's kind */
+hipError_t dn_launch_features(const DScene *dScene, SceneKind kind, int resX, int p0, int nLocal, F4 *guide, F4 *albedo,
                               hipStream_t stream);
 /* out = the filtered colour.  fb3 != NULL: the colour is a W*H*3 float image times `scale`, else the float4 image
    `color`.  tmpA, tmpB: two W*H float4 images of scratch (unused when passes == 0).  Parameters already checked. */

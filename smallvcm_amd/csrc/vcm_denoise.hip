@@ -158,20 +158,15 @@ k_atrous_var(DnPass2 P2, const F4 *__restrict__ color, const F4 *__restrict__ gu
 
 namespace vcm {
 
-hipError_t dn_launch_features(const DScene *dScene, DnSceneKind k, int resX, int p0, int nLocal, F4 *guide, F4 *albedo,
+hipError_t dn_launch_features(const DScene *dScene, SceneKind kind, int resX, int p0, int nLocal, F4 *guide, F4 *albedo,
                               hipStream_t stream)
 {
     int blocks = (nLocal + 255) / 256;
     blocks = blocks < 1 ? 1 : (blocks > 4096 ? 4096 : blocks);
-#define DN_FEATURES(S) hipLaunchKernelGGL((k_features<S>), dim3(blocks), dim3(256), 0, stream, dScene, resX, p0, nLocal, guide, albedo)
-    /* the kinds as vcm_api.hip's LAUNCH_SC picks them */
-    if (k.envMap) { if (k.bvh) DN_FEATURES(SceneBvhE); else if (k.intPhong && k.rects) DN_FEATURES(SceneRectsE); else DN_FEATURES(SceneListE); }
-    else if (k.bvh) { if (k.intPhong) DN_FEATURES(SceneBvh); else DN_FEATURES(SceneBvhG); }
-    else if (!k.intPhong) DN_FEATURES(SceneList);
-    else if (k.rects) DN_FEATURES(SceneRects);
-    else if (k.quads) DN_FEATURES(SceneQuads);
-    else DN_FEATURES(SceneList);
-#undef DN_FEATURES
+    with_scene_kind<kWrapNone>(kind, false, false, [&](auto tag) {
+        using S = typename decltype(tag)::type;
+        hipLaunchKernelGGL((k_features<S>), dim3(blocks), dim3(256), 0, stream, dScene, resX, p0, nLocal, guide, albedo);
+    });
     return hipGetLastError();
 }
 

@@ -62,6 +62,16 @@ def test_the_context_info_accessor_is_a_debug_entry_point():
     assert L.vcm_debug_context_info(None, out) == -1
 
 
+def test_the_scene_kind_rule_is_a_debug_entry_point():
+    """vcm_debug_scene_kind (the rule that picks a context's kind, for tests/test_scene_kind.py) is declared in the debug
+    header only and answers without a device"""
+    assert "vcm_debug_scene_kind" in _declared_symbols("smallvcm_amd_debug.h")
+    assert "vcm_debug_scene_kind" not in _declared_symbols("smallvcm_amd.h")
+    L = load_library(require_gpu=False)
+    L.vcm_debug_scene_kind.argtypes = [C.c_int] * 5
+    assert L.vcm_debug_scene_kind(0, 0, 0, 0, 0) == 0
+
+
 def test_farm_library_exports_what_its_header_declares():
     """include/smallvcm_amd_farm.h = the multi-GPU host's boundary (smallvcm_amd/host/libsmallvcm_amd_farm.so); loads
     without a GPU, exports exactly the declared entry points, PODs as the ctypes mirror assumes"""
