@@ -15,6 +15,7 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 from oracle_lib import Oracle  # noqa: E402
+from planted_lib import build_slab, place_slabs, reference_order, slab_words, sorted_block_cells  # noqa: E402
 from smallvcm_amd._abi import VCM_MERGE_RECORD_FLOATS  # noqa: E402
 from smallvcm_amd.renderer import RenderFarm, ShardedVertexCM, cornell_scene  # noqa: E402
 
@@ -74,14 +75,6 @@ class OracleBackend:
         dst.copy_(torch.from_numpy(self.o.framebuffer().ravel()))
 
 
-def sorted_block_cells(S):
-    """cells per block of the sorted exchange (smallvcm_amd/csrc/vcm_kernels.h sorted_block_cells)"""
-    k, p = 4096 // max(S, 1), 16
-    while p * 2 <= k and p < 1024:
-        p *= 2
-    return p
-
-
 class SortedOracleBackend(OracleBackend):
     """+ the SORTED exchange of round 5 (include/smallvcm_amd.h vcm_sort_light_records / vcm_import_sorted_light_records),
     restated in numpy so that ShardedVertexCM's sorted path and the slab layout run over gloo on the CPU: a rank's records
@@ -117,54 +110,23 @@ class SortedOracleBackend(OracleBackend):
     def sorted_slab_words(self, stride):
         if os.environ.get("SMALLVCM_AMD_SORTED_EXCHANGE", "1") == "0" or not (1 <= stride < (1 << 24)):
             return -1
-        return (stride * 13 + self.n_blocks + 1 + 3) & ~3
+        return slab_words(stride, self.n_cells, self.K)
 
     def sort_records(self, dst, stride):
         recs = self.o.records()
-        n = len(recs)
-        slab = np.zeros(self.sorted_slab_words(stride), np.uint32)
-        cells = self._cells(recs[:, :3]) if n else np.zeros(0, np.int64)
-        order = np.argsort(cells, kind="stable")
-        w = recs[order].view(np.uint32).copy()
-        if n:
-            w[:, 12] = (w[:, 12] & 0xff) | (order.astype(np.uint32) << 8)
-        slab[:n * 13] = w.ravel()
-        edges = np.minimum(np.arange(self.n_blocks + 1, dtype=np.int64) * self.K, self.n_cells)
-        slab[stride * 13:stride * 13 + self.n_blocks + 1] = np.searchsorted(cells[order], edges, side="left").astype(np.uint32)
+        cells = self._cells(recs[:, :3]) if len(recs) else np.zeros(0, np.int64)
+        slab = build_slab(recs, cells, stride, self.n_cells, self.K)               # tests/planted_lib.py
         dst[:len(slab)] = torch.from_numpy(slab.view(np.float32))
 
     def import_sorted_records(self, gathered, counts, stride):
         S, words = len(counts), self.sorted_slab_words(stride)
         slabs = gathered.numpy().view(np.uint32).reshape(S, words)
-        base = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
-        total = int(base[-1])
-        cnt = np.zeros((S, self.n_cells), np.int64)
-        recs, cells = [], []
-        for r in range(S):
-            w = slabs[r, :counts[r] * 13].reshape(counts[r], 13)
-            c = self._cells(w[:, :3].view(np.float32)) if counts[r] else np.zeros(0, np.int64)
-            assert np.all(np.diff(c) >= 0), "a slab is in cell order"
-            edges = np.minimum(np.arange(self.n_blocks + 1, dtype=np.int64) * self.K, self.n_cells)
-            assert np.array_equal(slabs[r, stride * 13:stride * 13 + self.n_blocks + 1].astype(np.int64), np.searchsorted(c, edges, side="left")), "block starts"
-            cnt[r] = np.bincount(c, minlength=self.n_cells)
-            recs.append(w)
-            cells.append(c)
-        cell_start = np.concatenate([[0], np.cumsum(cnt.sum(axis=0))])          # hashgrid.hxx:75-81
-        before = np.cumsum(cnt, axis=0) - cnt                                       # records of lower ranks in the cell
-        placed = np.zeros((total, 13), np.uint32)
-        index = np.zeros(total, np.int64)
-        for r in range(S):
-            local_start = np.concatenate([[0], np.cumsum(cnt[r])])
-            i = np.arange(counts[r], dtype=np.int64)
-            dst = cell_start[cells[r]] + before[r][cells[r]] + (i - local_start[cells[r]])
-            placed[dst] = recs[r]
-            index[dst] = base[r] + (recs[r][:, 12] >> 8)
-        assert len(np.unique(index)) == total
+        cells = [self._cells(slabs[r, :counts[r] * 13].reshape(counts[r], 13)[:, :3].view(np.float32)) if counts[r] else np.zeros(0, np.int64)
+                 for r in range(S)]
+        placed, index, _ = place_slabs(slabs, counts, stride, cells, self.n_cells, self.K)
         # = HashGrid::Build's stable counting sort over ALL records in the reference's order
-        ref = np.zeros((total, 13), np.uint32)
-        ref[index] = placed
-        ref[:, 12] &= 0xff
-        all_cells = self._cells(ref[:, :3].view(np.float32)) if total else np.zeros(0, np.int64)
+        ref = reference_order(placed, index)
+        all_cells = self._cells(ref[:, :3].view(np.float32)) if len(ref) else np.zeros(0, np.int64)
         assert np.array_equal(index, np.argsort(all_cells, kind="stable")), "in-cell order = vertex order, rank-major"
         self.o.import_records(ref.view(np.float32))
 

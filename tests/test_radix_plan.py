@@ -5,7 +5,8 @@ me with my digit, entries staged by digit, written out in runs, cellStart from t
 reference's counting sort produces: a STABLE sort of the vertices by cell and the exclusive scan of the cell counts.
 
 This is a model of the launch arithmetic (what a workgroup owns, where its entries go), not the product: the kernels themselves
-are compared with the oracle on the GPU (tests/test_gpu_parity.py, tests/test_gpu_switches.py: SMALLVCM_AMD_GRID_SORT*)."""
+are compared with the oracle on the GPU (tests/test_gpu_parity.py, tests/test_gpu_switches.py: SMALLVCM_AMD_GRID_SORT*).
+On planted cells -- tile, round and chunk edges, one workgroup -- the kernels run in tests/test_gpu_planted_records.py."""
 import numpy as np
 import pytest
 
