@@ -671,6 +671,43 @@ int vcm_robust_update_buffers(int device, long long n, const void *sumDev3, int 
 int vcm_robust_resolve_buffers(int device, long long n, const void *prevDev, const void *bucketsDev, int k, int buckets, void *outDev, void *hipStream);
 int vcm_robust_stats_buffers(int device, long long n, const void *prevDev, const void *bucketsDev, int k, int buckets, vcm_robust_stats *out, void *hipStream);
 
+/* ---- the technique breakdown: which part of the estimator carries a pixel ----
+ * The framebuffer is the sum of five kinds of addends, and a tracked context keeps each kind in a plane of its own BESIDE
+ * the framebuffer, without touching a rendering kernel: running sums over iterations with the framebuffer's meaning
+ * (divide by the iteration count to get the image), which add up to the framebuffer up to the rounding of another order.
+ *   VCM_PART_EMISSION     the camera path ends on an emitter or on the background (vertexcm.hxx:434-447, :468-479)
+ *   VCM_PART_DIRECT       direct illumination of every camera vertex, MIS-weighted (:487-494)
+ *   VCM_PART_CONNECT      the connections of camera vertices to light vertices (:498-526)
+ *   VCM_PART_MERGE        the range merges (:530-538)
+ *   VCM_PART_LIGHT_TRACE  the light vertices connected to the camera: the light splats (:380-384, :862-933)
+ * The order of the additions is fixed (smallvcm_amd/csrc/vcm_parts.h "THE ORDER"): the planes are the same bits on every
+ * run.  A plane an algorithm cannot fill stays exactly zero: light tracing fills LIGHT_TRACE alone, and it then equals the
+ * framebuffer bit for bit; PPM and BPM fill EMISSION and MERGE; BPT leaves MERGE empty.
+ * vcm_track_parts(ctx, 1) switches this on for a context whose framebuffer holds no iteration: a new context, or one right
+ * after vcm_clear_framebuffer (which also zeroes the planes); 0 switches it off.  Off -- the default -- costs nothing: no
+ * launch, no allocation, no byte.  Memory when on: 5 planes x 12 = 60 bytes per pixel (252 MB at 2048^2) until vcm_destroy,
+ * and 16 more from the first vcm_part_device on.  Independent of vcm_track_variance and vcm_track_robust.  The split is
+ * read from what wavefront mode keeps apart, so it is refused for a sharded context (its framebuffer is a shard of the
+ * image), for VCM_ALGO_PATH_TRACE / VCM_ALGO_EYE_LIGHT (no technique split here) and for a context in strict order;
+ * vcm_set_strict_order(ctx, 1) is refused while tracking is on, and vcm_begin_iteration fails with maxPathLength > 31 (the
+ * iteration would not be wavefront).  The reads are refused before the first iteration, for a part outside 0..4 and for
+ * a scale that is not finite.
+ * vcm_get_parts_stats: luminance[i] = the sum over pixels of 0.212671 r + 0.715160 g + 0.072169 b of plane i, divided by
+ * the iteration count; a pixel with a non-finite value in any plane is counted in nonFinite and left out of every sum.
+ * Binary64, no floating-point atomics, a fixed grid and a fixed combination tree (that of vcm_get_noise_stats): the same
+ * bits on every run.  It synchronises. */
+#define VCM_PART_EMISSION 0
+#define VCM_PART_DIRECT 1
+#define VCM_PART_CONNECT 2
+#define VCM_PART_MERGE 3
+#define VCM_PART_LIGHT_TRACE 4
+#define VCM_PART_COUNT 5
+typedef struct vcm_parts_stats { int iterations; long long pixels, nonFinite; double luminance[VCM_PART_COUNT]; } vcm_parts_stats;
+int vcm_track_parts(vcm_ctx *ctx, int on);
+int vcm_read_part(vcm_ctx *ctx, int part, float scale, float *rgbHost);   /* W*H*3 floats = plane * scale; scale 1 gives the raw sums */
+int vcm_part_device(vcm_ctx *ctx, int part, float scale, void **devPtr);  /* W*H float4 {rgb*scale, 1}, fit for vcm_denoise_buffers; valid until the next call */
+int vcm_get_parts_stats(vcm_ctx *ctx, vcm_parts_stats *out);              /* synchronises */
+
 #ifdef __cplusplus
 }
 #endif

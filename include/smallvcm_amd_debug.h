@@ -99,6 +99,12 @@ void vcm_debug_variance_max_blocks(int blocks);
  * that of the variance kernels: vcm_debug_variance_max_blocks caps both. */
 int vcm_debug_read_robust_images(vcm_ctx *ctx, float *prevHost4, float *bucketsHost4);
 
+/* The cap of the grids of k_resolve_parts, k_parts_stats and the part reads of a context with vcm_track_parts on (0
+ * restores the default, 2048 workgroups of 256 lanes), so that a test reaches the grid-stride paths and the second
+ * reduction level with a few hundred pixels.  Process-wide; the combination tree, and so the last bits of
+ * vcm_parts_stats.luminance, depend on it: not for production hosts. */
+void vcm_debug_parts_max_blocks(int blocks);
+
 /* sizeof the PODs of smallvcm_amd.h as the library was compiled */
 unsigned vcm_sizeof_scene_desc(void);
 unsigned vcm_sizeof_stats(void);

@@ -168,6 +168,24 @@ class RobustStats(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+# VCM_PART_*: the planes of the technique breakdown (vcm_track_parts)
+PART_EMISSION, PART_DIRECT, PART_CONNECT, PART_MERGE, PART_LIGHT_TRACE = 0, 1, 2, 3, 4
+PART_COUNT = 5
+PART_NAMES = ("emission", "direct", "connect", "merge", "lighttrace")
+PARTS = {n: i for i, n in enumerate(PART_NAMES)}
+
+
+class PartsStats(C.Structure):
+    """vcm_parts_stats: per plane of the technique breakdown, the luminance summed over the pixels and divided by
+    `iterations`; pixels with a non-finite value in any plane are counted and left out (include/smallvcm_amd.h)"""
+    _fields_ = [("iterations", C.c_int), ("pixels", C.c_longlong), ("nonFinite", C.c_longlong),
+                ("luminance", C.c_double * PART_COUNT)]
+
+    def asdict(self):
+        return {"iterations": self.iterations, "pixels": self.pixels, "nonFinite": self.nonFinite,
+                "luminance": dict(zip(PART_NAMES, list(self.luminance)))}
+
+
 class Stats(C.Structure):
     _fields_ = [("lightVertices", C.c_longlong), ("gridVertices", C.c_longlong),
                 ("lightRays", C.c_longlong), ("cameraRays", C.c_longlong),

@@ -23,6 +23,7 @@
 #include "vcm_denoise.h"
 #include "vcm_variance.h"
 #include "vcm_robust.h"
+#include "vcm_parts.h"
 
 using namespace vcm;
 
@@ -193,6 +194,10 @@ struct vcm_ctx : Scratch {
     /* the firefly-robust estimate (vcm_robust.h): allocated by vcm_track_robust(ctx, M) */
     int robustBuckets, robustAlloc;   /* M while tracking is on, else 0; the M the planes were allocated for */
     F4 *dRobPrev, *dRobBuckets, *dRobOut;   /* N, M x N, N: the sum the last update saw, the bucket planes, the resolved image */
+    /* the technique breakdown (vcm_parts.h): allocated by vcm_track_parts(ctx, 1) */
+    bool trackParts;
+    float *dParts;                    /* VCM_PART_COUNT planes of N x 3 floats, the framebuffer's layout */
+    F4 *dPartOut;                     /* N: what the last vcm_part_device made (allocated by the first) */
     int fbIterations;                 /* iterations the framebuffer holds: those since the last vcm_clear_framebuffer; while
                                          tracking is on (it starts at 0 only) also the k of the two images */
     IterParams P;
@@ -970,6 +975,7 @@ void vcm_destroy(vcm_ctx *c)
         DFREE(c->dGuide); DFREE(c->dAlbedo); DFREE(c->dDnA); DFREE(c->dDnB); DFREE(c->dDenoised);
         DFREE(c->dVarPrev); DFREE(c->dVarMom);
         DFREE(c->dRobPrev); DFREE(c->dRobBuckets); DFREE(c->dRobOut);
+        DFREE(c->dParts); DFREE(c->dPartOut);
         c->dScene = NULL; DFREE(c->dSceneBlob); DFREE(c->dFb); DFREE(c->dRngLight); DFREE(c->dRngCam); DFREE(c->dHdr); DFREE(c->dStatsRing); DFREE(c->dStamps);
         for (int i = 0; i < EV_COUNT; i++) (void)hipEventDestroy(c->ev[i]);
         (void)hipStreamSynchronize(c->side);
@@ -990,6 +996,7 @@ int vcm_set_strict_order(vcm_ctx *c, int on)
 {
     if (!c) return fail("vcm_set_strict_order", "ctx is NULL");
     if (c->inIteration) return fail("vcm_set_strict_order", "iteration in progress");
+    if (on && c->trackParts) return fail("vcm_set_strict_order", "vcm_track_parts is on: the technique breakdown reads what wavefront mode keeps apart");
     c->strictOrder = on != 0;
     return 0;
 }
@@ -1044,6 +1051,8 @@ static int vcm_begin_iteration_impl(vcm_ctx *c, int iteration, unsigned minLen, 
     if (!c) return fail("vcm_begin_iteration", "ctx is NULL");
     if (c->inIteration) return fail("vcm_begin_iteration", "previous iteration not ended");
     if (maxLen > 255) return fail("vcm_begin_iteration", "maxPathLength > 255 unsupported (8-bit vertex counts)");
+    if (c->trackParts && maxLen > 31) return fail("vcm_begin_iteration", "vcm_track_parts is on and maxPathLength > 31: the iteration would not be wavefront, "
+                                                                          "and the technique breakdown reads what wavefront mode keeps apart");
     /* the two-launch scans (launch_scan_on) take at most 16384 tiles of 2048 entries: say so here, not in the middle of an
        iteration -- 33.5 M paths per rank, a 5792^2 frame */
     if ((long long)c->N / VCM_SCAN_TILE + 2 > 16384 || (long long)c->nLocal / VCM_SCAN_TILE + 2 > 16384)
@@ -1233,6 +1242,18 @@ static int flush_light_splats(vcm_ctx *c)
         hipLaunchKernelGGL(k_splat_apply_long, dim3(1024), dim3(256), 0, q, (const int *)pixStart, (const F4 *)list,
                            c->dSplat, c->dFb, (const int *)arrival, (const int *)pixCount);
         HIPCHK(hipGetLastError());
+        if (c->trackParts) {
+            /* the LIGHT_TRACE plane: the same two kernels over the same lists once more, with the plane in the framebuffer's
+               place -- the same additions in the same order, whichever of the three regimes a list falls into.  The queue of long
+               lists is counted anew (its word was consumed by the launch above); `sorted` is rewritten with what it holds. */
+            float *plane = c->dParts + (size_t)VCM_PART_LIGHT_TRACE * (size_t)c->N * 3;
+            HIPCHK(hipMemsetAsync(pixCount, 0, sizeof(int), q));
+            hipLaunchKernelGGL(k_splat_apply, dim3(aux_blocks(c->nLocal)), dim3(256), 0, q, c->N, (const int *)pixStart,
+                               (const F4 *)list, plane, arrival, pixCount, splatLong);
+            hipLaunchKernelGGL(k_splat_apply_long, dim3(1024), dim3(256), 0, q, (const int *)pixStart, (const F4 *)list,
+                               c->dSplat, plane, (const int *)arrival, (const int *)pixCount);
+            HIPCHK(hipGetLastError());
+        }
         if (overlap) {
             HIPCHK(hipEventRecord(c->evSplatDone, q));
             c->splatInFlight = true;
@@ -2048,6 +2069,9 @@ static int vcm_merge_impl(vcm_ctx *c)
             hipLaunchKernelGGL(k_resolve, dim3(resolve_blocks(c->nLocal, c->useVC)), dim3(256), 0, c->splat, c->P, (const F4 *)c->dCamOut,
                                (const uint32_t *)c->dCamMask, c->vs, c->dFb, take_stamps(c, c->stream));
             HIPCHK(hipGetLastError());
+            if (c->trackParts)   /* behind K5 on its stream, in front of everything that waits for K5: the scratch it reads is K5's */
+                HIPCHK(parts_launch_resolve(c->P, (const F4 *)c->dCamOut, (const uint32_t *)c->dCamMask, c->vs, c->dParts, (size_t)c->N * 3,
+                                            resolve_blocks(c->nLocal, c->useVC), c->splat));
             if (mark(c, EV_CAMERA)) return -1;
             if (c->nPend[0] > 0) {   /* the end mark: a one-lane launch behind K5, on its stream */
                 hipLaunchKernelGGL(k_stamp_many, dim3(1), dim3(1), 0, c->splat, take_stamps(c, c->stream));
@@ -2067,6 +2091,9 @@ static int vcm_merge_impl(vcm_ctx *c)
         hipLaunchKernelGGL(k_resolve, dim3(resolve_blocks(c->nLocal, false)), dim3(256), 0, c->stream, c->P, (const F4 *)c->dCamOut,
                            (const uint32_t *)c->dCamMask, c->vs, c->dFb, take_stamps(c, c->stream));
         HIPCHK(hipGetLastError());
+        if (c->trackParts)
+            HIPCHK(parts_launch_resolve(c->P, (const F4 *)c->dCamOut, (const uint32_t *)c->dCamMask, c->vs, c->dParts, (size_t)c->N * 3,
+                                        resolve_blocks(c->nLocal, false), c->stream));
     }
     if (join_splats(c)) return -1;               /* light tracing alone: nothing else waited for them */
     if (mark(c, EV_CAMERA)) return -1;
@@ -2249,6 +2276,12 @@ static int robust_reset_images(vcm_ctx *c)
     return 0;
 }
 
+static int parts_reset_planes(vcm_ctx *c)
+{
+    HIPCHK(hipMemsetAsync(c->dParts, 0, (size_t)VCM_PART_COUNT * (size_t)c->N * 3 * sizeof(float), c->stream));
+    return 0;
+}
+
 int vcm_clear_framebuffer(vcm_ctx *c)
 {
     if (!c) return fail("vcm_clear_framebuffer", "ctx is NULL");
@@ -2259,6 +2292,7 @@ int vcm_clear_framebuffer(vcm_ctx *c)
     c->fbIterations = 0;
     if (c->trackVariance && var_reset_images(c)) return -1;
     if (c->robustBuckets && robust_reset_images(c)) return -1;
+    if (c->trackParts && parts_reset_planes(c)) return -1;
     return 0;
 }
 
@@ -2740,6 +2774,88 @@ int vcm_robust_stats_buffers(int device, long long n, const void *prevDev, const
     if (robust_buffers_check("vcm_robust_stats_buffers", device, n, k, buckets, true)) return -1;
     return robust_stats_of("vcm_robust_stats_buffers", n, (const F4 *)prevDev, (const F4 *)bucketsDev, k, buckets, out, (hipStream_t)hipStream);
 }
+
+/* ---- the technique breakdown (kernels: vcm_parts.hip; the LIGHT_TRACE plane: flush_light_splats) ---- */
+int vcm_track_parts(vcm_ctx *c, int on)
+{
+    if (!c) return fail("vcm_track_parts", "ctx is NULL");
+    if (refuse_sharded(c, "vcm_track_parts")) return -1;
+    if (c->inIteration) return fail("vcm_track_parts", "iteration in progress");
+    if (!on) { c->trackParts = false; return 0; }   /* the planes stay until vcm_destroy; switching on again wants a clear */
+    if (c->renderer) return fail("vcm_track_parts", "VCM_ALGO_PATH_TRACE and VCM_ALGO_EYE_LIGHT have no technique split: the breakdown is that of the VertexCM algorithms");
+    if (c->strictOrder) return fail("vcm_track_parts", "the context is in strict order: the technique breakdown reads what wavefront mode keeps apart");
+    if (c->fbIterations != 0) return fail("vcm_track_parts", "the framebuffer holds iterations already: switch tracking on before the first "
+                                                              "iteration or right after vcm_clear_framebuffer");
+    g_hipFailed = false;
+    if (ensure_device(c)) return -1;
+    if (!c->dParts && dalloc(&c->dParts, (size_t)VCM_PART_COUNT * (size_t)c->N * 3)) return -1;
+    if (join_splats(c)) return -1;
+    if (parts_reset_planes(c)) return -1;
+    c->trackParts = true;
+    return 0;
+}
+
+/* tracked, not sharded, and at least one iteration in the planes */
+static int need_parts(vcm_ctx *c, const char *who)
+{
+    if (refuse_sharded(c, who)) return -1;
+    if (!c->trackParts) return fail(who, "vcm_track_parts is off");
+    if (c->fbIterations < 1) return fail(who, "the planes hold no iteration yet");
+    if (use_device(c)) return -1;
+    return join_splats(c);   /* the last k_resolve_parts runs behind K5 on the splat stream */
+}
+static int part_args_ok(const char *who, int part, float scale)
+{
+    if (part < 0 || part >= VCM_PART_COUNT) return fail(who, "part must be 0 .. 4 (VCM_PART_*)");
+    if (!parts_finite(scale)) return fail(who, "scale is not finite");
+    return 0;
+}
+
+int vcm_read_part(vcm_ctx *c, int part, float scale, float *rgbHost)
+{
+    if (!c || !rgbHost) return fail("vcm_read_part", "NULL argument");
+    g_hipFailed = false;
+    if (part_args_ok("vcm_read_part", part, scale) || need_parts(c, "vcm_read_part")) return -1;
+    float *d = NULL;
+    if (dalloc(&d, (size_t)c->N * 3)) return -1;
+    hipError_t e = parts_launch_read3(c->N, c->dParts + (size_t)part * (size_t)c->N * 3, scale, d, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(rgbHost, d, (size_t)c->N * 3 * sizeof(float), hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    (void)hipFree(d);
+    if (e != hipSuccess) { g_hipFailed = true; return fail("vcm_read_part", hipGetErrorString(e)); }
+    return 0;
+}
+
+int vcm_part_device(vcm_ctx *c, int part, float scale, void **devPtr)
+{
+    if (!c || !devPtr) return fail("vcm_part_device", "NULL argument");
+    g_hipFailed = false;
+    if (part_args_ok("vcm_part_device", part, scale) || need_parts(c, "vcm_part_device")) return -1;
+    if (!c->dPartOut && dalloc(&c->dPartOut, (size_t)c->N)) return -1;
+    HIPCHK(parts_launch_read4(c->N, c->dParts + (size_t)part * (size_t)c->N * 3, scale, c->dPartOut, c->stream));
+    *devPtr = c->dPartOut;   /* whoever reads it orders against the context's stream */
+    return 0;
+}
+
+int vcm_get_parts_stats(vcm_ctx *c, vcm_parts_stats *out)
+{
+    if (!c || !out) return fail("vcm_get_parts_stats", "NULL argument");
+    g_hipFailed = false;
+    if (need_parts(c, "vcm_get_parts_stats")) return -1;
+    const int cap = parts_max_blocks();
+    hipStream_t s = c->stream;
+    PartsAcc *scratch = NULL, result;   /* cap partials and the result behind them */
+    HIPCHK(hipMallocAsync((void **)&scratch, (size_t)(cap + 1) * sizeof(PartsAcc), s));
+    hipError_t e = parts_launch_stats(c->N, c->dParts, (size_t)c->N * 3, cap, scratch, scratch + cap, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(&result, scratch + cap, sizeof(PartsAcc), hipMemcpyDeviceToHost, s);
+    (void)hipFreeAsync(scratch, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (e != hipSuccess) { g_hipFailed = true; return fail("vcm_get_parts_stats", hipGetErrorString(e)); }
+    parts_finish_stats(result, c->fbIterations, c->N, out);
+    return 0;
+}
+
+void vcm_debug_parts_max_blocks(int blocks) { parts_set_max_blocks(blocks); }
 
 int vcm_iterations(vcm_ctx *c) { return c ? c->iterations : 0; }
 

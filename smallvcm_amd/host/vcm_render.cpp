@@ -14,6 +14,7 @@
 //              [--light-pick uniform|power [--light-pick-mix A] [--light-pick-report]]
 //              [--denoise [passes]] [--denoise-sigma c,n,z] [--no-demodulate] [--features-out prefix]
 //              [--noise-target E [--check-every N] [--max-iterations M]] [--track-variance] [--robust [M]]
+//              [--parts prefix]
 //              [--gpus N [--shards S] [--inflight K] [--devices 0,1,..] [--collectives rccl|threads] [--same-window]]
 //
 // --gpus N: the multi-GPU host (vcm_farm.hpp): N ranks = N host threads, one per GPU, cut into N / S groups; a
@@ -50,6 +51,12 @@
 // every pixel averages the central bucket means, trimmed by their Gini coefficient (vcm_read_robust).  Wants -i >= M and
 // one renderer on one GPU.  What the rule decided (vcm_get_robust_stats) is printed, and is "robust" in --json.  With
 // --denoise it is refused: filtering the robust image is a host's own vcm_robust_device + vcm_denoise_buffers for now.
+//
+// --parts P: the technique breakdown (vcm_track_parts): which part of the estimator carries a pixel.  Writes
+// P_emission.pfm, P_direct.pfm, P_connect.pfm, P_merge.pfm and P_lighttrace.pfm -- each plane divided by the iteration
+// count, so that the five add up to the image -- prints each part's share of the total luminance (vcm_get_parts_stats) and
+// adds "parts" to --json.  Wants one renderer on one GPU, a VertexCM algorithm (lt, ppm, bpm, bpt, vcm), no --strict and
+// --maxlen <= 31; anything else is refused with exit status 2 before any device call.
 //
 // -s / -a / -i keep the meaning they have in the reference's CLI
 // (src/config.hxx:246-395; scenes = g_SceneConfigs[0..3], :146-151).
@@ -119,6 +126,8 @@ int main(int argc, char **argv)
     int checkEvery = 4, maxIterations = 1024;
     int robust = 0;
     vcm_robust_stats rs = {};
+    std::string partsOut;
+    vcm_parts_stats ps = {};
     for (int i = 1; i < argc; i++) {
         const std::string a(argv[i]);
         auto need = [&](int n) { if (i + n >= argc) { fprintf(stderr, "vcm_render: %s needs %d argument(s)\n", a.c_str(), n); exit(2); } };
@@ -185,6 +194,7 @@ int main(int argc, char **argv)
             if (i + 1 < argc && argv[i + 1][0] >= '0' && argv[i + 1][0] <= '9') robust = atoi(argv[++i]);
             if (robust < 3 || robust > 15 || robust % 2 == 0) { fprintf(stderr, "vcm_render: --robust takes an odd number of buckets, 3 .. 15\n"); return 2; }
         }
+        else if (a == "--parts") { need(1); partsOut = argv[++i]; }
         else if (a == "--strict") strict = 1;
         else if (a == "--json") json = 1;
         else { fprintf(stderr, "vcm_render: unknown option %s (see the header of vcm_render.cpp)\n", a.c_str()); return 2; }
@@ -207,6 +217,18 @@ int main(int argc, char **argv)
     }
     if (robust && (renderers != 1 || gpus > 0)) {
         fprintf(stderr, "vcm_render: --robust wants one renderer on one GPU (a farm host reduces the frames and calls vcm_robust_update_buffers)\n");
+        return 2;
+    }
+    if (!partsOut.empty() && (renderers != 1 || gpus > 0)) {
+        fprintf(stderr, "vcm_render: --parts wants one renderer on one GPU (the technique breakdown is kept beside one context's framebuffer)\n");
+        return 2;
+    }
+    if (!partsOut.empty() && (algorithm == VCM_ALGO_PATH_TRACE || algorithm == VCM_ALGO_EYE_LIGHT)) {
+        fprintf(stderr, "vcm_render: --parts wants a VertexCM algorithm (lt, ppm, bpm, bpt, vcm): %s has no technique split\n", algoName.c_str());
+        return 2;
+    }
+    if (!partsOut.empty() && (strict || maxLen > 31)) {
+        fprintf(stderr, "vcm_render: --parts reads what wavefront mode keeps apart: no --strict, --maxlen <= 31\n");
         return 2;
     }
     if (haveTargetOption && !haveTarget) { fprintf(stderr, "vcm_render: --check-every and --max-iterations go with --noise-target\n"); return 2; }
@@ -347,6 +369,7 @@ int main(int argc, char **argv)
         if (strict && vcm_set_strict_order(r[g], 1)) return die("vcm_set_strict_order");
         if (trackVariance && vcm_track_variance(r[g], 1)) return die("vcm_track_variance");
         if (robust && vcm_track_robust(r[g], robust)) return die("vcm_track_robust");
+        if (!partsOut.empty() && vcm_track_parts(r[g], 1)) return die("vcm_track_parts");
     }
     if (pick && (pick->mode != VCM_LIGHT_PICK_UNIFORM || pickReport) && !json) {
         const int nLights = pickScene->base.base.base.nLights;
@@ -419,6 +442,26 @@ int main(int argc, char **argv)
         if (vcm_get_robust_stats(r[0], &rs)) return die("vcm_get_robust_stats");
         if (!json) printf("robust estimate after %d iteration(s) in %d buckets: %lld of %lld pixels trimmed, %lld with a non-finite bucket, Gini mean %.9g, max %.9g\n",
                           rs.iterations, rs.buckets, rs.trimmed, rs.pixels, rs.nonFinite, rs.meanGini, rs.maxGini);
+    }
+    if (!partsOut.empty()) {   // the five planes / iterations, rows top to bottom like SavePFM, and their shares
+        const char *name[VCM_PART_COUNT] = { "emission", "direct", "connect", "merge", "lighttrace" };
+        if (vcm_get_parts_stats(r[0], &ps)) return die("vcm_get_parts_stats");
+        for (int k = 0; k < VCM_PART_COUNT; k++) {
+            if (vcm_read_part(r[0], k, 1.f / ps.iterations, tmp.data())) return die("vcm_read_part");
+            const std::string path = partsOut + "_" + name[k] + ".pfm";
+            FILE *f = fopen(path.c_str(), "wb");
+            if (!f) { fprintf(stderr, "vcm_render: cannot write %s\n", path.c_str()); return 2; }
+            fprintf(f, "PF\n%d %d\n-1\n", resX, resY);
+            fwrite(tmp.data(), sizeof(float), n3, f);
+            fclose(f);
+        }
+        double total = 0;
+        for (int k = 0; k < VCM_PART_COUNT; k++) total += ps.luminance[k];
+        if (!json) {
+            printf("technique breakdown after %d iteration(s), %lld pixel(s) with a non-finite value left out:\n", ps.iterations, ps.nonFinite);
+            for (int k = 0; k < VCM_PART_COUNT; k++)
+                printf("  %-10s %6.2f %% of the luminance\n", name[k], total > 0 ? 100.0 * ps.luminance[k] / total : 0.0);
+        }
     }
     }
 
@@ -515,6 +558,10 @@ int main(int argc, char **argv)
         if (robust) snprintf(robustJson, sizeof(robustJson), ", \"robust\": {\"iterations\": %d, \"buckets\": %d, \"pixels\": %lld, \"trimmed\": %lld, "
                              "\"nonFinite\": %lld, \"meanGini\": %.17g, \"maxGini\": %.17g}", rs.iterations, rs.buckets, rs.pixels, rs.trimmed, rs.nonFinite,
                              rs.meanGini, rs.maxGini);
+        char partsJson[480] = "";
+        if (!partsOut.empty()) snprintf(partsJson, sizeof(partsJson), ", \"parts\": {\"iterations\": %d, \"pixels\": %lld, \"nonFinite\": %lld, \"luminance\": "
+                                        "{\"emission\": %.17g, \"direct\": %.17g, \"connect\": %.17g, \"merge\": %.17g, \"lighttrace\": %.17g}}",
+                                        ps.iterations, ps.pixels, ps.nonFinite, ps.luminance[0], ps.luminance[1], ps.luminance[2], ps.luminance[3], ps.luminance[4]);
         std::string ms = "[";
         for (size_t i = 0; i < rankMs.size(); i++) { char b[32]; snprintf(b, sizeof(b), "%s%.3f", i ? ", " : "", rankMs[i]); ms += b; }
         ms += "]";
@@ -523,12 +570,12 @@ int main(int argc, char **argv)
                "\"last_iteration_ms\": %.3f, \"rank_iteration_ms\": %s, \"library\": \"%s\", "
                "\"last_iteration_kernel_ms\": {\"light\": %.3f, \"camera\": %.3f, \"connect_di\": %.3f, \"merge\": %.3f, \"grid_side\": %.3f, \"light_phase\": %.3f, \"camera_phase\": %.3f}, "
                "\"last_iteration_counters\": {\"lightVertices\": %lld, \"lightRays\": %lld, \"cameraRays\": %lld, \"shadowRays\": %lld, "
-               "\"mergeQueries\": %lld, \"mergeCandidates\": %lld, \"mergeAccepted\": %lld, \"connections\": %lld, \"lightSplats\": %lld}%s}\n",
+               "\"mergeQueries\": %lld, \"mergeCandidates\": %lld, \"mergeAccepted\": %lld, \"connections\": %lld, \"lightSplats\": %lld}%s%s}\n",
                sceneID, algoName.c_str(), resX, resY, iterations, renderers, seed, gpus > 0 ? gpus : 1, rcclRanks, wall, paths / wall / 1e6,
                mean[0] / (n3 / 3), mean[1] / (n3 / 3), mean[2] / (n3 / 3), st.msTotal, ms.c_str(), vcm_build_tag(),
                st.msLightKernel, st.msCameraKernel, st.msConnectKernels, st.msMergeKernel, st.msGrid, st.msLight, st.msCamera,
                st.lightVertices, st.lightRays, st.cameraRays, st.shadowRays, st.mergeQueries, st.mergeCandidates, st.mergeAccepted,
-               st.connections, st.lightSplats, robustJson);
+               st.connections, st.lightSplats, robustJson, partsJson);
     }
     else
         printf("scene %d, %s, %dx%d, %d iteration(s) on %d renderer(s): %.3f s wall clock, %.2f Mpaths/s\n", sceneID,

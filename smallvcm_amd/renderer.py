@@ -21,7 +21,7 @@ import os
 
 import numpy as np
 
-from ._abi import (DenoiseParams, DenoiseParams2, FEATURES, NoiseStats, ROBUST_DEFAULT_BUCKETS, RobustStats, SceneDesc, SceneDesc2, SceneDesc3, SceneDesc4, SceneDesc5, Stats, SCENE_CONFIGS, VCM_MERGE_RECORD_FLOATS, ALGO_LIGHT_TRACE, ALGO_PPM, ALGO_BPM,
+from ._abi import (DenoiseParams, DenoiseParams2, FEATURES, NoiseStats, PART_NAMES, PARTS, PartsStats, ROBUST_DEFAULT_BUCKETS, RobustStats, SceneDesc, SceneDesc2, SceneDesc3, SceneDesc4, SceneDesc5, Stats, SCENE_CONFIGS, VCM_MERGE_RECORD_FLOATS, ALGO_LIGHT_TRACE, ALGO_PPM, ALGO_BPM,
                    ALGO_BPT, ALGO_VCM)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -138,6 +138,12 @@ def load_library(require_gpu=True):
         L.vcm_robust_update_buffers.argtypes = [C.c_int, C.c_longlong, vp, C.c_int, C.c_int, vp, vp, vp]
         L.vcm_robust_resolve_buffers.argtypes = [C.c_int, C.c_longlong, vp, vp, C.c_int, C.c_int, vp, vp]
         L.vcm_robust_stats_buffers.argtypes = [C.c_int, C.c_longlong, vp, vp, C.c_int, C.c_int, C.POINTER(RobustStats), vp]
+        L.vcm_track_parts.argtypes = [vp, C.c_int]
+        L.vcm_read_part.argtypes = [vp, C.c_int, C.c_float, fp]
+        L.vcm_part_device.argtypes = [vp, C.c_int, C.c_float, C.POINTER(vp)]
+        L.vcm_get_parts_stats.argtypes = [vp, C.POINTER(PartsStats)]
+        L.vcm_debug_parts_max_blocks.argtypes = [C.c_int]
+        L.vcm_debug_parts_max_blocks.restype = None
         L.vcm_denoise_defaults2.argtypes = [C.POINTER(DenoiseParams2)]
         L.vcm_denoise_defaults2.restype = None
         L.vcm_denoise2.argtypes = [vp, C.c_float, C.POINTER(DenoiseParams2)]
@@ -355,6 +361,7 @@ class HipBackend:
         self.device = device
         self._tstream = None
         self._max_len = 2
+        self._fb_iterations = 0   # iterations the framebuffer holds (since the last clear_framebuffer)
 
     def stream_context(self):
         """Run this context's kernels and the caller's torch ops (collectives,
@@ -420,9 +427,11 @@ class HipBackend:
 
     def end(self):
         _check(self.L, self.L.vcm_end_iteration(self.ctx), "vcm_end_iteration")
+        self._fb_iterations += 1
 
     def run_iteration(self, it, min_len, max_len):
         _check(self.L, self.L.vcm_run_iteration(self.ctx, it, min_len, max_len), "vcm_run_iteration")
+        self._fb_iterations += 1
 
     def synchronize(self):
         _check(self.L, self.L.vcm_synchronize(self.ctx), "vcm_synchronize")
@@ -485,6 +494,7 @@ class HipBackend:
 
     def clear_framebuffer(self):
         _check(self.L, self.L.vcm_clear_framebuffer(self.ctx), "vcm_clear_framebuffer")
+        self._fb_iterations = 0
 
     def stats(self):
         s = Stats()
@@ -583,6 +593,40 @@ class HipBackend:
         _check(self.L, self.L.vcm_get_robust_stats(self.ctx, C.byref(st)), "vcm_get_robust_stats")
         return st.asdict()
 
+    # ---- the technique breakdown ------------------------------------------------
+    def track_parts(self, on=True):
+        """keep the five kinds of addends of the framebuffer -- emission, direct, connect, merge, lighttrace -- in planes of
+        their own from the next iteration on (before the first iteration, or right after clear_framebuffer; a VertexCM
+        algorithm in wavefront mode on one GPU); 60 bytes per pixel"""
+        _check(self.L, self.L.vcm_track_parts(self.ctx, 1 if on else 0), "vcm_track_parts")
+
+    def part(self, which, scale=None):
+        """plane `which` (a name of PART_NAMES or a PART_* index) times `scale` -> [H, W, 3]; None: 1 / iterations, the
+        part of the image; 1: the raw sums"""
+        w = PARTS[which] if isinstance(which, str) else int(which)
+        if scale is None:
+            scale = 1.0 / self._fb_iterations if self._fb_iterations > 0 else 1.0
+        out = np.zeros((self.resy, self.resx, 3), np.float32)
+        _check(self.L, self.L.vcm_read_part(self.ctx, w, scale, out.ctypes.data_as(C.POINTER(C.c_float))), "vcm_read_part")
+        return out
+
+    def parts(self, scale=None):
+        """{name: part(name, scale)} for the five planes"""
+        return {n: self.part(n, scale) for n in PART_NAMES}
+
+    def part_device(self, which, scale):
+        """device pointer of the float4 image {plane rgb * scale, 1}; valid until the next call"""
+        w = PARTS[which] if isinstance(which, str) else int(which)
+        p = C.c_void_p()
+        _check(self.L, self.L.vcm_part_device(self.ctx, w, scale, C.byref(p)), "vcm_part_device")
+        return p.value
+
+    def parts_stats(self):
+        """vcm_get_parts_stats: {iterations, pixels, nonFinite, luminance: {name: sum over pixels / iterations}}"""
+        st = PartsStats()
+        _check(self.L, self.L.vcm_get_parts_stats(self.ctx, C.byref(st)), "vcm_get_parts_stats")
+        return st.asdict()
+
     def stats_at(self, ago):
         """counters and phase times of the iteration `ago` iterations before the last completed one (<= 63)"""
         st = Stats()
@@ -650,6 +694,11 @@ class VertexCM:
         """GetFramebuffer() by the firefly-robust estimate (the reference has no such call): wants backend.track_robust()
         before the first iteration and as many iterations as buckets"""
         return self.backend.robust()
+
+    def GetPart(self, which):
+        """the part of GetFramebuffer() that technique `which` carries (a name of PART_NAMES or a PART_* index; the
+        reference has no such call): wants backend.track_parts() before the first iteration"""
+        return self.backend.part(which)
 
     def GetDenoised(self, **params):
         """GetFramebuffer() through the edge-avoiding denoiser (the reference has no such call); params: see
