@@ -190,6 +190,32 @@ typedef struct vcm_scene_desc5 {
     const vcm_light_pick *pick;
 } vcm_scene_desc5;
 
+/* The pixel reconstruction filter (DESIGN.md "Pixel filter").  BOX: the reference's -- a camera path jitters inside its
+ * pixel, a light vertex adds to the pixel its projection falls in.  TENT and BSPLINE: filter importance sampling on
+ * both sides with a separable offset density g whose support is `radius` pixels (finite, 0 < radius <= 16) per axis:
+ * a camera path keeps its pixel and sends its ray through its sample moved by o ~ g, a light vertex is splatted to the
+ * pixel that holds its projection moved by o ~ g (dropped when that point is outside the image).  Every pixel is then
+ * measured with h = box * g on both sides; no splat carries a weight.  TENT: o = radius (u1 - u2) per axis, the tent of
+ * half-width radius (variance radius^2 / 6).  BSPLINE: o = radius (u1 + u2 + u3 + u4 - 2) / 2, the cubic B-spline on
+ * (-radius, radius) (variance radius^2 / 12: close to a Gaussian of sigma = radius / sqrt(12), 0.577 pixels at radius
+ * 2).  The first-hit guide images (vcm_render_features) stay unfiltered. */
+enum {
+    VCM_FILTER_BOX = 0,
+    VCM_FILTER_TENT = 1,
+    VCM_FILTER_BSPLINE = 2
+};
+typedef struct vcm_pixel_filter {
+    int   kind;
+    float radius;              /* pixels; ignored for BOX */
+} vcm_pixel_filter;
+
+/* Scene description, version 6: a version-5 scene and its pixel filter.  `filter` NULL, or kind BOX, renders exactly
+ * what vcm_create5 renders.  The filter is copied. */
+typedef struct vcm_scene_desc6 {
+    vcm_scene_desc5         base;
+    const vcm_pixel_filter *filter;
+} vcm_scene_desc6;
+
 /* VertexCM::AlgorithmType (src/vertexcm.hxx:182-204) -- same values */
 enum {
     VCM_ALGO_LIGHT_TRACE = 0,
@@ -291,6 +317,14 @@ vcm_ctx *vcm_create_sharded4(const vcm_scene_desc4 *scene, int algorithm,
 vcm_ctx *vcm_create5(const vcm_scene_desc5 *scene, int algorithm,
                      float radiusFactor, float radiusAlpha, int seed);
 vcm_ctx *vcm_create_sharded5(const vcm_scene_desc5 *scene, int algorithm,
+                             float radiusFactor, float radiusAlpha, int seed,
+                             int device, int rank, int worldSize);
+
+/* The same for a version-6 scene description (pixel filter).  NULL with vcm_last_error() for an unknown kind, a radius
+ * that is not finite, <= 0 or > 16 (TENT, BSPLINE), or a bad version-5 scene; checked before a device is looked for. */
+vcm_ctx *vcm_create6(const vcm_scene_desc6 *scene, int algorithm,
+                     float radiusFactor, float radiusAlpha, int seed);
+vcm_ctx *vcm_create_sharded6(const vcm_scene_desc6 *scene, int algorithm,
                              float radiusFactor, float radiusAlpha, int seed,
                              int device, int rank, int worldSize);
 
@@ -525,6 +559,9 @@ const vcm_scene_desc4 *vcm_scene_file_desc4(const vcm_scene_file *scene);
 /* The scene as a version-5 description: pick set when the file has a `lightpick uniform|power [uniformMix]` directive,
  * NULL otherwise; its base is vcm_scene_file_desc4's.  Points into the handle, like vcm_scene_file_desc. */
 const vcm_scene_desc5 *vcm_scene_file_desc5(const vcm_scene_file *scene);
+/* The same scene as a version-6 description: `filter` set when the file has a `filter tent|bspline radius` directive,
+ * NULL otherwise; its base is vcm_scene_file_desc5's.  Points into the handle, like vcm_scene_file_desc. */
+const vcm_scene_desc6 *vcm_scene_file_desc6(const vcm_scene_file *scene);
 
 /* Environment maps from files: Radiance RGBE (.hdr: "#?RADIANCE" / "#?RGBE", FORMAT=32-bit_rle_rgbe, "-Y H +X W", flat
  * or new-style run-length scanlines) or PFM (.pfm: "PF", either byte order; its bottom-up rows are flipped), picked by

@@ -63,7 +63,11 @@ enum {
     VCM_KAT_LIGHT_PICK = 9,       /* in: the pick's random float -> light index, its pmf; in[1] = a light index -> out[2] = the
                                      pmf the emitter-hit sites use for it (pick_light / light_pick_prob)
                                                                                                   DESIGN.md "Light selection" */
-    VCM_KAT_OPS = 10
+    VCM_KAT_FILTER = 10,          /* in: raster x, y of a projection, then the 8 floats of a filter draw -> offset x, y, the pixel the
+                                     splat goes to (-1: outside the image), and the moved point (x, y) + offset, added in the
+                                     record itself, for reading the pixel; needs a context with a pixel filter (vcm_create6)
+                                                                                                  DESIGN.md "Pixel filter" */
+    VCM_KAT_OPS = 11
 };
 int vcm_debug_kat(vcm_ctx *ctx, int op, int n, const float *in, float *out);
 
@@ -79,6 +83,11 @@ enum {
     VCM_INFO_COUNT = 11
 };
 int vcm_debug_context_info(vcm_ctx *ctx, int *out);
+
+/* The pixel filter of a context as its kernels see it (vcm_pixel_filter; kind VCM_FILTER_BOX: none, the context launches
+ * exactly the kernels of vcm_create5).  A filter without a lens launches the WithLens kinds, so VCM_INFO_LENS -- which
+ * stays "the scene has a thin lens" -- does not tell; this does.  Either pointer may be NULL. */
+int vcm_debug_pixel_filter(vcm_ctx *ctx, int *kind, float *radius);
 
 /* The rule that picks a context's kind from the five facts about its scene (csrc/scene_kind.h, scene_kind_of), for a
  * test of the rule itself: 0 SceneList, 1 SceneQuads, 2 SceneRects, 3 SceneBvh, 4 SceneBvhG, 5 SceneRectsE, 6 SceneListE,

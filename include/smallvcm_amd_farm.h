@@ -34,6 +34,7 @@ typedef struct vcm_farm_config {
     int   collectives;               /* 0: RCCL; 1: in-process stand-in (tests on one GPU; single process only) */
     const void *uniqueIds;           /* NULL when localRanks == ranks; else (1 + ranks / shards) ids from vcm_farm_unique_ids */
     int   nUniqueIds;
+    vcm_pixel_filter filter;         /* the pixel filter of every renderer (kind VCM_FILTER_BOX, as zeroed: the reference's) */
 } vcm_farm_config;
 
 typedef struct vcm_farm_result {

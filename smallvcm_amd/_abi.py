@@ -127,6 +127,27 @@ class SceneDesc5(C.Structure):
         return self.base.base.base.camera
 
 
+FILTER_BOX, FILTER_TENT, FILTER_BSPLINE = 0, 1, 2
+PIXEL_FILTERS = {"box": FILTER_BOX, "tent": FILTER_TENT, "bspline": FILTER_BSPLINE}
+FILTER_MAX_RADIUS = 16.0
+
+
+class PixelFilter(C.Structure):
+    """vcm_pixel_filter: the pixel reconstruction filter (FILTER_BOX / _TENT / _BSPLINE) and the support of its offset
+    density in pixels (include/smallvcm_amd.h)"""
+    _fields_ = [("kind", C.c_int), ("radius", C.c_float)]
+
+
+class SceneDesc6(C.Structure):
+    """vcm_scene_desc6: a version-5 scene and an optional pixel filter.  Like SceneDesc2 the arrays are owned by the
+    Python object that built it."""
+    _fields_ = [("base", SceneDesc5), ("filter", C.POINTER(PixelFilter))]
+
+    @property
+    def camera(self):
+        return self.base.base.base.base.camera
+
+
 class DenoiseParams(C.Structure):
     """vcm_denoise_params: a-trous passes (0 .. 12), the three edge-stopping sigmas, and whether the albedo is divided
     out before the first pass and multiplied back after the last (include/smallvcm_amd.h)"""

@@ -25,6 +25,10 @@
 //                                                        with equal probability (the default) or by emitted power,
 //                                                        mixed with the share uniformMix in [0, 1] of the uniform
 //                                                        choice (vcm_light_pick, vcm_scene_desc5, vcm_scene_file_desc5)
+//       filter tent|bspline radius                       the pixel reconstruction filter, at most once: the support of
+//                                                        the offset density in pixels, finite, > 0 and <= 16, nothing
+//                                                        after it (vcm_pixel_filter, vcm_scene_desc6,
+//                                                        vcm_scene_file_desc6)
 //   .obj        v, f (triangles; polygons are fanned around their first vertex; v, v/vt, v/vt/vn, v//vn; negative
 //               = relative indices), usemtl, mtllib; everything else is skipped
 //   .mtl        newmtl, Kd -> mDiffuseReflectance, Ks + Ns -> mPhongReflectance / mPhongExponent (materials.hxx:54-65),
@@ -67,6 +71,9 @@ struct vcm_scene_file {
     bool havePick = false;            /* `lightpick` */
     vcm_light_pick pick;
     vcm_scene_desc5 desc5;
+    bool haveFilter = false;          /* `filter` */
+    vcm_pixel_filter filter;
+    vcm_scene_desc6 desc6;
     ~vcm_scene_file() { vcm_envmap_free(envmap); }
 };
 
@@ -448,6 +455,17 @@ struct Loader {
                 out->pick.mode = mode == "power" ? VCM_LIGHT_PICK_POWER : VCM_LIGHT_PICK_UNIFORM;
                 out->pick.uniformMix = mix; out->pick.weights = NULL;
                 out->havePick = true;
+            } else if (key == "filter") {
+                const std::string kind = word(p);
+                float x[1];
+                const bool got = (kind == "tent" || kind == "bspline") && floats(p, x, 1);
+                const std::string rest = got ? word(p) : std::string();
+                if (!got || (!rest.empty() && rest[0] != '#')) { ok = fail(at + ": filter tent|bspline radius"); break; }
+                if (out->haveFilter) { ok = fail(at + ": a second filter"); break; }
+                if (!std::isfinite(x[0]) || !(x[0] > 0.f) || x[0] > 16.f) { ok = fail(at + ": filter radius must be finite, > 0 and <= 16"); break; }
+                out->filter.kind = kind == "tent" ? VCM_FILTER_TENT : VCM_FILTER_BSPLINE;
+                out->filter.radius = x[0];
+                out->haveFilter = true;
             } else if (key == "light") {
                 const std::string kind = word(p);
                 vcm_light l;
@@ -496,6 +514,8 @@ struct Loader {
         out->desc4.lens = out->haveLens ? &out->lens : NULL;
         out->desc5.base = out->desc4;
         out->desc5.pick = out->havePick ? &out->pick : NULL;
+        out->desc6.base = out->desc5;
+        out->desc6.filter = out->haveFilter ? &out->filter : NULL;
         return true;
     }
 };
@@ -536,6 +556,7 @@ void vcm_scene_file_free(vcm_scene_file *s) { delete s; }
 const vcm_scene_desc3 *vcm_scene_file_desc3(const vcm_scene_file *s) { return s ? &s->desc3 : NULL; }
 const vcm_scene_desc4 *vcm_scene_file_desc4(const vcm_scene_file *s) { return s ? &s->desc4 : NULL; }
 const vcm_scene_desc5 *vcm_scene_file_desc5(const vcm_scene_file *s) { return s ? &s->desc5 : NULL; }
+const vcm_scene_desc6 *vcm_scene_file_desc6(const vcm_scene_file *s) { return s ? &s->desc6 : NULL; }
 
 vcm_envmap *vcm_envmap_load(const char *path)
 {

@@ -50,6 +50,9 @@ struct SceneHost {
     std::vector<int> envMargGuide, envCondGuide;
     /* the thin lens (scene_host_set_lens; lensRadius == 0: the pinhole), DScene::lensRadius ... */
     float lensRadius = 0.f, lensFocus = 1.f, lensRight[3] = { 0.f, 0.f, 0.f }, lensUp[3] = { 0.f, 0.f, 0.f };
+    /* the pixel filter (scene_host_set_filter; filterKind BOX: the reference's), DScene::filterKind ... */
+    int filterKind = VCM_FILTER_BOX;
+    float filterRadius = 0.f;
     /* how lights are chosen (scene_host_set_pick; pickMode UNIFORM: no tables), DScene::pickMode ...; pickWeights are
        the weights before the mix and pickQuanta the m_i of pmf[i] = m_i 2^-23 (for reports and tests) */
     int pickMode = VCM_LIGHT_PICK_UNIFORM, pickGuide = 0;
@@ -97,6 +100,7 @@ struct SceneHost {
         d.lensRadius = lensRadius; d.lensFocus = lensFocus;
         for (int k = 0; k < 3; k++) { d.lensRight[k] = lensRight[k]; d.lensUp[k] = lensUp[k]; }
         d.pickMode = pickMode; d.pickGuide = pickGuide;
+        d.filterKind = filterKind; d.filterRadius = filterRadius;
         { const char *e = getenv("SMALLVCM_AMD_NO_RECTS"); if (e && e[0] == '1') d.nFastRects[0] = d.nFastRects[1] = d.nFastRects[2] = 0; }   /* measurement switch */
     }
 };
@@ -404,6 +408,23 @@ inline bool scene_host_set_pick(SceneHost &s, const vcm_light_pick *pick, std::s
 inline bool scene_host_from_desc5(const vcm_scene_desc5 &sc, SceneHost &s, std::string &err)
 {
     return scene_host_from_desc4(sc.base, s, err) && scene_host_set_pick(s, sc.pick, err);
+}
+
+/* ---- the pixel filter (vcm_core.h filter_offset) ---- */
+inline bool scene_host_set_filter(SceneHost &s, const vcm_pixel_filter *filter, std::string &err)
+{
+    s.filterKind = VCM_FILTER_BOX; s.filterRadius = 0.f;
+    if (!filter || filter->kind == VCM_FILTER_BOX) return true;
+    if (filter->kind != VCM_FILTER_TENT && filter->kind != VCM_FILTER_BSPLINE) { err = "pixel filter: unknown kind"; return false; }
+    const float r = filter->radius;
+    if (!std::isfinite(r) || !(r > 0.f) || r > 16.f) { err = "pixel filter: radius must be finite, > 0 and <= 16 pixels"; return false; }
+    s.filterKind = filter->kind; s.filterRadius = r;
+    return true;
+}
+
+inline bool scene_host_from_desc6(const vcm_scene_desc6 &sc, SceneHost &s, std::string &err)
+{
+    return scene_host_from_desc5(sc.base, s, err) && scene_host_set_filter(s, sc.filter, err);
 }
 
 /* ---- brute-force list: consecutive triangles in pairs, fields interleaved (vcm_core.h TriPair) ---- */

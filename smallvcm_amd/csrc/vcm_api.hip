@@ -181,6 +181,7 @@ struct vcm_ctx : Scratch {
     SceneKind kind;                   /* the instantiation the ray-casting kernels are launched in (scene_kind.h); set by ensure_device */
     bool envMap;                      /* the scene's background is an environment map: the SceneRectsE / SceneListE / SceneBvhE kernels */
     bool lens;                        /* the camera is a thin lens: the WithLens kernels for the camera vertex */
+    bool filter;                      /* the scene has a pixel filter: the WithLens kernels too (vcm_core.h kLens) */
     bool pick;                        /* lights are chosen from a table: the WithPick kernels */
     bool intPhong;                    /* every Phong exponent in use is an integer in [1, 65536]: the kernels whose pow is the binary
                                          exponentiation alone (detmath.h); otherwise the SceneList / SceneBvhG kernels and the general merge */
@@ -210,7 +211,7 @@ struct vcm_ctx : Scratch {
 
 /* A ray-casting kernel is launched in the instantiation of the context's kind, under the wrappers it exists for (Wrap:
    scene_kind.h): f(tag) launches it with S = typename decltype(tag)::type.  What f evaluates, it evaluates once. */
-template <unsigned Wrap, class F> static void launch_kind(const vcm_ctx *c, F &&f) { with_scene_kind<Wrap>(c->kind, c->lens, c->pick, f); }
+template <unsigned Wrap, class F> static void launch_kind(const vcm_ctx *c, F &&f) { with_scene_kind<Wrap>(c->kind, c->lens || c->filter, c->pick, f); }
 
 /* K4 of a context: k_merge_pairs or k_merge_walk (VCM_MERGE_*), with the pow its exponents allow */
 typedef void (*MergeKernel)(const DScene *, IterParams, GridStore, VertexStore, const int *, const int *, unsigned long long *, int, StampArgs);
@@ -770,6 +771,7 @@ static vcm_ctx *create_from_host(SceneHost *h, int algorithm, float radiusFactor
     c->scene = h;
     c->envMap = h->envW > 0;
     c->lens = h->lensRadius > 0.f;
+    c->filter = h->filterKind != VCM_FILTER_BOX;
     c->pick = h->pickMode != VCM_LIGHT_PICK_UNIFORM;
     scene_host_build_accel(*h, scene_host_force_bvh());
     /* VertexCM::VertexCM vertexcm.hxx:222-244 */
@@ -874,6 +876,16 @@ vcm_ctx *vcm_create_sharded5(const vcm_scene_desc5 *scene, int algorithm, float 
     return create_from_host(h, algorithm, radiusFactor, radiusAlpha, seed, device, rank, worldSize);
 }
 
+vcm_ctx *vcm_create_sharded6(const vcm_scene_desc6 *scene, int algorithm, float radiusFactor, float radiusAlpha,
+                             int seed, int device, int rank, int worldSize)
+{
+    if (!scene) { fail("vcm_create6", "scene is NULL"); return NULL; }
+    SceneHost *h = new (std::nothrow) SceneHost();
+    std::string err;
+    if (!h || !scene_host_from_desc6(*scene, *h, err)) { delete h; fail("vcm_create6", err.c_str()); return NULL; }
+    return create_from_host(h, algorithm, radiusFactor, radiusAlpha, seed, device, rank, worldSize);
+}
+
 /* Which device a renderer-per-host-core host puts its next renderer on (vcm_next_device).  The reference's driver
  * builds one renderer per host core and runs them concurrently (smallvcm.cxx:61-72, :99-108): on a multi-GPU node the
  * drop-in deals them round-robin over the visible devices -- every GPU renders whole iterations of its renderers
@@ -932,6 +944,11 @@ vcm_ctx *vcm_create4(const vcm_scene_desc4 *scene, int algorithm, float radiusFa
 vcm_ctx *vcm_create5(const vcm_scene_desc5 *scene, int algorithm, float radiusFactor, float radiusAlpha, int seed)
 {
     return vcm_create_sharded5(scene, algorithm, radiusFactor, radiusAlpha, seed, next_device(true), 0, 1);
+}
+
+vcm_ctx *vcm_create6(const vcm_scene_desc6 *scene, int algorithm, float radiusFactor, float radiusAlpha, int seed)
+{
+    return vcm_create_sharded6(scene, algorithm, radiusFactor, radiusAlpha, seed, next_device(true), 0, 1);
 }
 
 void vcm_destroy(vcm_ctx *c)
@@ -3034,6 +3051,7 @@ int vcm_debug_numeric_spec(int op, int n, const float *a, const float *b, float 
 int vcm_debug_kat(vcm_ctx *c, int op, int n, const float *in, float *out)
 {
     if (!c || !in || !out || n < 0 || op < 0 || op >= VCM_KAT_OPS) return fail("vcm_debug_kat", "bad argument");
+    if (op == VCM_KAT_FILTER && !c->filter) return fail("vcm_debug_kat", "VCM_KAT_FILTER needs a context with a pixel filter (vcm_create6)");
     if (op == VCM_KAT_LENS && !c->lens) return fail("vcm_debug_kat", "VCM_KAT_LENS needs a context with a thin lens (vcm_create4)");
     if (ensure_device(c)) return -1;
     if (n == 0) return 0;
@@ -3069,6 +3087,14 @@ int vcm_debug_context_info(vcm_ctx *c, int *out)
     out[VCM_INFO_PRIMS] = (int)c->scene->prims.size();
     out[VCM_INFO_LIGHTS] = (int)c->scene->lights.size();
     out[VCM_INFO_MERGE_KERNEL] = c->lastMergeKernel;
+    return 0;
+}
+
+int vcm_debug_pixel_filter(vcm_ctx *c, int *kind, float *radius)
+{
+    if (!c) return fail("vcm_debug_pixel_filter", "bad argument");
+    if (kind) *kind = c->scene->filterKind;
+    if (radius) *radius = c->scene->filterRadius;
     return 0;
 }
 

@@ -394,6 +394,10 @@ struct DScene {
        and the guide of the cdf (pickGuide + 1 ints, pickGuide = the power of two >= nLights; env_search) */
     int pickMode, pickGuide;
     long long offPickPmf, offPickCdf, offPickGuide;
+    /* the pixel reconstruction filter (vcm_pixel_filter; filterKind == VCM_FILTER_BOX: the reference's box, no offset):
+       the kind of the offset density g and its support in pixels (filter_offset below) */
+    int filterKind;
+    float filterRadius;
     template <class T> VCM_HD const T *at(long long off) const { return reinterpret_cast<const T *>(reinterpret_cast<const char *>(this) + off); }
     VCM_HD const vcm_prim *prims() const { return at<vcm_prim>(offPrims); }
     VCM_HD const vcm_material *materials() const { return at<vcm_material>(offMaterials); }
@@ -449,17 +453,22 @@ struct SceneBvhE : DScene { static constexpr bool kBvh = true; static constexpr 
 #define VCM_ENV_KIND(S) true
 #endif
 
-/* kLens: the camera is a thin lens (DScene::lensRadius > 0).  Only the kernels that hold the camera vertex (strict K1,
-   K3, the path tracer, eye light, k_connect_camera) and the known-answer kernel exist in these kinds, one over each kind
-   above; a scene with a lens launches them there and every other kernel where it would without one.  The host builds
-   carry the lens branch in every kind and take it at run time. */
+/* kLens: the camera vertex is not the reference's -- a thin lens (DScene::lensRadius > 0), a pixel filter
+   (DScene::filterKind != VCM_FILTER_BOX), or both.  Only the kernels that hold the camera vertex (strict K1, K3, the path
+   tracer, eye light, k_connect_camera) and the known-answer kernel exist in these kinds, one over each kind above; a
+   scene with a lens or a filter launches them there and every other kernel where it would without one.  Inside them the
+   two features are branches on scene constants, the same for every lane of a launch: a filter costs no third set of
+   instantiations, and the kinds without the wrapper hold neither branch.  The host builds carry both branches in every
+   kind and take them at run time. */
 template <class S> struct WithLens : S { static constexpr bool kLens = true; };
 #if defined(__HIP_DEVICE_COMPILE__)
 #define VCM_LENS_KIND(S) (S::kLens)
-#define VCM_LENS_ON(S, sc) (S::kLens)
+#define VCM_LENS_ON(S, sc) (S::kLens && (sc).lensRadius > 0.f)
+#define VCM_FILTER_ON(S, sc) (S::kLens && (sc).filterKind != VCM_FILTER_BOX)
 #else
 #define VCM_LENS_KIND(S) true
 #define VCM_LENS_ON(S, sc) ((sc).lensRadius > 0.f)
+#define VCM_FILTER_ON(S, sc) ((sc).filterKind != VCM_FILTER_BOX)
 #endif
 
 /* kPick: lights are chosen from a table (DScene::pickMode != UNIFORM).  Only the kernels that choose a light or weigh
@@ -2327,12 +2336,71 @@ VCM_HD bool lens_project(const DScene &sc, V3 l, V3 x, V3 &raster)
     return true;
 }
 
+/* ---- the pixel filter (DESIGN.md "Pixel filter") ----
+ * Filter importance sampling on both sides of the image plane: a camera path keeps its jittered sample and its pixel
+ * and sends its ray through sample + o; a light vertex projects as before and is splatted to the pixel that holds
+ * projection + o, with o ~ g in both cases.  Both then measure a pixel with h = box * g, no splat carries a weight and
+ * no neighbour is written.  The first-hit guide images (vcm_denoise.h) stay unfiltered on purpose: the denoiser wants
+ * sharp guides.
+ * The draws come from streams of their own, beside the lens's: kind 4 = a camera path's offset (keyed by the global
+ * path, vertex 0), kind 5 = the offset of a light vertex's connection to the camera (keyed by the global light path
+ * and the vertex's pathLength, as kind 3 is).  A draw is up to 8 floats: Philox blocks 2 * vertex (r[0..3]) and, for the
+ * filters that read them, 2 * vertex + 1 (r[4..7]).  The eight floats travel as scalars: as an array behind a pointer
+ * they cost every kernel that holds them 16 bytes of scratch per lane. */
+struct FilterDraw { float r0, r1, r2, r3, r4, r5, r6, r7; };
+VCM_HD void filter_rnd(const IterParams &P, uint32_t kind, uint32_t path, uint32_t vertex, int filterKind, FilterDraw &d)
+{
+    uint32_t w0, w1, w2, w3;   /* PathRng's stream (philox.h): key = (seed, localIter), counter = (path, kind, block, 0) */
+    philox4x32_10(path, kind, vertex << 1, 0u, P.seed, P.localIter, w0, w1, w2, w3);
+    d.r0 = rng_word_to_float(w0); d.r1 = rng_word_to_float(w1); d.r2 = rng_word_to_float(w2); d.r3 = rng_word_to_float(w3);
+    d.r4 = d.r5 = d.r6 = d.r7 = 0.5f;
+    if (filterKind == VCM_FILTER_BSPLINE) {
+        philox4x32_10(path, kind, (vertex << 1) + 1u, 0u, P.seed, P.localIter, w0, w1, w2, w3);
+        d.r4 = rng_word_to_float(w0); d.r5 = rng_word_to_float(w1); d.r6 = rng_word_to_float(w2); d.r7 = rng_word_to_float(w3);
+    }
+}
+/* the offset of the eight floats of a draw, each in (0, 1): + - x only, so the host and the device agree bit for bit without
+   contraction.  TENT: radius (u1 - u2) per axis, the tent of half-width radius (variance radius^2 / 6).  BSPLINE:
+   radius (u1 + u2 + u3 + u4 - 2) / 2, the cubic B-spline on (-radius, radius) (variance radius^2 / 12).  |o| <= radius. */
+VCM_HD void filter_offset(int filterKind, float radius, const FilterDraw &d, float &ox, float &oy)
+{
+    ox = 0.f; oy = 0.f;
+    if (filterKind == VCM_FILTER_TENT) {
+        ox = radius * (d.r0 - d.r1);
+        oy = radius * (d.r2 - d.r3);
+    } else if (filterKind == VCM_FILTER_BSPLINE) {
+        ox = radius * ((((d.r0 + d.r1) + (d.r2 + d.r3)) - 2.f) * 0.5f);
+        oy = radius * ((((d.r4 + d.r5) + (d.r6 + d.r7)) - 2.f) * 0.5f);
+    }
+}
+/* the raster point a camera path's ray goes through: its sample moved by a kind-4 draw */
+VCM_HD void filter_camera_sample(const DScene &sc, const IterParams &P, int pathIdx, float &rx, float &ry)
+{
+    FilterDraw d;
+    float ox, oy;
+    filter_rnd(P, 4u, (uint32_t)pathIdx, 0u, sc.filterKind, d);
+    filter_offset(sc.filterKind, sc.filterRadius, d, ox, oy);
+    rx = rx + ox; ry = ry + oy;
+}
+/* the pixel a splat at raster point (x, y) goes to given the floats of a draw: the one that holds (x, y) + o, or -1 when
+   that point is outside the image (rejected, not folded back); the early-out is exact because |o| <= radius */
+VCM_HD int filter_splat_pixel(const DScene &sc, float x, float y, const FilterDraw &d, float &ox, float &oy)
+{
+    const vcm_camera &cam = sc.camera;
+    filter_offset(sc.filterKind, sc.filterRadius, d, ox, oy);
+    x = x + ox; y = y + oy;
+    if (!(x >= 0 && y >= 0 && x < cam.resolution[0] && y < cam.resolution[1])) return -1;
+    return int(x) + int(y) * (int)cam.resolution[0];
+}
+
 /* ConnectToCamera :862-933; the splat is an atomic add (Framebuffer::AddColor
  * framebuffer.hxx:43-57 on an arbitrary pixel) */
 /* splatOut == NULL: the splat is an fp32 atomic add on fb (strict mode);
  * otherwise *splatOut receives (contrib.rgb, pixel) -- pixel -1 when nothing is
  * splatted -- and k_splat_apply adds the splats of a pixel in vertex order. */
-/* lensPath: the global index of the light path (the lens kinds' kind-3 draw; unused without a lens).  With a lens the
+/* lensPath: the global index of the light path (the kind-3 draw of a lens and the kind-5 draw of a pixel filter; unused
+ * without either).  With a filter the splat goes to the pixel that holds the projection moved by a kind-5 offset, and
+ * nothing else changes: same contribution, same MIS weight; lightSplats counts what is splatted.  With a lens the
  * camera vertex is a lens point drawn per light vertex, and the rest is evaluated from it: the lens-area pdf of that
  * vertex is common to every strategy that holds it, so it enters no MIS weight, and it cancels the importance's. */
 template <class SC>
@@ -2353,7 +2421,16 @@ VCM_HD void connect_to_camera(const SC &sc, const IterParams &P, const SubPathSt
     V3 directionToCamera = camPos - hitpoint;
     if (dot(ld3(cam.forward), -directionToCamera) <= 0.f) return;
     if (!VCM_LENS_ON(SC, sc)) ip = transform_point(cam.worldToRaster, hitpoint);
-    if (!(ip.x >= 0 && ip.y >= 0 && ip.x < cam.resolution[0] && ip.y < cam.resolution[1])) return;
+    int filterPixel = 0;
+    if (VCM_FILTER_ON(SC, sc)) {
+        const float fr = sc.filterRadius;   /* no offset reaches the image from outside the image grown by the support */
+        if (!(ip.x >= -fr && ip.y >= -fr && ip.x < cam.resolution[0] + fr && ip.y < cam.resolution[1] + fr)) return;
+        FilterDraw d;
+        float ox, oy;
+        filter_rnd(P, 5u, (uint32_t)lensPath, st.pathLength, sc.filterKind, d);
+        filterPixel = filter_splat_pixel(sc, ip.x, ip.y, d, ox, oy);
+        if (filterPixel < 0) return;
+    } else if (!(ip.x >= 0 && ip.y >= 0 && ip.x < cam.resolution[0] && ip.y < cam.resolution[1])) return;
     const float distEye2 = lensqr(directionToCamera);
     const float distance = sqrtf(distEye2);
     directionToCamera = directionToCamera / distance;
@@ -2377,11 +2454,11 @@ VCM_HD void connect_to_camera(const SC &sc, const IterParams &P, const SubPathSt
         const bool occluded = scene_occluded(sc, hitpoint, directionToCamera, distance);
         RC_MARK(18);
         if (occluded) return;
-        const int x = int(ip.x), y = int(ip.y);
+        const int pixel = VCM_FILTER_ON(SC, sc) ? filterPixel : int(ip.x) + int(ip.y) * P.resX;
         if (splatOut) {
-            *splatOut = mk4(contrib.x, contrib.y, contrib.z, u2f((uint32_t)(x + y * P.resX)));
+            *splatOut = mk4(contrib.x, contrib.y, contrib.z, u2f((uint32_t)pixel));
         } else {
-            float *px = fb + (size_t)(x + y * P.resX) * 3;
+            float *px = fb + (size_t)pixel * 3;
             fb_atomic_add(px + 0, contrib.x);
             fb_atomic_add(px + 1, contrib.y);
             fb_atomic_add(px + 2, contrib.z);
@@ -2491,7 +2568,7 @@ VCM_HD void connect_stored_vertex_to_camera(const SC &sc, const IterParams &P, c
     Bsdf bsdf;
     bsdf_restore(bsdf, mk3(c.x, c.y, c.z), mk3(d.x, d.y, d.z), f2u(a.w) >> 8, sc);
     /* the slot is nStored * nLocal + lp (light_path_step): the light path is recoverable without a field of its own */
-    const int lensPath = VCM_LENS_ON(SC, sc) ? P.p0 + (int)(slot % (size_t)P.nLocal) : 0;
+    const int lensPath = (VCM_LENS_ON(SC, sc) || VCM_FILTER_ON(SC, sc)) ? P.p0 + (int)(slot % (size_t)P.nLocal) : 0;
     connect_to_camera(sc, P, st, mk3(a.x, a.y, a.z), bsdf, fb, ls, splatOut, lensPath);
 }
 
@@ -3032,7 +3109,9 @@ VCM_HD int wave_queue_take(int &base, int &left, int *counter, int blockSize, in
 
 /* GenerateCameraSample :564-606 (+ Camera::GenerateRay camera.hxx:108-117); with a lens the ray starts at a lens point
    (kind-2 draw) and cameraPdfW keeps its formula with cos = forward . dir: by similar triangles it is the same
-   per-pixel density */
+   per-pixel density.  With a pixel filter the ray goes through the sample moved by a kind-4 offset -- possibly outside
+   the pixel or the image: rasterToWorld is linear -- while (sx, sy), and so the path's pixel, stay the sample's; the
+   formulas of cameraPdfW and dVCM are evaluated with the actual direction. */
 template <class S>
 VCM_HD void camera_path_begin(const S &sc, const IterParams &P, CameraPath &cp, int localPath, const uint32_t *lightLenMask = 0)
 {
@@ -3052,7 +3131,9 @@ VCM_HD void camera_path_begin(const S &sc, const IterParams &P, CameraPath &cp, 
     const float jy = jit[1];
     cp.sx = float(x) + jx;
     cp.sy = float(y) + jy;
-    const V3 worldRaster = transform_point(cam.rasterToWorld, mk3(cp.sx, cp.sy, 0.f));
+    float rx = cp.sx, ry = cp.sy;
+    if (VCM_FILTER_ON(S, sc)) filter_camera_sample(sc, P, pathIdx, rx, ry);
+    const V3 worldRaster = transform_point(cam.rasterToWorld, mk3(rx, ry, 0.f));
     V3 org = ld3(cam.position);
     V3 dir = normalize(worldRaster - org);
     if (VCM_LENS_ON(S, sc)) {
@@ -3379,7 +3460,9 @@ VCM_HD void pt_path_begin(const S &sc, const IterParams &P, PtPath &pp, int loca
     pp.rng.k = 2u;
     pp.sx = float(pathIdx % P.resX) + jit[0];   /* :56-59 */
     pp.sy = float(pathIdx / P.resX) + jit[1];
-    const V3 worldRaster = transform_point(cam.rasterToWorld, mk3(pp.sx, pp.sy, 0.f));   /* camera.hxx:108-117 */
+    float rx = pp.sx, ry = pp.sy;
+    if (VCM_FILTER_ON(S, sc)) filter_camera_sample(sc, P, pathIdx, rx, ry);   /* the pixel filter: a kind-4 draw (camera_path_begin) */
+    const V3 worldRaster = transform_point(cam.rasterToWorld, mk3(rx, ry, 0.f));   /* camera.hxx:108-117 */
     pp.org = ld3(cam.position);
     pp.dir = normalize(worldRaster - pp.org);
     if (VCM_LENS_ON(S, sc)) {   /* the thin lens: a kind-2 draw (camera_path_begin) */
@@ -3505,7 +3588,9 @@ VCM_HD bool eyelight_path(const SC &sc, const IterParams &P, int localPath, V3 &
     sx = float(pathIdx % P.resX) + jit[0];
     sy = float(pathIdx / P.resX) + jit[1];
     Ray ray;
-    const V3 worldRaster = transform_point(cam.rasterToWorld, mk3(sx, sy, 0.f));
+    float rx = sx, ry = sy;
+    if (VCM_FILTER_ON(SC, sc)) filter_camera_sample(sc, P, pathIdx, rx, ry);   /* like the lens: in every iteration */
+    const V3 worldRaster = transform_point(cam.rasterToWorld, mk3(rx, ry, 0.f));
     ray.org = ld3(cam.position);
     ray.dir = normalize(worldRaster - ray.org);
     if (VCM_LENS_ON(SC, sc)) {   /* the thin lens draws its kind-2 sample in every iteration, the first included */

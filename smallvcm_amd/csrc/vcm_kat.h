@@ -110,6 +110,17 @@ VCM_HD void kat_eval(const SC &sc, int op, const float *in, float *out)
         const int asked = (int)in[1];
         out[2] = light_pick_prob(sc, asked < 0 ? 0 : asked, 1.f / lightCount);
     } break;
+    case VCM_KAT_FILTER:   /* the pixel filter: connect_to_camera's offset and pixel (vcm_core.h filter_splat_pixel); out[3], out[4]
+                              restate the moved point here, they are not read from the camera sites */
+        if constexpr (VCM_LENS_KIND(SC)) {
+            float ox, oy;
+            FilterDraw d;
+            d.r0 = in[2]; d.r1 = in[3]; d.r2 = in[4]; d.r3 = in[5]; d.r4 = in[6]; d.r5 = in[7]; d.r6 = in[8]; d.r7 = in[9];
+            const int pixel = filter_splat_pixel(sc, in[0], in[1], d, ox, oy);
+            out[0] = ox; out[1] = oy; out[2] = (float)pixel;
+            out[3] = in[0] + ox; out[4] = in[1] + oy;
+        }
+        break;
     default: break;
     }
 }

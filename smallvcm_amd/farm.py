@@ -12,7 +12,7 @@ import os
 
 import numpy as np
 
-from ._abi import SceneDesc, Stats
+from ._abi import PIXEL_FILTERS, PixelFilter, SceneDesc, Stats
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 FARM_LIB_PATH = os.environ.get("SMALLVCM_AMD_FARM_LIB") or os.path.join(_HERE, "host", "libsmallvcm_amd_farm.so")
@@ -24,7 +24,7 @@ class FarmConfig(C.Structure):
                 ("baseSeed", C.c_int), ("minLen", C.c_uint), ("maxLen", C.c_uint), ("iterations", C.c_int), ("warmup", C.c_int),
                 ("sameWindow", C.c_int), ("ranks", C.c_int), ("firstRank", C.c_int), ("localRanks", C.c_int),
                 ("devices", C.c_int * MAX_RANKS), ("shards", C.c_int), ("inflight", C.c_int), ("collectives", C.c_int),
-                ("uniqueIds", C.c_void_p), ("nUniqueIds", C.c_int)]
+                ("uniqueIds", C.c_void_p), ("nUniqueIds", C.c_int), ("filter", PixelFilter)]
 
 
 class FarmResult(C.Structure):
@@ -62,9 +62,10 @@ def unique_ids(n):
 
 def farm_render(scene, algorithm, iterations, ranks, shards, inflight, devices=None, first_rank=0, warmup=0, same_window=False,
                 collectives="rccl", ids=None, radius_factor=0.003, radius_alpha=0.75, seed=1234, min_len=0, max_len=10,
-                want_image=True):
+                want_image=True, pixel_filter=None):
     """-> dict(wall_s, renderers, rccl_ranks, rank_iteration_ms, stats, image).  `devices`: the HIP device of each rank
-    hosted by this process (default: all `ranks` ranks, device = rank)."""
+    hosted by this process (default: all `ranks` ranks, device = rank).  `pixel_filter`: (kind, radius) with kind "tent" or
+    "bspline" (include/smallvcm_amd.h vcm_pixel_filter) for every renderer; None: the reference's box."""
     L = load_farm_library()
     devices = list(range(ranks)) if devices is None else list(devices)
     cfg = FarmConfig()
@@ -75,6 +76,8 @@ def farm_render(scene, algorithm, iterations, ranks, shards, inflight, devices=N
     for i, d in enumerate(devices):
         cfg.devices[i] = d
     cfg.shards, cfg.inflight, cfg.collectives = shards, inflight, 0 if collectives == "rccl" else 1
+    if pixel_filter is not None:
+        cfg.filter = PixelFilter(PIXEL_FILTERS[pixel_filter[0]], float(pixel_filter[1]))
     keep = None
     if ids is not None:
         keep = C.create_string_buffer(ids, len(ids))

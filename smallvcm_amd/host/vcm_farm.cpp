@@ -675,8 +675,17 @@ bool rank_main(RankArgs &a)
     for (int k = 0; k < cfg.inflight; k++) {
         Slot &sl = slots[(size_t)k];
         const int rid = a.group * cfg.inflight + k;
-        sl.ctx = vcm_create_sharded(&cfg.scene, cfg.algorithm, cfg.radiusFactor, cfg.radiusAlpha, cfg.baseSeed + rid, a.device,
-                                    a.shard, cfg.shards);   // seed: smallvcm.cxx:68
+        if (cfg.filter.kind != VCM_FILTER_BOX) {   // a pixel filter: the same scene as a version-6 description (the arrays stay in cfg.scene)
+            vcm_scene_desc6 d6;
+            memset(&d6, 0, sizeof(d6));
+            vcm_scene_desc2 &b = d6.base.base.base.base;
+            scene_as_desc2(cfg.scene, b);
+            d6.filter = &cfg.filter;
+            sl.ctx = vcm_create_sharded6(&d6, cfg.algorithm, cfg.radiusFactor, cfg.radiusAlpha, cfg.baseSeed + rid, a.device,
+                                         a.shard, cfg.shards);
+        } else
+            sl.ctx = vcm_create_sharded(&cfg.scene, cfg.algorithm, cfg.radiusFactor, cfg.radiusAlpha, cfg.baseSeed + rid, a.device,
+                                        a.shard, cfg.shards);   // seed: smallvcm.cxx:68
         if (!sl.ctx) { sh.fail(std::string("vcm_create_sharded: ") + vcm_last_error()); return false; }
         HIPOK(hipStreamCreateWithFlags(&sl.stream, hipStreamNonBlocking));
         sl.commStream = commStream;
@@ -899,6 +908,7 @@ int vcm_farm_render(const vcm_farm_config *c, vcm_farm_result *out, float *image
     fc.sameWindow = c->sameWindow != 0; fc.ranks = c->ranks; fc.firstRank = c->firstRank; fc.localRanks = c->localRanks;
     fc.devices.assign(c->devices, c->devices + c->localRanks);
     fc.shards = c->shards; fc.inflight = c->inflight; fc.rccl = c->collectives == 0;
+    fc.filter = c->filter;
     if (c->uniqueIds && c->nUniqueIds > 0)
         fc.uniqueIds.assign((const char *)c->uniqueIds, (const char *)c->uniqueIds + (size_t)c->nUniqueIds * sizeof(ncclUniqueId));
     const FarmResult r = farm_render(fc);

@@ -37,11 +37,25 @@
 #ifndef SMALLVCM_AMD_VCM_FARM_HPP
 #define SMALLVCM_AMD_VCM_FARM_HPP
 
+#include <cstring>
 #include <string>
 #include <vector>
 
 #include "smallvcm_amd.h"
 #include "smallvcm_amd_farm.h"
+
+// A version-1 scene (fixed arrays) as a version-2 description: counts and pointers into `scene`, which has to outlive
+// `out`.  What the later descriptions (env map, lens, light selection, pixel filter) are stacked on.
+inline void scene_as_desc2(const vcm_scene_desc &scene, vcm_scene_desc2 &out)
+{
+    out.nPrims = scene.nPrims; out.prims = scene.prims;
+    out.nMaterials = scene.nMaterials; out.materials = scene.materials; out.mat2light = scene.mat2light;
+    out.nLights = scene.nLights; out.lights = scene.lights;
+    out.backgroundLight = scene.backgroundLight;
+    memcpy(out.sceneCenter, scene.sceneCenter, sizeof(out.sceneCenter));
+    out.sceneRadius = scene.sceneRadius; out.invSceneRadiusSqr = scene.invSceneRadiusSqr;
+    out.camera = scene.camera;
+}
 
 struct FarmConfig {
     vcm_scene_desc scene;
@@ -63,6 +77,7 @@ struct FarmConfig {
     //        warmup .. warmup + n - 1 (the radius window bench.py times at one GPU), warm-up = indices 0..warmup-1.
     bool sameWindow;
     std::vector<char> uniqueIds;   // empty: all ranks are local; else (1 + groups) ids of vcm_farm_unique_id_bytes() each
+    vcm_pixel_filter filter = { VCM_FILTER_BOX, 0.f };   // the pixel filter of every renderer (vcm_create_sharded6); BOX: vcm_create_sharded
 };
 
 struct FarmResult {

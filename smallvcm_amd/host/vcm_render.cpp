@@ -12,6 +12,7 @@
 //              [--device D] [--strict] [--warmup W] [-o out.pfm] [--json] [--scene-file f.vcmscene|f.obj]
 //              [--envmap f.hdr|f.pfm [--envmap-scale S]] [--aperture R --focus D]
 //              [--light-pick uniform|power [--light-pick-mix A] [--light-pick-report]]
+//              [--filter tent|bspline R]
 //              [--denoise [passes]] [--denoise-sigma c,n,z] [--no-demodulate] [--features-out prefix]
 //              [--noise-target E [--check-every N] [--max-iterations M]] [--track-variance] [--robust [M]]
 //              [--parts prefix]
@@ -33,6 +34,11 @@
 // equal probability (the default) or by emitted power, --light-pick-mix A in [0, 1] of the uniform choice mixed in; they
 // override a scene file's `lightpick` directive.  The mode in effect is printed when it is not the default, and with
 // --light-pick-report the five most probable lights and their probabilities.
+//
+// --filter tent|bspline R: the pixel reconstruction filter (vcm_pixel_filter, vcm_scene_desc6) in place of the reference's
+// box: filter importance sampling with an offset density of support R pixels (finite, 0 < R <= 16) on the camera side
+// and on the light splats; it overrides a scene file's `filter` directive, and with --gpus every renderer of the farm
+// takes it.  The guide images of --features-out stay unfiltered.
 //
 // --denoise [passes]: the image goes through the edge-avoiding a-trous filter (vcm_denoise: vcm_denoise_defaults with
 // `passes`, --denoise-sigma's sigmaColor,sigmaNormal,sigmaDepth and --no-demodulate applied) before it is written to
@@ -117,6 +123,8 @@ int main(int argc, char **argv)
     std::string pickName;
     float pickMix = 0.f;
     bool havePickMix = false, pickReport = false;
+    std::string filterName;
+    float filterRadius = 0.f;
     bool denoise = false;
     vcm_denoise_params dn;
     vcm_denoise_defaults(&dn);
@@ -169,6 +177,13 @@ int main(int argc, char **argv)
             havePickMix = true;
         }
         else if (a == "--light-pick-report") pickReport = true;
+        else if (a == "--filter") {
+            need(2);
+            filterName = argv[++i];
+            char *e = NULL;
+            filterRadius = strtof(argv[++i], &e);
+            if ((filterName != "tent" && filterName != "bspline") || e == argv[i] || *e) { fprintf(stderr, "vcm_render: --filter tent|bspline R\n"); return 2; }
+        }
         else if (a == "--denoise") {
             denoise = true;
             if (i + 1 < argc && argv[i + 1][0] >= '0' && argv[i + 1][0] <= '9') dn.passes = atoi(argv[++i]);
@@ -261,13 +276,8 @@ int main(int argc, char **argv)
         vcm_make_envmap_light(envScale, &envLights[(size_t)scene.backgroundLight]);
         memset(&envDesc, 0, sizeof(envDesc));
         vcm_scene_desc2 &b = envDesc.base;
-        b.nPrims = scene.nPrims; b.prims = scene.prims;
-        b.nMaterials = scene.nMaterials; b.materials = scene.materials; b.mat2light = scene.mat2light;
-        b.nLights = scene.nLights; b.lights = envLights.data();
-        b.backgroundLight = scene.backgroundLight;
-        memcpy(b.sceneCenter, scene.sceneCenter, sizeof(b.sceneCenter));
-        b.sceneRadius = scene.sceneRadius; b.invSceneRadiusSqr = scene.invSceneRadiusSqr;
-        b.camera = scene.camera;
+        scene_as_desc2(scene, b);
+        b.lights = envLights.data();
         envDesc.envmap = envmap;
         envScene = &envDesc;
     }
@@ -282,16 +292,7 @@ int main(int argc, char **argv)
         memset(&lensDesc, 0, sizeof(lensDesc));
         if (envScene) lensDesc.base = *envScene;
         else if (loaded) lensDesc.base = *vcm_scene_file_desc3(loaded);
-        else {   // the built-in scene as a version-2 description (the arrays stay in `scene`)
-            vcm_scene_desc2 &b = lensDesc.base.base;
-            b.nPrims = scene.nPrims; b.prims = scene.prims;
-            b.nMaterials = scene.nMaterials; b.materials = scene.materials; b.mat2light = scene.mat2light;
-            b.nLights = scene.nLights; b.lights = scene.lights;
-            b.backgroundLight = scene.backgroundLight;
-            memcpy(b.sceneCenter, scene.sceneCenter, sizeof(b.sceneCenter));
-            b.sceneRadius = scene.sceneRadius; b.invSceneRadiusSqr = scene.invSceneRadiusSqr;
-            b.camera = scene.camera;
-        }
+        else scene_as_desc2(scene, lensDesc.base.base);   // the built-in scene (the arrays stay in `scene`)
         lensDesc.lens = lens;
         lensScene = &lensDesc;
     }
@@ -310,23 +311,32 @@ int main(int argc, char **argv)
         else {
             if (envScene) pickDesc.base.base = *envScene;
             else if (loaded) pickDesc.base.base = *vcm_scene_file_desc3(loaded);
-            else {   // the built-in scene as a version-2 description (the arrays stay in `scene`)
-                vcm_scene_desc2 &b = pickDesc.base.base.base;
-                b.nPrims = scene.nPrims; b.prims = scene.prims;
-                b.nMaterials = scene.nMaterials; b.materials = scene.materials; b.mat2light = scene.mat2light;
-                b.nLights = scene.nLights; b.lights = scene.lights;
-                b.backgroundLight = scene.backgroundLight;
-                memcpy(b.sceneCenter, scene.sceneCenter, sizeof(b.sceneCenter));
-                b.sceneRadius = scene.sceneRadius; b.invSceneRadiusSqr = scene.invSceneRadiusSqr;
-                b.camera = scene.camera;
-            }
+            else scene_as_desc2(scene, pickDesc.base.base.base);   // the built-in scene (the arrays stay in `scene`)
             pickDesc.base.lens = NULL;
         }
         pickDesc.pick = pick;
         pickScene = &pickDesc;
     }
+    // the pixel filter (--filter, else a scene file's `filter`): the scene as a version-6 description
+    vcm_pixel_filter flagFilter;
+    flagFilter.kind = filterName == "tent" ? VCM_FILTER_TENT : VCM_FILTER_BSPLINE;
+    flagFilter.radius = filterRadius;
+    const vcm_pixel_filter *filter = !filterName.empty() ? &flagFilter : loaded ? vcm_scene_file_desc6(loaded)->filter : NULL;
+    vcm_scene_desc6 filterDesc;
+    const vcm_scene_desc6 *filterScene = NULL;
+    if (filter && gpus <= 0) {
+        memset(&filterDesc, 0, sizeof(filterDesc));
+        if (pickScene) filterDesc.base = *pickScene;
+        else if (lensScene) filterDesc.base.base = *lensScene;
+        else if (envScene) filterDesc.base.base.base = *envScene;
+        else if (loaded) filterDesc.base.base.base = *vcm_scene_file_desc3(loaded);
+        else scene_as_desc2(scene, filterDesc.base.base.base.base);   // the built-in scene (the arrays stay in `scene`)
+        filterDesc.filter = filter;
+        filterScene = &filterDesc;
+    }
     auto create = [&](int s) {
-        return pickScene ? vcm_create_sharded5(pickScene, algorithm, radiusFactor, radiusAlpha, s, device, 0, 1)
+        return filterScene ? vcm_create_sharded6(filterScene, algorithm, radiusFactor, radiusAlpha, s, device, 0, 1)
+             : pickScene ? vcm_create_sharded5(pickScene, algorithm, radiusFactor, radiusAlpha, s, device, 0, 1)
              : lensScene ? vcm_create_sharded4(lensScene, algorithm, radiusFactor, radiusAlpha, s, device, 0, 1)
              : envScene ? vcm_create_sharded3(envScene, algorithm, radiusFactor, radiusAlpha, s, device, 0, 1)
              : loaded ? vcm_create_sharded2(vcm_scene_file_desc(loaded), algorithm, radiusFactor, radiusAlpha, s, device, 0, 1)
@@ -348,6 +358,7 @@ int main(int argc, char **argv)
         fc.rccl = rccl != 0; fc.warmup = warmup;
         fc.firstRank = 0; fc.localRanks = gpus;   // every rank is a thread of this process
         fc.sameWindow = sameWindow != 0;
+        if (filter) fc.filter = *filter;
         const int visible = vcm_device_count();
         if (visible <= 0) { fprintf(stderr, "vcm_render: no HIP device available (this program has no CPU path)\n"); return 2; }
         for (int k = 0; k < gpus; k++) fc.devices.push_back(k < (int)devices.size() ? devices[(size_t)k] : (fc.rccl ? k : k % visible));

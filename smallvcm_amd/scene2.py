@@ -15,8 +15,8 @@ import math
 
 import numpy as np
 
-from ._abi import (Camera, EnvMap, Light, LightPick, Material, Prim, SceneDesc2, SceneDesc3, SceneDesc4, SceneDesc5, ThinLens,
-                   LIGHT_PICK_CUSTOM, LIGHT_PICK_MODES)
+from ._abi import (Camera, EnvMap, Light, LightPick, Material, Prim, SceneDesc2, SceneDesc3, SceneDesc4, SceneDesc5, SceneDesc6, ThinLens,
+                   PixelFilter, FILTER_BOX, FILTER_MAX_RADIUS, LIGHT_PICK_CUSTOM, LIGHT_PICK_MODES, PIXEL_FILTERS)
 
 
 def _f3(v):
@@ -53,6 +53,7 @@ class SceneBuilder:
         self.envmap = None
         self.lens = None
         self.pick = None
+        self.filter = None
 
     # ---- materials (materials.hxx:33-65) ----
     def material(self, diffuse=(0, 0, 0), phong=(0, 0, 0), exponent=1.0, mirror=(0, 0, 0), ior=-1.0):
@@ -150,6 +151,18 @@ class SceneBuilder:
             raise ValueError("light_pick: weights go with mode 'custom'")
         self.pick = (LIGHT_PICK_MODES[mode], a, w)
 
+    # ---- the pixel filter ----
+    def pixel_filter(self, kind, radius=0.0):
+        """the pixel reconstruction filter (include/smallvcm_amd.h vcm_pixel_filter): "box" (the reference's), "tent" or
+        "bspline" with the support `radius` of its offset density in pixels, finite, > 0 and <= 16.  build() then
+        returns a SceneDesc6."""
+        if kind not in PIXEL_FILTERS:
+            raise ValueError("pixel_filter: kind must be 'box', 'tent' or 'bspline'")
+        r = float(radius)
+        if PIXEL_FILTERS[kind] != FILTER_BOX and not (math.isfinite(r) and 0.0 < r <= FILTER_MAX_RADIUS):
+            raise ValueError("pixel_filter: radius must be finite, > 0 and <= %g pixels" % FILTER_MAX_RADIUS)
+        self.filter = (PIXEL_FILTERS[kind], r)
+
     # ---- the description ----
     def build(self, position, forward, up, fov_deg, resx, resy):
         d = SceneDesc2()
@@ -167,7 +180,7 @@ class SceneBuilder:
         if self.L.vcm_make_camera(_f3(position), _f3(forward), _f3(up), float(fov_deg), int(resx), int(resy), C.byref(d.camera)) != 0:
             raise ValueError("bad camera")
         d._keep = (prims, mats, m2l, lights)   # the arrays live as long as the description
-        if self.envmap is None and self.lens is None and self.pick is None:
+        if self.envmap is None and self.lens is None and self.pick is None and self.filter is None:
             return d
         d3 = SceneDesc3()
         d3.base = d
@@ -178,7 +191,7 @@ class SceneBuilder:
             m.rgb = self.envmap.ctypes.data_as(C.POINTER(C.c_float))
             d3.envmap = C.pointer(m)
             d3._keep = (d._keep, self.envmap, m)
-        if self.lens is None and self.pick is None:
+        if self.lens is None and self.pick is None and self.filter is None:
             return d3
         d4 = SceneDesc4()
         d4.base = d3
@@ -187,14 +200,23 @@ class SceneBuilder:
             lens = ThinLens(*self.lens)
             d4.lens = C.pointer(lens)
             d4._keep = (d3._keep, lens)
-        if self.pick is None:
+        if self.pick is None and self.filter is None:
             return d4
-        mode, mix, w = self.pick
-        if w is not None and len(w) != len(self.lights):
-            raise ValueError("light_pick: %d weights for %d lights" % (len(w), len(self.lights)))
         d5 = SceneDesc5()
         d5.base = d4
-        pick = LightPick(mode, mix, w.ctypes.data_as(C.POINTER(C.c_float)) if w is not None else None)
-        d5.pick = C.pointer(pick)
-        d5._keep = (d4._keep, pick, w)
-        return d5
+        d5._keep = (d4._keep,)
+        if self.pick is not None:
+            mode, mix, w = self.pick
+            if w is not None and len(w) != len(self.lights):
+                raise ValueError("light_pick: %d weights for %d lights" % (len(w), len(self.lights)))
+            pick = LightPick(mode, mix, w.ctypes.data_as(C.POINTER(C.c_float)) if w is not None else None)
+            d5.pick = C.pointer(pick)
+            d5._keep = (d4._keep, pick, w)
+        if self.filter is None:
+            return d5
+        d6 = SceneDesc6()
+        d6.base = d5
+        flt = PixelFilter(*self.filter)
+        d6.filter = C.pointer(flt)
+        d6._keep = (d5._keep, flt)
+        return d6
