@@ -60,7 +60,9 @@ enum {
     VCM_LIGHT_DIRECTIONAL = 1, /* src/lights.hxx:236 */
     VCM_LIGHT_POINT = 2,       /* src/lights.hxx:320 */
     VCM_LIGHT_BACKGROUND = 3,  /* src/lights.hxx:401 */
-    VCM_LIGHT_ENVMAP = 4       /* an image around the scene (vcm_scene_desc3; DESIGN.md "Environment map") */
+    VCM_LIGHT_ENVMAP = 4,      /* an image around the scene (vcm_scene_desc3; DESIGN.md "Environment map") */
+    VCM_LIGHT_SPOT = 5,        /* a point light with a cone (DESIGN.md "Spot and sphere lights") */
+    VCM_LIGHT_SPHERE = 6       /* an emissive sphere primitive (same section) */
 };
 
 /* Tagged union of the public light fields (src/lights.hxx:229-232, 314-315,
@@ -69,7 +71,14 @@ enum {
  *   directional: frame, intensity
  *   point:       p0 = mPosition, intensity
  *   background:  intensity = mBackgroundColor, scale = mScale
- *   envmap:      scale (the radiance is texel * scale; the image comes with vcm_scene_desc3) */
+ *   envmap:      scale (the radiance is texel * scale; the image comes with vcm_scene_desc3)
+ *   spot:        p0 = position, frame (mZ = the axis, built as the directional light's), intensity = radiant intensity on
+ *                the axis, e1 = { cos(outer half-angle), cos(inner half-angle), 1 / (cosInner - cosOuter) or 0 for a hard
+ *                edge }, scale = the cone's pdf 1 / (2 pi (1 - cosOuter)).  Falloff for c = dot(axis, direction from the
+ *                light): 0 for c < cosOuter, else t^2 (3 - 2 t) with t = clamp((c - cosOuter) e1[2], 0, 1); 1 inside a
+ *                hard-edged cone
+ *   sphere:      p0 = centre, e1[0] = radius, intensity = emitted radiance (outward only), invArea = 1 / (4 pi r^2).  It
+ *                belongs to ONE sphere primitive of the same centre and radius, whose material maps to it (mat2light) */
 typedef struct vcm_light {
     int   type;
     float p0[3];
@@ -167,7 +176,9 @@ typedef struct vcm_scene_desc4 {
 /* How a light is chosen where a path samples one (DESIGN.md "Light selection").  UNIFORM: every light with probability
  * 1 / nLights, as the reference does.  POWER: in proportion to the flux the light emits (area: pi lum(intensity) area;
  * point: 4 pi lum; directional: pi R^2 lum; background: 4 pi^2 R^2 lum scale; environment map: pi R^2 x the integral of
- * lum(texel scale) over the sphere; lum = the reference's Luminance, R = the scene sphere's radius).  CUSTOM: in proportion
+ * lum(texel scale) over the sphere; spot: 2 pi lum ((1 - cosInner) + (cosInner - cosOuter) / 2); sphere: pi lum x 4 pi r^2;
+ * lum = the reference's Luminance, R = the scene sphere's radius).  A scene with a spot or a sphere light always chooses
+ * through a table: UNIFORM, or no vcm_light_pick at all, then means equal weights (DESIGN.md "Spot and sphere lights").  CUSTOM: in proportion
  * to `weights` (nLights floats, finite, >= 0, not all zero; a zero weight is accepted only for a light that emits
  * nothing).  uniformMix a in [0, 1] blends the normalised weights with the uniform choice over the lights of non-zero
  * weight: w_i <- (1 - a) w_i / sum w + a / n'.  The probabilities are whole multiples of 2^-23 that sum to 1, at least one
@@ -519,6 +530,9 @@ unsigned vcm_scene_config_mask(int sceneID);
  *   vcm_make_directional_light DirectionalLight          lights.hxx:239-243    (frame)
  *   vcm_make_point_light       PointLight                lights.hxx:324-328
  *   vcm_make_background_light  BackgroundLight           lights.hxx:404-408    (the reference's sky colour)
+ *   vcm_make_spot_light        (no counterpart)          direction need not be normalised; half-angles in degrees,
+ *                                                        0 < outerDeg <= 180, 0 <= innerDeg <= outerDeg
+ *   vcm_make_sphere_light      (no counterpart)          goes with a vcm_make_sphere primitive of the same centre and radius
  *   vcm_make_material          Material::Reset           materials.hxx:44-51   (black, exponent 1, no refraction)
  *   vcm_make_camera            Camera::Setup             camera.hxx:37-76
  *   vcm_make_scene_sphere      Scene::BuildSceneSphere   scene.hxx:387-398
@@ -532,6 +546,9 @@ void vcm_make_point_light(const float *position, const float *intensity, vcm_lig
 void vcm_make_background_light(float scale, vcm_light *out);
 /* the light of a vcm_scene_desc3's environment map (radiance = texel * scale); it must be the scene's backgroundLight */
 void vcm_make_envmap_light(float scale, vcm_light *out);
+void vcm_make_spot_light(const float *position, const float *direction, const float *intensity, float outerDeg, float innerDeg,
+                         vcm_light *out);
+void vcm_make_sphere_light(const float *center, float radius, const float *intensity, vcm_light *out);
 void vcm_make_material(vcm_material *out);
 int  vcm_make_camera(const float *position, const float *forward, const float *up, float horizontalFovDeg, int resX, int resY,
                      vcm_camera *out);

@@ -67,7 +67,11 @@ enum {
                                      splat goes to (-1: outside the image), and the moved point (x, y) + offset, added in the
                                      record itself, for reading the pixel; needs a context with a pixel filter (vcm_create6)
                                                                                                   DESIGN.md "Pixel filter" */
-    VCM_KAT_OPS = 11
+    VCM_KAT_LIGHT_RADIANCE_AT = 11, /* in: light, rayDir, the normal at the hit -> radiance, directPdfA, emissionPdfW: the emitter
+                                     hit as the render path asks it (a sphere light needs the normal; every other type
+                                     answers as VCM_KAT_LIGHT_RADIANCE does); needs a context with a spot or a sphere light
+                                                                                     DESIGN.md "Spot and sphere lights" */
+    VCM_KAT_OPS = 12
 };
 int vcm_debug_kat(vcm_ctx *ctx, int op, int n, const float *in, float *out);
 
@@ -83,6 +87,10 @@ enum {
     VCM_INFO_COUNT = 11
 };
 int vcm_debug_context_info(vcm_ctx *ctx, int *out);
+
+/* 1: the context launches the WithLights kinds (its scene holds a spot or a sphere light; VCM_INFO_PICK is then 1 too,
+ * whatever the caller asked for); 0: it launches exactly the kernels it launched before there were such lights. */
+int vcm_debug_lights_kind(vcm_ctx *ctx);
 
 /* The pixel filter of a context as its kernels see it (vcm_pixel_filter; kind VCM_FILTER_BOX: none, the context launches
  * exactly the kernels of vcm_create5).  A filter without a lens launches the WithLens kinds, so VCM_INFO_LENS -- which

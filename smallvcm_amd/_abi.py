@@ -13,6 +13,9 @@ VCM_MERGE_RECORD_FLOATS = 13
 PRIM_TRIANGLE, PRIM_SPHERE = 0, 1
 LIGHT_AREA, LIGHT_DIRECTIONAL, LIGHT_POINT, LIGHT_BACKGROUND = 0, 1, 2, 3
 LIGHT_ENVMAP = 4
+LIGHT_SPOT, LIGHT_SPHERE = 5, 6
+LIGHT_TYPE_NAMES = {LIGHT_AREA: "area", LIGHT_DIRECTIONAL: "directional", LIGHT_POINT: "point", LIGHT_BACKGROUND: "background",
+                    LIGHT_ENVMAP: "envmap", LIGHT_SPOT: "spot", LIGHT_SPHERE: "sphere"}
 
 # VertexCM::AlgorithmType (reference src/vertexcm.hxx:182-204)
 ALGO_LIGHT_TRACE, ALGO_PPM, ALGO_BPM, ALGO_BPT, ALGO_VCM = 0, 1, 2, 3, 4

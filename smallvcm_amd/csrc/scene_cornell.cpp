@@ -406,6 +406,29 @@ extern "C" void vcm_make_envmap_light(float scale, vcm_light *out)
     put3(out->intensity, sp3(1.f));
     out->scale = scale;
 }
+extern "C" void vcm_make_spot_light(const float *position, const float *direction, const float *intensity, float outerDeg,
+                                    float innerDeg, vcm_light *out)
+{   /* the cosines and the cone's pdf are rounded once, from binary64; scene_host.h refuses what is out of range */
+    memset(out, 0, sizeof(*out));
+    out->type = VCM_LIGHT_SPOT;
+    put3(out->p0, ld3(position));
+    Frame f; frame_from_z(f, ld3(direction));
+    put3(out->frameX, f.mX); put3(out->frameY, f.mY); put3(out->frameZ, f.mZ);
+    put3(out->intensity, ld3(intensity));
+    const double rad = 3.14159265358979323846 / 180.0;
+    const float cosOuter = (float)cos((double)outerDeg * rad), cosInner = (float)cos((double)innerDeg * rad);
+    out->e1[0] = cosOuter; out->e1[1] = cosInner;
+    out->e1[2] = cosInner > cosOuter ? (float)(1.0 / ((double)cosInner - (double)cosOuter)) : 0.f;
+    out->scale = (float)(1.0 / (2.0 * 3.14159265358979323846 * (1.0 - (double)cosOuter)));
+}
+extern "C" void vcm_make_sphere_light(const float *center, float radius, const float *intensity, vcm_light *out)
+{
+    memset(out, 0, sizeof(*out));
+    out->type = VCM_LIGHT_SPHERE;
+    put3(out->p0, ld3(center)); out->e1[0] = radius;
+    put3(out->intensity, ld3(intensity));
+    out->invArea = (float)(1.0 / (4.0 * 3.14159265358979323846 * (double)radius * (double)radius));
+}
 extern "C" void vcm_make_material(vcm_material *out)
 {   /* Material::Reset materials.hxx:44-51 */
     reset_material(*out);

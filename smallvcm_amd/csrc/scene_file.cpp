@@ -15,6 +15,12 @@
 //       camera px py pz  fx fy fz  ux uy uz  hfovDeg     Camera::Setup (camera.hxx:37-76)
 //       light point px py pz  r g b                      PointLight (lights.hxx:324-328)
 //       light directional dx dy dz  r g b                DirectionalLight (lights.hxx:239-243)
+//       light spot px py pz  dx dy dz  r g b  outerDeg innerDeg
+//                                                        a point light with a cone around (dx, dy, dz): r g b on the axis,
+//                                                        full inside the half-angle innerDeg, smoothly to zero at outerDeg
+//                                                        (0 < outerDeg <= 180, 0 <= innerDeg <= outerDeg; equal: a hard edge)
+//       light sphere cx cy cz radius  r g b              a sphere that emits the radiance r g b outwards: the sphere
+//                                                        primitive, a black material of its own and its light
 //       light background scale                           BackgroundLight (lights.hxx:404-408)
 //       light envmap <file.hdr|file.pfm> scale           an environment map as the background (vcm_scene_desc3,
 //                                                        vcm_scene_file_desc3; the image: vcm_envmap_load below)
@@ -469,8 +475,25 @@ struct Loader {
             } else if (key == "light") {
                 const std::string kind = word(p);
                 vcm_light l;
-                float x[6];
-                if (kind == "point" && floats(p, x, 6)) vcm_make_point_light(x, x + 3, &l);
+                float x[11];
+                if (kind == "spot") {
+                    if (!floats(p, x, 11)) { ok = fail(at + ": light spot px py pz dx dy dz r g b outerDeg innerDeg"); break; }
+                    if (!std::isfinite(x[9]) || !(x[9] > 0.f) || x[9] > 180.f) { ok = fail(at + ": light spot outerDeg must be finite, > 0 and <= 180"); break; }
+                    if (!std::isfinite(x[10]) || x[10] < 0.f || x[10] > x[9]) { ok = fail(at + ": light spot innerDeg must be finite, >= 0 and <= outerDeg"); break; }
+                    vcm_make_spot_light(x, x + 3, x + 6, x[9], x[10], &l);
+                } else if (kind == "sphere") {
+                    if (!floats(p, x, 7)) { ok = fail(at + ": light sphere cx cy cz radius r g b"); break; }
+                    if (!std::isfinite(x[3]) || !(x[3] > 0.f)) { ok = fail(at + ": light sphere radius must be finite and > 0"); break; }
+                    vcm_material m;   // its own black material, mat2light -> the light, as an emissive triangle's
+                    vcm_make_material(&m);
+                    vcm_make_sphere_light(x, x[3], x + 4, &l);
+                    vcm_prim s;
+                    vcm_make_sphere(x, x[3], (int)out->materials.size(), &s);
+                    out->materials.push_back(m);
+                    out->mat2light.push_back((int)out->lights.size());
+                    out->prims.push_back(s);
+                }
+                else if (kind == "point" && floats(p, x, 6)) vcm_make_point_light(x, x + 3, &l);
                 else if (kind == "directional" && floats(p, x, 6)) vcm_make_directional_light(x, x + 3, &l);
                 else if (kind == "background" && floats(p, x, 1)) { vcm_make_background_light(x[0], &l); background = (int)out->lights.size(); }
                 else if (kind == "envmap") {
@@ -482,7 +505,7 @@ struct Loader {
                     vcm_make_envmap_light(x[0], &l);
                     background = (int)out->lights.size();
                 }
-                else { ok = fail(at + ": light point|directional x y z r g b, light background scale, or light envmap file scale"); break; }
+                else { ok = fail(at + ": light point|directional x y z r g b, light spot px py pz dx dy dz r g b outerDeg innerDeg, light sphere cx cy cz radius r g b, light background scale, or light envmap file scale"); break; }
                 out->lights.push_back(l);
             } else ok = fail(at + ": unknown directive " + key);
         }

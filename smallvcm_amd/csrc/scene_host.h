@@ -105,6 +105,54 @@ struct SceneHost {
     }
 };
 
+/* does the scene hold a light of the types only the WithLights kernels know (vcm_core.h)? */
+inline bool scene_host_has_new_lights(const SceneHost &s)
+{
+    for (const vcm_light &l : s.lights) if (l.type == VCM_LIGHT_SPOT || l.type == VCM_LIGHT_SPHERE) return true;
+    return false;
+}
+
+inline void scene_host_lights_need_table(SceneHost &s);   /* below, with the light-pick tables */
+
+/* spot and sphere lights (include/smallvcm_amd.h has the fields); every other type value stays unchecked, as it was */
+inline bool scene_host_check_lights(const SceneHost &s, std::string &err)
+{
+    for (size_t i = 0; i < s.lights.size(); i++) {
+        const vcm_light &l = s.lights[i];
+        if (l.type != VCM_LIGHT_SPOT && l.type != VCM_LIGHT_SPHERE) continue;
+        const bool spot = l.type == VCM_LIGHT_SPOT;
+        if ((int)i == s.backgroundLight) { err = spot ? "a spot light cannot be the backgroundLight" : "a sphere light cannot be the backgroundLight"; return false; }
+        for (int k = 0; k < 3; k++)
+            if (!std::isfinite(l.p0[k]) || !std::isfinite(l.intensity[k])) {
+                err = spot ? "spot light: position and intensity must be finite" : "sphere light: centre and intensity must be finite"; return false;
+            }
+        if (spot) {
+            for (int k = 0; k < 3; k++)
+                if (!std::isfinite(l.frameX[k]) || !std::isfinite(l.frameY[k]) || !std::isfinite(l.frameZ[k]) || !std::isfinite(l.e1[k])) {
+                    err = "spot light: direction and angles must be finite"; return false;
+                }
+            const float cosOuter = l.e1[0], cosInner = l.e1[1];
+            if (!(cosOuter >= -1.f) || !(cosOuter < 1.f)) { err = "spot light: the outer half-angle must be > 0 and <= 180 degrees"; return false; }
+            if (!(cosInner >= cosOuter) || !(cosInner <= 1.f)) { err = "spot light: the inner half-angle must be >= 0 and <= the outer one"; return false; }
+            if (l.e1[2] < 0.f) { err = "spot light: the falloff scale e1[2] must be >= 0"; return false; }
+            if (!std::isfinite(l.scale) || !(l.scale > 0.f)) { err = "spot light: the cone pdf must be finite and > 0"; return false; }
+        } else {
+            const float r = l.e1[0];
+            if (!std::isfinite(r) || !(r > 0.f)) { err = "sphere light: radius must be finite and > 0"; return false; }
+            if (!std::isfinite(l.invArea) || !(l.invArea > 0.f)) { err = "sphere light: invArea must be finite and > 0"; return false; }
+            int owner = -1, count = 0;
+            for (size_t p = 0; p < s.prims.size(); p++)
+                if (s.mat2light[(size_t)s.prims[p].matID] == (int)i) { owner = (int)p; count++; }
+            if (count != 1) { err = "sphere light: exactly one primitive must carry a material mapped to it"; return false; }
+            const vcm_prim &pr = s.prims[(size_t)owner];
+            if (pr.type != VCM_PRIM_SPHERE || pr.p0[0] != l.p0[0] || pr.p0[1] != l.p0[1] || pr.p0[2] != l.p0[2] || pr.p1[0] != r) {
+                err = "sphere light: its primitive must be a VCM_PRIM_SPHERE of the same centre and radius"; return false;
+            }
+        }
+    }
+    return true;
+}
+
 inline bool scene_host_check(const SceneHost &s, std::string &err)
 {
     if (s.lights.empty()) { err = "scene has no light"; return false; }
@@ -115,7 +163,7 @@ inline bool scene_host_check(const SceneHost &s, std::string &err)
     for (int l : s.mat2light)
         if (l >= (int)s.lights.size()) { err = "mat2light entry out of range"; return false; }
     if (s.backgroundLight >= (int)s.lights.size()) { err = "backgroundLight out of range"; return false; }
-    return true;
+    return scene_host_check_lights(s, err);
 }
 
 /* an env-map light comes with its image (scene_host_set_envmap): vcm_scene_desc / vcm_scene_desc2 cannot carry one */
@@ -138,7 +186,9 @@ inline bool scene_host_from_desc(const vcm_scene_desc &sc, SceneHost &s, std::st
     for (int k = 0; k < 3; k++) s.sceneCenter[k] = sc.sceneCenter[k];
     s.sceneRadius = sc.sceneRadius; s.invSceneRadiusSqr = sc.invSceneRadiusSqr;
     s.camera = sc.camera;
-    return scene_host_check(s, err) && scene_host_no_envmap(s, err);
+    if (!(scene_host_check(s, err) && scene_host_no_envmap(s, err))) return false;
+    scene_host_lights_need_table(s);
+    return true;
 }
 
 inline bool scene_host_copy_desc2(const vcm_scene_desc2 &sc, SceneHost &s, std::string &err)
@@ -158,7 +208,9 @@ inline bool scene_host_copy_desc2(const vcm_scene_desc2 &sc, SceneHost &s, std::
 }
 inline bool scene_host_from_desc2(const vcm_scene_desc2 &sc, SceneHost &s, std::string &err)
 {
-    return scene_host_copy_desc2(sc, s, err) && scene_host_no_envmap(s, err);
+    if (!(scene_host_copy_desc2(sc, s, err) && scene_host_no_envmap(s, err))) return false;
+    scene_host_lights_need_table(s);
+    return true;
 }
 
 /* ---- the environment map's tables (vcm_core.h env_search / env_sample_dir / env_eval) ----
@@ -247,7 +299,9 @@ inline bool scene_host_set_envmap(SceneHost &s, const vcm_envmap *m, std::string
 
 inline bool scene_host_from_desc3(const vcm_scene_desc3 &sc, SceneHost &s, std::string &err)
 {
-    return scene_host_copy_desc2(sc.base, s, err) && scene_host_set_envmap(s, sc.envmap, err);
+    if (!(scene_host_copy_desc2(sc.base, s, err) && scene_host_set_envmap(s, sc.envmap, err))) return false;
+    scene_host_lights_need_table(s);
+    return true;
 }
 
 /* ---- the thin lens (vcm_core.h lens_point / lens_ray / lens_project) ----
@@ -301,6 +355,8 @@ inline double scene_host_light_power(const SceneHost &s, int i)
     switch (l.type) {
     case VCM_LIGHT_AREA: w = l.invArea > 0.f ? PI * lum / (double)l.invArea : 0.0; break;
     case VCM_LIGHT_POINT: w = 4.0 * PI * lum; break;
+    case VCM_LIGHT_SPOT: w = 2.0 * PI * lum * ((1.0 - (double)l.e1[1]) + ((double)l.e1[1] - (double)l.e1[0]) / 2.0); break;
+    case VCM_LIGHT_SPHERE: w = l.invArea > 0.f ? PI * lum / (double)l.invArea : 0.0; break;
     case VCM_LIGHT_DIRECTIONAL: w = PI * R * R * lum; break;
     case VCM_LIGHT_BACKGROUND: w = 4.0 * PI * PI * R * R * lum * (double)l.scale; break;
     case VCM_LIGHT_ENVMAP: {
@@ -358,7 +414,38 @@ inline void scene_host_apportion(const std::vector<double> &w, std::vector<int> 
     }
 }
 
-inline bool scene_host_set_pick(SceneHost &s, const vcm_light_pick *pick, std::string &err)
+/* the tables of the probabilities `mixed` (>= 0, sum 1) */
+inline void scene_host_pick_tables(SceneHost &s, const std::vector<double> &mixed, int mode)
+{
+    const size_t n = s.lights.size();
+    scene_host_apportion(mixed, s.pickQuanta);
+    s.pickPmf.resize(n); s.pickCdf.resize(n + 1);
+    long long acc = 0;
+    s.pickCdf[0] = 0.f;
+    for (size_t i = 0; i < n; i++) {   /* whole multiples of 2^-23 up to 1: exact in binary32 */
+        s.pickPmf[i] = (float)s.pickQuanta[i] * 1.1920928955078125e-07f;
+        acc += s.pickQuanta[i];
+        s.pickCdf[i + 1] = (float)acc * 1.1920928955078125e-07f;
+    }
+    s.pickGuide = scene_host_env_guide_size((int)n);
+    s.pickGuideTable.resize((size_t)s.pickGuide + 1);
+    scene_host_env_guide(s.pickCdf.data(), (int)n, s.pickGuide, s.pickGuideTable.data());
+    s.pickMode = mode;
+}
+
+/* A scene with a spot or a sphere light always has a table: the branches of those lights exist only in the kernels that
+   wrap the table kinds (vcm_core.h WithLights).  Where the caller asked for the uniform choice the table says so: CUSTOM
+   with one weight for every light, i.e. 2^23 / n quanta each, the remainder to the lowest indices. */
+inline void scene_host_lights_need_table(SceneHost &s)
+{
+    if (s.pickMode != VCM_LIGHT_PICK_UNIFORM || !scene_host_has_new_lights(s)) return;
+    const size_t n = s.lights.size();
+    s.pickWeights.assign(n, 1.0);
+    scene_host_pick_tables(s, std::vector<double>(n, 1.0 / (double)n), VCM_LIGHT_PICK_CUSTOM);
+}
+
+/* the tables the caller asked for (NULL or UNIFORM: none) */
+inline bool scene_host_pick_as_asked(SceneHost &s, const vcm_light_pick *pick, std::string &err)
 {
     s.pickMode = VCM_LIGHT_PICK_UNIFORM; s.pickGuide = 0;
     s.pickPmf.clear(); s.pickCdf.clear(); s.pickGuideTable.clear(); s.pickWeights.clear(); s.pickQuanta.clear();
@@ -389,19 +476,13 @@ inline bool scene_host_set_pick(SceneHost &s, const vcm_light_pick *pick, std::s
     s.pickWeights = w;
     std::vector<double> mixed(n, 0.0);
     for (size_t i = 0; i < n; i++) if (w[i] > 0.0) mixed[i] = (1.0 - (double)a) * w[i] / total + (double)a / (double)nz;
-    scene_host_apportion(mixed, s.pickQuanta);
-    s.pickPmf.resize(n); s.pickCdf.resize(n + 1);
-    long long acc = 0;
-    s.pickCdf[0] = 0.f;
-    for (size_t i = 0; i < n; i++) {   /* whole multiples of 2^-23 up to 1: exact in binary32 */
-        s.pickPmf[i] = (float)s.pickQuanta[i] * 1.1920928955078125e-07f;
-        acc += s.pickQuanta[i];
-        s.pickCdf[i + 1] = (float)acc * 1.1920928955078125e-07f;
-    }
-    s.pickGuide = scene_host_env_guide_size((int)n);
-    s.pickGuideTable.resize((size_t)s.pickGuide + 1);
-    scene_host_env_guide(s.pickCdf.data(), (int)n, s.pickGuide, s.pickGuideTable.data());
-    s.pickMode = pick->mode;
+    scene_host_pick_tables(s, mixed, pick->mode);
+    return true;
+}
+inline bool scene_host_set_pick(SceneHost &s, const vcm_light_pick *pick, std::string &err)
+{
+    if (!scene_host_pick_as_asked(s, pick, err)) return false;
+    scene_host_lights_need_table(s);
     return true;
 }
 

@@ -5,7 +5,8 @@
 // feature kernel of the denoiser and vcm_debug_context_info read that value.  with_scene_kind turns it back into a type
 // and adds the wrappers a kernel has instantiations for: WithLens (the kernels that hold the camera vertex, for a scene
 // with a thin lens) and WithPick (the kernels that choose a light or weigh an emitter hit, for a scene with a light-pick
-// table), WithPick over WithLens where a kernel has both.
+// table), WithPick over WithLens where a kernel has both, and WithLights over WithPick for a scene with a spot or a sphere
+// light (such a scene always has a table, so WithLights exists over the WithPick kinds alone).
 #ifndef SMALLVCM_AMD_SCENE_KIND_H
 #define SMALLVCM_AMD_SCENE_KIND_H
 
@@ -57,30 +58,38 @@ template <class S> struct SceneTag { using type = S; };
 /* the wrappers a kernel is instantiated for */
 enum : unsigned { kWrapNone = 0, kWrapLens = 1, kWrapPick = 2 };
 
-template <unsigned Wrap, class S, class F> void with_wrappers(bool lens, bool pick, F &f)
+/* the wrappers a context launches with; lights implies pick (wrappers_valid) */
+struct SceneWrappers { bool lens, pick, lights; };
+constexpr bool wrappers_valid(SceneWrappers w) { return !w.lights || w.pick; }
+static_assert(wrappers_valid({ false, false, false }) && wrappers_valid({ true, true, false }) && wrappers_valid({ false, true, true }),
+              "what a scene without / with the spot and sphere lights launches");
+static_assert(!wrappers_valid({ false, false, true }), "no WithLights kernel exists without the table");
+
+template <unsigned Wrap, class S, class F> void with_wrappers(SceneWrappers w, F &f)
 {
     if constexpr (Wrap & kWrapLens) {
-        if (lens) with_wrappers<Wrap & ~kWrapLens, WithLens<S>>(lens, pick, f);
-        else with_wrappers<Wrap & ~kWrapLens, S>(lens, pick, f);
+        if (w.lens) with_wrappers<Wrap & ~kWrapLens, WithLens<S>>(w, f);
+        else with_wrappers<Wrap & ~kWrapLens, S>(w, f);
     } else if constexpr (Wrap & kWrapPick) {
-        if (pick) f(SceneTag<WithPick<S>>{});
+        if (w.pick && w.lights) f(SceneTag<WithLights<WithPick<S>>>{});
+        else if (w.pick) f(SceneTag<WithPick<S>>{});
         else f(SceneTag<S>{});
     } else f(SceneTag<S>{});
 }
 
 /* Calls f once, with the tag of the instantiation a scene of `kind` takes.  Only the wrappers named in Wrap are ever
    applied, so f is instantiated for exactly the types the kernel exists for. */
-template <unsigned Wrap, class F> void with_scene_kind(SceneKind kind, bool lens, bool pick, F &&f)
+template <unsigned Wrap, class F> void with_scene_kind(SceneKind kind, SceneWrappers w, F &&f)
 {
     switch (kind) {
-    case SceneKind::List:   return with_wrappers<Wrap, SceneList>(lens, pick, f);
-    case SceneKind::Quads:  return with_wrappers<Wrap, SceneQuads>(lens, pick, f);
-    case SceneKind::Rects:  return with_wrappers<Wrap, SceneRects>(lens, pick, f);
-    case SceneKind::Bvh:    return with_wrappers<Wrap, SceneBvh>(lens, pick, f);
-    case SceneKind::BvhG:   return with_wrappers<Wrap, SceneBvhG>(lens, pick, f);
-    case SceneKind::RectsE: return with_wrappers<Wrap, SceneRectsE>(lens, pick, f);
-    case SceneKind::ListE:  return with_wrappers<Wrap, SceneListE>(lens, pick, f);
-    case SceneKind::BvhE:   return with_wrappers<Wrap, SceneBvhE>(lens, pick, f);
+    case SceneKind::List:   return with_wrappers<Wrap, SceneList>(w, f);
+    case SceneKind::Quads:  return with_wrappers<Wrap, SceneQuads>(w, f);
+    case SceneKind::Rects:  return with_wrappers<Wrap, SceneRects>(w, f);
+    case SceneKind::Bvh:    return with_wrappers<Wrap, SceneBvh>(w, f);
+    case SceneKind::BvhG:   return with_wrappers<Wrap, SceneBvhG>(w, f);
+    case SceneKind::RectsE: return with_wrappers<Wrap, SceneRectsE>(w, f);
+    case SceneKind::ListE:  return with_wrappers<Wrap, SceneListE>(w, f);
+    case SceneKind::BvhE:   return with_wrappers<Wrap, SceneBvhE>(w, f);
     }
 }
 

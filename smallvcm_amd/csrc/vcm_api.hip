@@ -183,6 +183,7 @@ struct vcm_ctx : Scratch {
     bool lens;                        /* the camera is a thin lens: the WithLens kernels for the camera vertex */
     bool filter;                      /* the scene has a pixel filter: the WithLens kernels too (vcm_core.h kLens) */
     bool pick;                        /* lights are chosen from a table: the WithPick kernels */
+    bool lights;                      /* the scene holds a spot or a sphere light: WithLights over WithPick (then pick is set) */
     bool intPhong;                    /* every Phong exponent in use is an integer in [1, 65536]: the kernels whose pow is the binary
                                          exponentiation alone (detmath.h); otherwise the SceneList / SceneBvhG kernels and the general merge */
     /* feature buffers and denoiser (vcm_denoise.h): allocated by the first vcm_render_features / vcm_denoise */
@@ -211,7 +212,7 @@ struct vcm_ctx : Scratch {
 
 /* A ray-casting kernel is launched in the instantiation of the context's kind, under the wrappers it exists for (Wrap:
    scene_kind.h): f(tag) launches it with S = typename decltype(tag)::type.  What f evaluates, it evaluates once. */
-template <unsigned Wrap, class F> static void launch_kind(const vcm_ctx *c, F &&f) { with_scene_kind<Wrap>(c->kind, c->lens || c->filter, c->pick, f); }
+template <unsigned Wrap, class F> static void launch_kind(const vcm_ctx *c, F &&f) { with_scene_kind<Wrap>(c->kind, SceneWrappers{ c->lens || c->filter, c->pick, c->lights }, f); }
 
 /* K4 of a context: k_merge_pairs or k_merge_walk (VCM_MERGE_*), with the pow its exponents allow */
 typedef void (*MergeKernel)(const DScene *, IterParams, GridStore, VertexStore, const int *, const int *, unsigned long long *, int, StampArgs);
@@ -773,6 +774,7 @@ static vcm_ctx *create_from_host(SceneHost *h, int algorithm, float radiusFactor
     c->lens = h->lensRadius > 0.f;
     c->filter = h->filterKind != VCM_FILTER_BOX;
     c->pick = h->pickMode != VCM_LIGHT_PICK_UNIFORM;
+    c->lights = c->pick && scene_host_has_new_lights(*h);   /* such a scene always has a table (scene_host_lights_need_table) */
     scene_host_build_accel(*h, scene_host_force_bvh());
     /* VertexCM::VertexCM vertexcm.hxx:222-244 */
     switch (algorithm) {
@@ -3052,6 +3054,7 @@ int vcm_debug_kat(vcm_ctx *c, int op, int n, const float *in, float *out)
 {
     if (!c || !in || !out || n < 0 || op < 0 || op >= VCM_KAT_OPS) return fail("vcm_debug_kat", "bad argument");
     if (op == VCM_KAT_FILTER && !c->filter) return fail("vcm_debug_kat", "VCM_KAT_FILTER needs a context with a pixel filter (vcm_create6)");
+    if (op == VCM_KAT_LIGHT_RADIANCE_AT && !c->lights) return fail("vcm_debug_kat", "VCM_KAT_LIGHT_RADIANCE_AT needs a context with a spot or a sphere light");
     if (op == VCM_KAT_LENS && !c->lens) return fail("vcm_debug_kat", "VCM_KAT_LENS needs a context with a thin lens (vcm_create4)");
     if (ensure_device(c)) return -1;
     if (n == 0) return 0;
@@ -3096,6 +3099,12 @@ int vcm_debug_pixel_filter(vcm_ctx *c, int *kind, float *radius)
     if (kind) *kind = c->scene->filterKind;
     if (radius) *radius = c->scene->filterRadius;
     return 0;
+}
+
+int vcm_debug_lights_kind(vcm_ctx *c)
+{
+    if (!c) return fail("vcm_debug_lights_kind", "bad argument");
+    return c->lights ? 1 : 0;
 }
 
 int vcm_debug_scene_kind(int envMap, int bvh, int intPhong, int rects, int quads)

@@ -369,6 +369,7 @@ struct DScene {
     static constexpr bool kEnvMap = false;
     static constexpr bool kLens = false;
     static constexpr bool kPick = false;
+    static constexpr bool kLights = false;
     int nPrims, nMaterials, nLights, backgroundLight;
     float sceneCenter[3], sceneRadius, invSceneRadiusSqr;
     vcm_camera camera;
@@ -482,6 +483,17 @@ template <class S> struct WithPick : S { static constexpr bool kPick = true; };
 #else
 #define VCM_PICK_KIND(S) true
 #define VCM_PICK_ON(S, sc) ((sc).pickMode != 0)
+#endif
+
+/* kLights: the scene holds a spot or a sphere light (VCM_LIGHT_SPOT, VCM_LIGHT_SPHERE).  Their branches of Illuminate,
+   Emit and the emitter hit exist only in these kinds, one over each WithPick kind -- such a scene always has a table
+   (scene_host.h scene_host_lights_need_table), so the kinds without a table, and the table kinds themselves, hold what
+   they held before there were such lights.  The host builds carry the branches in every kind. */
+template <class S> struct WithLights : S { static constexpr bool kLights = true; };
+#if defined(__HIP_DEVICE_COMPILE__)
+#define VCM_LIGHTS_KIND(S) (S::kLights)
+#else
+#define VCM_LIGHTS_KIND(S) true
 #endif
 
 /* ---- the scene's small tables in LDS ----
@@ -1930,6 +1942,28 @@ VCM_HD V3 bsdf_sample(const Bsdf &b, const S &sc, bool fixIsLight, float r0, flo
 /* ---- lights.hxx ---------------------------------------------------- */
 VCM_HD bool light_is_finite(const vcm_light &l) { return l.type == VCM_LIGHT_AREA || l.type == VCM_LIGHT_POINT; }
 VCM_HD bool light_is_delta(const vcm_light &l) { return l.type == VCM_LIGHT_DIRECTIONAL || l.type == VCM_LIGHT_POINT; }
+/* the same two questions in a kind that knows the spot (finite, delta) and the sphere (finite, not delta); the kinds
+   without them keep the two comparisons above */
+template <class S> VCM_HD bool light_is_finite(const S &, const vcm_light &l)
+{
+    if constexpr (VCM_LIGHTS_KIND(S)) if (l.type == VCM_LIGHT_SPOT || l.type == VCM_LIGHT_SPHERE) return true;
+    return light_is_finite(l);
+}
+template <class S> VCM_HD bool light_is_delta(const S &, const vcm_light &l)
+{
+    if constexpr (VCM_LIGHTS_KIND(S)) if (l.type == VCM_LIGHT_SPOT) return true;
+    return light_is_delta(l);
+}
+/* the spot's falloff for c = the cosine between its axis and a direction from the light: 0 outside the outer cone, the
+   smoothstep t^2 (3 - 2 t) of t = (c - cosOuter) / (cosInner - cosOuter) between the cones, 1 inside the inner one (and
+   inside the whole cone of a hard edge, e1[2] == 0) */
+VCM_HD float spot_falloff(const vcm_light &l, float c)
+{
+    if (c < l.e1[0]) return 0.f;
+    if (l.e1[2] == 0.f) return 1.f;
+    const float t = smin(smax((c - l.e1[0]) * l.e1[2], 0.f), 1.f);
+    return t * t * (3.f - 2.f * t);
+}
 VCM_HD vcm_light get_light(const DScene &sc, int idx)
 {   /* Scene::GetLightPtr scene.hxx:98-102 */
     idx = (sc.nLights - 1 < idx) ? sc.nLights - 1 : idx;
@@ -2094,6 +2128,35 @@ VCM_HD V3 light_illuminate(const vcm_light &l, const S &sc, V3 recvPos, float rx
 {
     if constexpr (VCM_ENV_KIND(S))
         if (l.type == VCM_LIGHT_ENVMAP) return env_illuminate(sc, rx, ry, dirToLight, distance, directPdfW, emissionPdfW, cosAtLight);
+    if constexpr (VCM_LIGHTS_KIND(S)) {
+        if (l.type == VCM_LIGHT_SPOT) {   /* the point light's, times the falloff; emissionPdfW = the density Emit draws with */
+            dirToLight = ld3(l.p0) - recvPos;
+            const float distSqr = lensqr(dirToLight);
+            directPdfW = distSqr;
+            distance = sqrtf(distSqr);
+            dirToLight = dirToLight / distance;
+            cosAtLight = 1.f;
+            emissionPdfW = l.scale;
+            const float s = spot_falloff(l, dot(ld3(l.frameZ), -dirToLight));
+            if (s == 0.f) return sp3(0.f);
+            return ld3(l.intensity) * s;
+        }
+        if (l.type == VCM_LIGHT_SPHERE) {   /* a uniform point of the whole sphere, then AreaLight::Illuminate with its normal */
+            float pdf;
+            const V3 n = sample_uniform_sphere(rx, ry, pdf);
+            const V3 lightPoint = ld3(l.p0) + l.e1[0] * n;
+            dirToLight = lightPoint - recvPos;
+            const float distSqr = lensqr(dirToLight);
+            distance = sqrtf(distSqr);
+            dirToLight = dirToLight / distance;
+            const float cosNormalDir = dot(n, -dirToLight);
+            if (cosNormalDir < VCM_EPS_COSINE) return sp3(0.f);   /* the far side: about 55 % of a receiver's samples */
+            directPdfW = l.invArea * distSqr / cosNormalDir;
+            cosAtLight = cosNormalDir;
+            emissionPdfW = l.invArea * cosNormalDir * VCM_INV_PI_F;
+            return ld3(l.intensity);
+        }
+    }
     if (l.type == VCM_LIGHT_AREA) {   /* AreaLight::Illuminate :129-166 */
         float u, v;
         sample_uniform_triangle(rx, ry, u, v);
@@ -2140,6 +2203,34 @@ VCM_HD V3 light_emit(const vcm_light &l, const S &sc, float dx, float dy, float 
 {
     if constexpr (VCM_ENV_KIND(S))
         if (l.type == VCM_LIGHT_ENVMAP) return env_emit(sc, dx, dy, px, py, position, direction, emissionPdfW, directPdfA, cosThetaLight);
+    if constexpr (VCM_LIGHTS_KIND(S)) {
+        if (l.type == VCM_LIGHT_SPOT) {   /* uniform in the outer cone: cos theta = 1 - dx (1 - cosOuter), phi = 2 pi dy */
+            position = ld3(l.p0);
+            const float cosTheta = 1.f - dx * (1.f - l.e1[0]);
+            const float sinTheta = sqrtf(smax(0.f, 1.f - cosTheta * cosTheta));
+            float s, c;
+            dm_sincosf_cold(2.f * VCM_PI_F * dy, s, c);
+            Frame f; f.mX = ld3(l.frameX); f.mY = ld3(l.frameY); f.mZ = ld3(l.frameZ);
+            direction = to_world(f, mk3(c * sinTheta, s * sinTheta, cosTheta));
+            emissionPdfW = l.scale;
+            directPdfA = 1.f;
+            cosThetaLight = 1.f;
+            return ld3(l.intensity) * spot_falloff(l, cosTheta);
+        }
+        if (l.type == VCM_LIGHT_SPHERE) {   /* a uniform point, then AreaLight::Emit in the frame of its normal */
+            float pdf;
+            const V3 n = sample_uniform_sphere(px, py, pdf);
+            position = ld3(l.p0) + l.e1[0] * n;
+            V3 localDirOut = sample_cos_hemisphere(dx, dy, emissionPdfW);
+            emissionPdfW *= l.invArea;
+            localDirOut.z = smax(localDirOut.z, VCM_EPS_COSINE);
+            Frame f; frame_from_z(f, n);
+            direction = to_world(f, localDirOut);
+            directPdfA = l.invArea;
+            cosThetaLight = localDirOut.z;
+            return ld3(l.intensity) * localDirOut.z;
+        }
+    }
     if (l.type == VCM_LIGHT_AREA) {   /* AreaLight::Emit :168-198 */
         float u, v;
         sample_uniform_triangle(px, py, u, v);
@@ -2205,6 +2296,25 @@ VCM_HD V3 light_get_radiance(const vcm_light &l, const S &sc, V3 rayDir,
         return radiance;
     }
     return sp3(0.f);   /* directional :296-304, point :378-386 */
+}
+/* the emitter hit where the caller holds the intersection: `normal` = Isect::normal, which a sphere light needs (it is
+   the sphere's outward normal at the hit); every other type is answered by the function above, a spot -- never hit --
+   with zero */
+template <class S>
+VCM_HD V3 light_get_radiance_at(const vcm_light &l, const S &sc, V3 rayDir, V3 normal,
+                                float &directPdfA, float &emissionPdfW)
+{
+    if constexpr (VCM_LIGHTS_KIND(S)) {
+        if (l.type == VCM_LIGHT_SPHERE) {   /* AreaLight::GetRadiance :200-221 with the normal at the hit */
+            const float cosOutL = smax(0.f, dot(normal, -rayDir));
+            if (cosOutL == 0.f) return sp3(0.f);
+            directPdfA = l.invArea;
+            emissionPdfW = cos_hemisphere_pdf(normal, -rayDir);
+            emissionPdfW *= l.invArea;
+            return ld3(l.intensity);
+        }
+    }
+    return light_get_radiance(l, sc, rayDir, directPdfA, emissionPdfW);
 }
 
 /* ------------------------------------------------------------------ */
@@ -2285,11 +2395,11 @@ VCM_HD void generate_light_sample(const S &sc, const IterParams &P, PathRng &rng
     directPdfA *= lightPickProb;
     st.throughput = st.throughput / emissionPdfW;
     st.pathLength = 1;
-    st.isFiniteLight = light_is_finite(light) ? 1u : 0u;
+    st.isFiniteLight = light_is_finite(sc, light) ? 1u : 0u;
     st.specularPath = 0;
     st.dVCM = mis(directPdfA / emissionPdfW);
-    if (!light_is_delta(light)) {
-        const float usedCosLight = light_is_finite(light) ? cosLight : 1.f;
+    if (!light_is_delta(sc, light)) {
+        const float usedCosLight = light_is_finite(sc, light) ? cosLight : 1.f;
         st.dVC = mis(usedCosLight / emissionPdfW);
     } else {
         st.dVC = 0.f;
@@ -2577,12 +2687,13 @@ VCM_HD void connect_stored_vertex_to_camera(const SC &sc, const IterParams &P, c
 /* GetLightRadiance :617-658 */
 template <class S>
 VCM_HD V3 get_light_radiance(const S &sc, const IterParams &P, const vcm_light &light, int lightID,
-                             const SubPathState &st, V3 rayDir)
-{   /* lightID: the index of `light`; a light the table never picks (pmf 0) emits nothing and returns at iszero() */
+                             const SubPathState &st, V3 rayDir, V3 normal)
+{   /* lightID: the index of `light`; a light the table never picks (pmf 0) emits nothing and returns at iszero();
+       normal: Isect::normal of the hit (anything on a miss: the background needs none) */
     const int lightCount = sc.nLights;
     const float lightPickProb = light_pick_prob(sc, lightID, 1.f / lightCount);
     float directPdfA = 0.f, emissionPdfW = 0.f;
-    const V3 radiance = light_get_radiance(light, sc, rayDir, directPdfA, emissionPdfW);
+    const V3 radiance = light_get_radiance_at(light, sc, rayDir, normal, directPdfA, emissionPdfW);
     if (iszero(radiance)) return sp3(0.f);
     if (st.pathLength == 1) return radiance;
     if (P.useVM && !P.useVC) return st.specularPath ? radiance : sp3(0.f);
@@ -2612,7 +2723,7 @@ VCM_HD V3 direct_illumination(const SC &sc, const IterParams &P, float rPick, fl
     const V3 bsdfFactor = bsdf_evaluate(bsdf, sc, directionToLight, cosToLight, &bsdfDirPdfW, &bsdfRevPdfW);
     if (iszero(bsdfFactor)) return sp3(0.f);
     const float continuationProbability = bsdf.contProb;
-    bsdfDirPdfW *= light_is_delta(light) ? 0.f : continuationProbability;
+    bsdfDirPdfW *= light_is_delta(sc, light) ? 0.f : continuationProbability;
     bsdfRevPdfW *= continuationProbability;
     const float wLight = mis(bsdfDirPdfW / (lightPickProb * directPdfW));
     const float wCamera = mis(emissionPdfW * cosToLight / (directPdfW * cosAtLight)) *
@@ -3186,7 +3297,7 @@ VCM_HD bool camera_path_step(const SC &sc, const IterParams &P, CameraPath &cp, 
     if (!hitSomething) {   /* :434-447 */
         if (sc.backgroundLight >= 0) {
             if (st.pathLength >= P.minLen)
-                cp.color = cp.color + st.throughput * get_light_radiance(sc, P, sc.lights()[sc.backgroundLight], sc.backgroundLight, st, ray.dir);
+                cp.color = cp.color + st.throughput * get_light_radiance(sc, P, sc.lights()[sc.backgroundLight], sc.backgroundLight, st, ray.dir, isect.normal);
         }
         return false;
     }
@@ -3204,7 +3315,7 @@ VCM_HD bool camera_path_step(const SC &sc, const IterParams &P, CameraPath &cp, 
     if (isect.lightID >= 0) {   /* :468-479 */
         const vcm_light &light = get_light(sc, isect.lightID);
         if (st.pathLength >= P.minLen)
-            cp.color = cp.color + st.throughput * get_light_radiance(sc, P, light, isect.lightID, st, ray.dir);
+            cp.color = cp.color + st.throughput * get_light_radiance(sc, P, light, isect.lightID, st, ray.dir, isect.normal);
         return false;
     }
     if (st.pathLength >= P.maxLen) return false;   /* :482 */
@@ -3505,7 +3616,7 @@ VCM_HD bool pt_path_step(const SC &sc, const IterParams &P, PtPath &pp, LaneStat
         if (pp.pathLength < P.minLen) return false;
         const vcm_light &light = get_light(sc, isect.lightID);
         float directPdfA = 0.f, emissionPdfW = 0.f;
-        const V3 contrib = light_get_radiance(light, sc, ray.dir, directPdfA, emissionPdfW);
+        const V3 contrib = light_get_radiance_at(light, sc, ray.dir, isect.normal, directPdfA, emissionPdfW);
         if (iszero(contrib)) return false;
         float misWeight = 1.f;
         if (pp.pathLength > 1 && !pp.lastSpecular) {
@@ -3533,7 +3644,7 @@ VCM_HD bool pt_path_step(const SC &sc, const IterParams &P, PtPath &pp, LaneStat
             const V3 factor = bsdf_evaluate(bsdf, sc, directionToLight, cosThetaOut, &bsdfPdfW, NULL);
             if (!iszero(factor)) {
                 float weight = 1.f;
-                if (!light_is_delta(light)) {
+                if (!light_is_delta(sc, light)) {
                     const float contProb = bsdf.contProb;
                     bsdfPdfW *= contProb;
                     weight = mis2(directPdfW * lightPickProb, bsdfPdfW);

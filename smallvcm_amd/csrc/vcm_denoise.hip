@@ -163,7 +163,7 @@ hipError_t dn_launch_features(const DScene *dScene, SceneKind kind, int resX, in
 {
     int blocks = (nLocal + 255) / 256;
     blocks = blocks < 1 ? 1 : (blocks > 4096 ? 4096 : blocks);
-    with_scene_kind<kWrapNone>(kind, false, false, [&](auto tag) {
+    with_scene_kind<kWrapNone>(kind, SceneWrappers{ false, false, false }, [&](auto tag) {
         using S = typename decltype(tag)::type;
         hipLaunchKernelGGL((k_features<S>), dim3(blocks), dim3(256), 0, stream, dScene, resX, p0, nLocal, guide, albedo);
     });

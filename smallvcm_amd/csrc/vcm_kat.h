@@ -62,7 +62,7 @@ VCM_HD void kat_eval(const SC &sc, int op, const float *in, float *out)
         const V3 e = light_emit(l, sc, in[1], in[2], in[3], in[4], pos, dir, emissionPdfW, directPdfA, cosLight);
         out[0] = e.x; out[1] = e.y; out[2] = e.z; out[3] = pos.x; out[4] = pos.y; out[5] = pos.z;
         out[6] = dir.x; out[7] = dir.y; out[8] = dir.z; out[9] = emissionPdfW; out[10] = directPdfA; out[11] = cosLight;
-        out[12] = light_is_finite(l) ? 1.f : 0.f; out[13] = light_is_delta(l) ? 1.f : 0.f;
+        out[12] = light_is_finite(sc, l) ? 1.f : 0.f; out[13] = light_is_delta(sc, l) ? 1.f : 0.f;
     } break;
     case VCM_KAT_LIGHT_ILLUMINATE: {   /* AbstractLight::Illuminate lights.hxx:131, :244, :329, :410 */
         const vcm_light &l = get_light(sc, (int)in[0]);
@@ -121,6 +121,13 @@ VCM_HD void kat_eval(const SC &sc, int op, const float *in, float *out)
             out[3] = in[0] + ox; out[4] = in[1] + oy;
         }
         break;
+    case VCM_KAT_LIGHT_RADIANCE_AT: {   /* light_get_radiance_at (vcm_core.h): the emitter hit with the normal at the hit */
+        const vcm_light &l = get_light(sc, (int)in[0]);
+        float directPdfA = 0.f, emissionPdfW = 0.f;
+        const V3 r = light_get_radiance_at(l, sc, ld3(in + 1), ld3(in + 4), directPdfA, emissionPdfW);
+        out[0] = r.x; out[1] = r.y; out[2] = r.z;
+        if (!iszero(r)) { out[3] = directPdfA; out[4] = emissionPdfW; }
+    } break;
     default: break;
     }
 }

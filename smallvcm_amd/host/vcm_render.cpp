@@ -392,7 +392,12 @@ int main(int argc, char **argv)
             std::vector<std::pair<float, int>> top;
             for (int l = 0; l < nLights; l++) top.push_back(std::make_pair(-res[(size_t)l * VCM_KAT_FLOATS + 2], l));
             std::sort(top.begin(), top.end());
-            for (size_t k = 0; k < top.size() && k < 5; k++) printf("  light %d: pmf %.7g\n", top[k].second, -top[k].first);
+            static const char *const typeNames[] = { "area", "directional", "point", "background", "envmap", "spot", "sphere" };
+            const vcm_light *lights = pickScene->base.base.base.lights;
+            for (size_t k = 0; k < top.size() && k < 5; k++) {
+                const int t = lights[top[k].second].type;
+                printf("  light %d (%s): pmf %.7g\n", top[k].second, t >= 0 && t <= VCM_LIGHT_SPHERE ? typeNames[t] : "?", -top[k].first);
+            }
         }
     }
     // untimed warm-up on a throw-away renderer: allocations, first-launch costs

@@ -43,6 +43,10 @@ class SceneBuilder:
         L.vcm_make_background_light.restype = None
         L.vcm_make_envmap_light.argtypes = [C.c_float, C.POINTER(Light)]
         L.vcm_make_envmap_light.restype = None
+        L.vcm_make_spot_light.argtypes = [fp, fp, fp, C.c_float, C.c_float, C.POINTER(Light)]
+        L.vcm_make_spot_light.restype = None
+        L.vcm_make_sphere_light.argtypes = [fp, C.c_float, fp, C.POINTER(Light)]
+        L.vcm_make_sphere_light.restype = None
         L.vcm_make_material.argtypes = [C.POINTER(Material)]
         L.vcm_make_material.restype = None
         L.vcm_make_camera.argtypes = [fp, fp, fp, C.c_float, C.c_int, C.c_int, C.POINTER(Camera)]
@@ -100,6 +104,33 @@ class SceneBuilder:
         light = Light()
         self.L.vcm_make_point_light(_f3(position), _f3(intensity), C.byref(light))
         self.lights.append(light)
+
+    def spot_light(self, position, direction, intensity, outer_deg, inner_deg=None):
+        """a point light with a cone around `direction` (include/smallvcm_amd.h VCM_LIGHT_SPOT): `intensity` is the radiant
+        intensity on the axis, full inside the half-angle inner_deg, smoothly down to zero at outer_deg (0 < outer <=
+        180, 0 <= inner <= outer; inner_deg None: a hard edge at outer_deg)"""
+        o = float(outer_deg)
+        i = o if inner_deg is None else float(inner_deg)
+        if not (math.isfinite(o) and 0.0 < o <= 180.0):
+            raise ValueError("spot_light: outer_deg must be finite, > 0 and <= 180")
+        if not (math.isfinite(i) and 0.0 <= i <= o):
+            raise ValueError("spot_light: inner_deg must be finite, >= 0 and <= outer_deg")
+        light = Light()
+        self.L.vcm_make_spot_light(_f3(position), _f3(direction), _f3(intensity), o, i, C.byref(light))
+        self.lights.append(light)
+
+    def sphere_light(self, center, radius, intensity):
+        """a sphere that emits the radiance `intensity` outwards (include/smallvcm_amd.h VCM_LIGHT_SPHERE): the sphere
+        primitive, a black material of its own and the light its mat2light entry names; returns the primitive's index"""
+        r = float(radius)
+        if not (math.isfinite(r) and r > 0.0):
+            raise ValueError("sphere_light: radius must be finite and > 0")
+        mat = self.material()
+        light = Light()
+        self.L.vcm_make_sphere_light(_f3(center), r, _f3(intensity), C.byref(light))
+        self.lights.append(light)
+        self.mat2light[mat] = len(self.lights) - 1
+        return self.sphere(center, r, mat)
 
     def background_light(self, scale=1.0):
         light = Light()
