@@ -227,6 +227,29 @@ typedef struct vcm_scene_desc6 {
     const vcm_pixel_filter *filter;
 } vcm_scene_desc6;
 
+/* The sampler: where a path's random floats come from.  PHILOX (the default): independent white noise, float k of the
+ * counter-based stream (seed, local iteration, path, kind) -- the reference's Rng made random-access.  SOBOL: float k is
+ * component k & 1 of pair k >> 1 of a padded two-dimensional Sobol sequence with hash-based Owen scrambling (Burley
+ * 2020), indexed by the local iteration: the scrambles depend on (seed, path, kind, pair) only, so for every pair the
+ * points of iterations a 2^m .. (a + 1) 2^m - 1 are a (0, m, 2)-net, and the draw groups of a path start on pair
+ * boundaries (one position is skipped where needed; skipped positions count in vcm_get_rng_counts).  Lower error at
+ * equal cost where the integrand is smooth in a few dimensions (anti-aliasing, area and sky lights, the first bounce,
+ * depth of field); largest gain at power-of-two iteration counts.  DESIGN.md "Sampler". */
+enum {
+    VCM_SAMPLER_PHILOX = 0,
+    VCM_SAMPLER_SOBOL = 1
+};
+typedef struct vcm_sampler {
+    int kind;
+} vcm_sampler;
+
+/* Scene description, version 7: a version-6 scene and its sampler.  `sampler` NULL, or kind PHILOX, renders exactly
+ * what vcm_create6 renders.  The sampler is copied. */
+typedef struct vcm_scene_desc7 {
+    vcm_scene_desc6    base;
+    const vcm_sampler *sampler;
+} vcm_scene_desc7;
+
 /* VertexCM::AlgorithmType (src/vertexcm.hxx:182-204) -- same values */
 enum {
     VCM_ALGO_LIGHT_TRACE = 0,
@@ -336,6 +359,14 @@ vcm_ctx *vcm_create_sharded5(const vcm_scene_desc5 *scene, int algorithm,
 vcm_ctx *vcm_create6(const vcm_scene_desc6 *scene, int algorithm,
                      float radiusFactor, float radiusAlpha, int seed);
 vcm_ctx *vcm_create_sharded6(const vcm_scene_desc6 *scene, int algorithm,
+                             float radiusFactor, float radiusAlpha, int seed,
+                             int device, int rank, int worldSize);
+
+/* The same for a version-7 scene description (sampler).  NULL with vcm_last_error() for an unknown kind or a bad
+ * version-6 scene; checked before a device is looked for. */
+vcm_ctx *vcm_create7(const vcm_scene_desc7 *scene, int algorithm,
+                     float radiusFactor, float radiusAlpha, int seed);
+vcm_ctx *vcm_create_sharded7(const vcm_scene_desc7 *scene, int algorithm,
                              float radiusFactor, float radiusAlpha, int seed,
                              int device, int rank, int worldSize);
 
@@ -579,6 +610,9 @@ const vcm_scene_desc5 *vcm_scene_file_desc5(const vcm_scene_file *scene);
 /* The same scene as a version-6 description: `filter` set when the file has a `filter tent|bspline radius` directive,
  * NULL otherwise; its base is vcm_scene_file_desc5's.  Points into the handle, like vcm_scene_file_desc. */
 const vcm_scene_desc6 *vcm_scene_file_desc6(const vcm_scene_file *scene);
+/* The same scene as a version-7 description: its base is vcm_scene_file_desc6's, its sampler that of the file's
+ * `sampler sobol|philox` directive, NULL without one.  Points into the handle, like vcm_scene_file_desc. */
+const vcm_scene_desc7 *vcm_scene_file_desc7(const vcm_scene_file *scene);
 
 /* Environment maps from files: Radiance RGBE (.hdr: "#?RADIANCE" / "#?RGBE", FORMAT=32-bit_rle_rgbe, "-Y H +X W", flat
  * or new-style run-length scanlines) or PFM (.pfm: "PF", either byte order; its bottom-up rows are flipped), picked by

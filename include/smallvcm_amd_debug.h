@@ -71,7 +71,12 @@ enum {
                                      hit as the render path asks it (a sphere light needs the normal; every other type
                                      answers as VCM_KAT_LIGHT_RADIANCE does); needs a context with a spot or a sphere light
                                                                                      DESIGN.md "Spot and sphere lights" */
-    VCM_KAT_OPS = 12
+    VCM_KAT_SAMPLER = 12,         /* in: the BIT PATTERNS of the integers seed, sample index i, path, kind, position k in floats 0..4
+                                     (memcpy, not values: i and seed need 32 bits) -> out[0] = float k of the Sobol sampler for that
+                                     stream and index, out[1] = the bit pattern of its 32-bit word.  The op names the
+                                     sampler's function (csrc/sobol.h sobol_word), not the context's mode: any context answers
+                                                                                                  DESIGN.md "Sampler" */
+    VCM_KAT_OPS = 13
 };
 int vcm_debug_kat(vcm_ctx *ctx, int op, int n, const float *in, float *out);
 
@@ -96,6 +101,10 @@ int vcm_debug_lights_kind(vcm_ctx *ctx);
  * exactly the kernels of vcm_create5).  A filter without a lens launches the WithLens kinds, so VCM_INFO_LENS -- which
  * stays "the scene has a thin lens" -- does not tell; this does.  Either pointer may be NULL. */
 int vcm_debug_pixel_filter(vcm_ctx *ctx, int *kind, float *radius);
+
+/* The sampler of a context as its kernels see it (vcm_sampler; VCM_SAMPLER_PHILOX: the context launches exactly the
+ * kernels of vcm_create6, VCM_SAMPLER_SOBOL: the WithSobol kinds). */
+int vcm_debug_sampler(vcm_ctx *ctx, int *kind);
 
 /* The rule that picks a context's kind from the five facts about its scene (csrc/scene_kind.h, scene_kind_of), for a
  * test of the rule itself: 0 SceneList, 1 SceneQuads, 2 SceneRects, 3 SceneBvh, 4 SceneBvhG, 5 SceneRectsE, 6 SceneListE,

@@ -35,6 +35,7 @@ typedef struct vcm_farm_config {
     const void *uniqueIds;           /* NULL when localRanks == ranks; else (1 + ranks / shards) ids from vcm_farm_unique_ids */
     int   nUniqueIds;
     vcm_pixel_filter filter;         /* the pixel filter of every renderer (kind VCM_FILTER_BOX, as zeroed: the reference's) */
+    vcm_sampler sampler;             /* the sampler of every renderer (kind VCM_SAMPLER_PHILOX, as zeroed: the default) */
 } vcm_farm_config;
 
 typedef struct vcm_farm_result {

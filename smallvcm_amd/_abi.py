@@ -151,6 +151,52 @@ class SceneDesc6(C.Structure):
         return self.base.base.base.base.camera
 
 
+SAMPLER_PHILOX, SAMPLER_SOBOL = 0, 1
+SAMPLERS = {"philox": SAMPLER_PHILOX, "sobol": SAMPLER_SOBOL}
+SAMPLER_NAMES = {v: k for k, v in SAMPLERS.items()}
+
+
+class Sampler(C.Structure):
+    """vcm_sampler: where the paths' random floats come from (SAMPLER_PHILOX: white noise, the default; SAMPLER_SOBOL:
+    the Owen-scrambled Sobol sequence; include/smallvcm_amd.h)"""
+    _fields_ = [("kind", C.c_int)]
+
+
+class SceneDesc7(C.Structure):
+    """vcm_scene_desc7: a version-6 scene and an optional sampler.  Like SceneDesc2 the arrays are owned by the Python
+    object that built it."""
+    _fields_ = [("base", SceneDesc6), ("sampler", C.POINTER(Sampler))]
+
+    @property
+    def camera(self):
+        return self.base.base.base.base.base.camera
+
+
+def with_sampler(desc, kind):
+    """a SceneDesc2 .. SceneDesc6 as a SceneDesc7 with the sampler `kind` ("sobol", "philox" or a SAMPLER_* value; None:
+    sampler = NULL); the levels in between get NULL settings.  The result keeps `desc` alive."""
+    chain = [SceneDesc2, SceneDesc3, SceneDesc4, SceneDesc5, SceneDesc6, SceneDesc7]
+    if isinstance(desc, SceneDesc7):
+        desc = desc.base
+    if type(desc) not in chain:
+        raise TypeError("with_sampler: a SceneDesc2 .. SceneDesc7 is needed (a built-in box: SceneBuilder or a scene file)")
+    d = desc
+    for cls in chain[chain.index(type(desc)) + 1:]:
+        up = cls()
+        up.base = d
+        up._keep = (getattr(d, "_keep", None), d)
+        d = up
+    if kind is not None:
+        if isinstance(kind, str):
+            if kind not in SAMPLERS:
+                raise ValueError("sampler: must be 'sobol' or 'philox'")
+            kind = SAMPLERS[kind]
+        s = Sampler(int(kind))
+        d.sampler = C.pointer(s)
+        d._keep = d._keep + (s,)
+    return d
+
+
 class DenoiseParams(C.Structure):
     """vcm_denoise_params: a-trous passes (0 .. 12), the three edge-stopping sigmas, and whether the albedo is divided
     out before the first pass and multiplied back after the last (include/smallvcm_amd.h)"""

@@ -35,6 +35,10 @@
 //                                                        the offset density in pixels, finite, > 0 and <= 16, nothing
 //                                                        after it (vcm_pixel_filter, vcm_scene_desc6,
 //                                                        vcm_scene_file_desc6)
+//       sampler sobol|philox                             where the paths' random floats come from, at most once: the
+//                                                        Owen-scrambled Sobol sequence or the default white noise,
+//                                                        nothing after it (vcm_sampler, vcm_scene_desc7,
+//                                                        vcm_scene_file_desc7)
 //   .obj        v, f (triangles; polygons are fanned around their first vertex; v, v/vt, v/vt/vn, v//vn; negative
 //               = relative indices), usemtl, mtllib; everything else is skipped
 //   .mtl        newmtl, Kd -> mDiffuseReflectance, Ks + Ns -> mPhongReflectance / mPhongExponent (materials.hxx:54-65),
@@ -80,6 +84,9 @@ struct vcm_scene_file {
     bool haveFilter = false;          /* `filter` */
     vcm_pixel_filter filter;
     vcm_scene_desc6 desc6;
+    bool haveSampler = false;         /* `sampler` */
+    vcm_sampler sampler;
+    vcm_scene_desc7 desc7;
     ~vcm_scene_file() { vcm_envmap_free(envmap); }
 };
 
@@ -472,6 +479,13 @@ struct Loader {
                 out->filter.kind = kind == "tent" ? VCM_FILTER_TENT : VCM_FILTER_BSPLINE;
                 out->filter.radius = x[0];
                 out->haveFilter = true;
+            } else if (key == "sampler") {
+                const std::string kind = word(p);
+                const std::string rest = word(p);
+                if ((kind != "sobol" && kind != "philox") || (!rest.empty() && rest[0] != '#')) { ok = fail(at + ": sampler sobol|philox"); break; }
+                if (out->haveSampler) { ok = fail(at + ": a second sampler"); break; }
+                out->sampler.kind = kind == "sobol" ? VCM_SAMPLER_SOBOL : VCM_SAMPLER_PHILOX;
+                out->haveSampler = true;
             } else if (key == "light") {
                 const std::string kind = word(p);
                 vcm_light l;
@@ -539,6 +553,8 @@ struct Loader {
         out->desc5.pick = out->havePick ? &out->pick : NULL;
         out->desc6.base = out->desc5;
         out->desc6.filter = out->haveFilter ? &out->filter : NULL;
+        out->desc7.base = out->desc6;
+        out->desc7.sampler = out->haveSampler ? &out->sampler : NULL;
         return true;
     }
 };
@@ -580,6 +596,7 @@ const vcm_scene_desc3 *vcm_scene_file_desc3(const vcm_scene_file *s) { return s 
 const vcm_scene_desc4 *vcm_scene_file_desc4(const vcm_scene_file *s) { return s ? &s->desc4 : NULL; }
 const vcm_scene_desc5 *vcm_scene_file_desc5(const vcm_scene_file *s) { return s ? &s->desc5 : NULL; }
 const vcm_scene_desc6 *vcm_scene_file_desc6(const vcm_scene_file *s) { return s ? &s->desc6 : NULL; }
+const vcm_scene_desc7 *vcm_scene_file_desc7(const vcm_scene_file *s) { return s ? &s->desc7 : NULL; }
 
 vcm_envmap *vcm_envmap_load(const char *path)
 {

@@ -53,6 +53,8 @@ struct SceneHost {
     /* the pixel filter (scene_host_set_filter; filterKind BOX: the reference's), DScene::filterKind ... */
     int filterKind = VCM_FILTER_BOX;
     float filterRadius = 0.f;
+    /* the sampler (scene_host_set_sampler; PHILOX: the default), DScene::samplerKind */
+    int sampler = VCM_SAMPLER_PHILOX;
     /* how lights are chosen (scene_host_set_pick; pickMode UNIFORM: no tables), DScene::pickMode ...; pickWeights are
        the weights before the mix and pickQuanta the m_i of pmf[i] = m_i 2^-23 (for reports and tests) */
     int pickMode = VCM_LIGHT_PICK_UNIFORM, pickGuide = 0;
@@ -101,6 +103,7 @@ struct SceneHost {
         for (int k = 0; k < 3; k++) { d.lensRight[k] = lensRight[k]; d.lensUp[k] = lensUp[k]; }
         d.pickMode = pickMode; d.pickGuide = pickGuide;
         d.filterKind = filterKind; d.filterRadius = filterRadius;
+        d.samplerKind = sampler;
         { const char *e = getenv("SMALLVCM_AMD_NO_RECTS"); if (e && e[0] == '1') d.nFastRects[0] = d.nFastRects[1] = d.nFastRects[2] = 0; }   /* measurement switch */
     }
 };
@@ -506,6 +509,21 @@ inline bool scene_host_set_filter(SceneHost &s, const vcm_pixel_filter *filter, 
 inline bool scene_host_from_desc6(const vcm_scene_desc6 &sc, SceneHost &s, std::string &err)
 {
     return scene_host_from_desc5(sc.base, s, err) && scene_host_set_filter(s, sc.filter, err);
+}
+
+/* ---- the sampler (sobol.h) ---- */
+inline bool scene_host_set_sampler(SceneHost &s, const vcm_sampler *sampler, std::string &err)
+{
+    s.sampler = VCM_SAMPLER_PHILOX;
+    if (!sampler || sampler->kind == VCM_SAMPLER_PHILOX) return true;
+    if (sampler->kind != VCM_SAMPLER_SOBOL) { err = "sampler: unknown kind"; return false; }
+    s.sampler = VCM_SAMPLER_SOBOL;
+    return true;
+}
+
+inline bool scene_host_from_desc7(const vcm_scene_desc7 &sc, SceneHost &s, std::string &err)
+{
+    return scene_host_from_desc6(sc.base, s, err) && scene_host_set_sampler(s, sc.sampler, err);
 }
 
 /* ---- brute-force list: consecutive triangles in pairs, fields interleaved (vcm_core.h TriPair) ---- */

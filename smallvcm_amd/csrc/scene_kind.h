@@ -6,10 +6,14 @@
 // and adds the wrappers a kernel has instantiations for: WithLens (the kernels that hold the camera vertex, for a scene
 // with a thin lens) and WithPick (the kernels that choose a light or weigh an emitter hit, for a scene with a light-pick
 // table), WithPick over WithLens where a kernel has both, and WithLights over WithPick for a scene with a spot or a sphere
-// light (such a scene always has a table, so WithLights exists over the WithPick kinds alone).
+// light (such a scene always has a table, so WithLights exists over the WithPick kinds alone).  A scene with the Sobol
+// sampler takes, in every kernel that draws (kWrapSobol), ONE kind per kind of scene: WithSobol over the widest chain
+// of the other wrappers the kernel has, whatever else the scene holds; there lens, filter and table are run-time
+// branches (vcm_core.h WithSobol).  Kernels that draw nothing are launched as without it.
 #ifndef SMALLVCM_AMD_SCENE_KIND_H
 #define SMALLVCM_AMD_SCENE_KIND_H
 
+#include <type_traits>
 #include "vcm_core.h"
 
 namespace vcm {
@@ -56,18 +60,34 @@ constexpr bool scene_kind_is_rects(SceneKind k) { return k == SceneKind::Rects |
 template <class S> struct SceneTag { using type = S; };
 
 /* the wrappers a kernel is instantiated for */
-enum : unsigned { kWrapNone = 0, kWrapLens = 1, kWrapPick = 2 };
+enum : unsigned { kWrapNone = 0, kWrapLens = 1, kWrapPick = 2, kWrapSobol = 4 };
 
 /* the wrappers a context launches with; lights implies pick (wrappers_valid) */
-struct SceneWrappers { bool lens, pick, lights; };
+struct SceneWrappers { bool lens, pick, lights; bool sobol = false; };
 constexpr bool wrappers_valid(SceneWrappers w) { return !w.lights || w.pick; }
 static_assert(wrappers_valid({ false, false, false }) && wrappers_valid({ true, true, false }) && wrappers_valid({ false, true, true }),
               "what a scene without / with the spot and sphere lights launches");
 static_assert(!wrappers_valid({ false, false, true }), "no WithLights kernel exists without the table");
 
+/* the widest chain of wrappers a kernel of `Wrap` has over S: what WithSobol sits on */
+template <unsigned Wrap, class S> struct WidestChain {
+    using L = std::conditional_t<(Wrap & kWrapLens) != 0, WithLens<S>, S>;
+    using type = std::conditional_t<(Wrap & kWrapPick) != 0, WithLights<WithPick<L>>, L>;
+};
+static_assert(std::is_same_v<WidestChain<kWrapLens | kWrapPick, SceneRects>::type, WithLights<WithPick<WithLens<SceneRects>>>>, "K3, the path tracer, strict K1");
+static_assert(std::is_same_v<WidestChain<kWrapPick, SceneBvh>::type, WithLights<WithPick<SceneBvh>>>, "K1, k_connect_di");
+static_assert(std::is_same_v<WidestChain<kWrapLens, SceneList>::type, WithLens<SceneList>>, "k_connect_camera, eye light");
+static_assert(WithSobol<WidestChain<kWrapLens | kWrapPick, SceneListE>::type>::kSobol && WithSobol<WidestChain<kWrapLens | kWrapPick, SceneListE>::type>::kLens &&
+              WithSobol<WidestChain<kWrapLens | kWrapPick, SceneListE>::type>::kPick && WithSobol<WidestChain<kWrapLens | kWrapPick, SceneListE>::type>::kLights &&
+              WithSobol<WidestChain<kWrapLens | kWrapPick, SceneListE>::type>::kEnvMap, "the Sobol kind carries every branch");
+static_assert(!WithLights<WithPick<WithLens<SceneRects>>>::kSobol && !SceneRects::kSobol, "no other kind draws from it");
+
 template <unsigned Wrap, class S, class F> void with_wrappers(SceneWrappers w, F &f)
 {
-    if constexpr (Wrap & kWrapLens) {
+    if constexpr (Wrap & kWrapSobol) {
+        if (w.sobol) f(SceneTag<WithSobol<typename WidestChain<Wrap & ~kWrapSobol, S>::type>>{});
+        else with_wrappers<Wrap & ~kWrapSobol, S>(w, f);
+    } else if constexpr (Wrap & kWrapLens) {
         if (w.lens) with_wrappers<Wrap & ~kWrapLens, WithLens<S>>(w, f);
         else with_wrappers<Wrap & ~kWrapLens, S>(w, f);
     } else if constexpr (Wrap & kWrapPick) {

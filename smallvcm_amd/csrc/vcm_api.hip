@@ -184,6 +184,7 @@ struct vcm_ctx : Scratch {
     bool filter;                      /* the scene has a pixel filter: the WithLens kernels too (vcm_core.h kLens) */
     bool pick;                        /* lights are chosen from a table: the WithPick kernels */
     bool lights;                      /* the scene holds a spot or a sphere light: WithLights over WithPick (then pick is set) */
+    bool sobol;                       /* the scene asks for the Sobol sampler: the WithSobol kind of every kernel that draws */
     bool intPhong;                    /* every Phong exponent in use is an integer in [1, 65536]: the kernels whose pow is the binary
                                          exponentiation alone (detmath.h); otherwise the SceneList / SceneBvhG kernels and the general merge */
     /* feature buffers and denoiser (vcm_denoise.h): allocated by the first vcm_render_features / vcm_denoise */
@@ -212,7 +213,7 @@ struct vcm_ctx : Scratch {
 
 /* A ray-casting kernel is launched in the instantiation of the context's kind, under the wrappers it exists for (Wrap:
    scene_kind.h): f(tag) launches it with S = typename decltype(tag)::type.  What f evaluates, it evaluates once. */
-template <unsigned Wrap, class F> static void launch_kind(const vcm_ctx *c, F &&f) { with_scene_kind<Wrap>(c->kind, SceneWrappers{ c->lens || c->filter, c->pick, c->lights }, f); }
+template <unsigned Wrap, class F> static void launch_kind(const vcm_ctx *c, F &&f) { with_scene_kind<Wrap>(c->kind, SceneWrappers{ c->lens || c->filter, c->pick, c->lights, c->sobol }, f); }
 
 /* K4 of a context: k_merge_pairs or k_merge_walk (VCM_MERGE_*), with the pow its exponents allow */
 typedef void (*MergeKernel)(const DScene *, IterParams, GridStore, VertexStore, const int *, const int *, unsigned long long *, int, StampArgs);
@@ -775,6 +776,7 @@ static vcm_ctx *create_from_host(SceneHost *h, int algorithm, float radiusFactor
     c->filter = h->filterKind != VCM_FILTER_BOX;
     c->pick = h->pickMode != VCM_LIGHT_PICK_UNIFORM;
     c->lights = c->pick && scene_host_has_new_lights(*h);   /* such a scene always has a table (scene_host_lights_need_table) */
+    c->sobol = h->sampler == VCM_SAMPLER_SOBOL;
     scene_host_build_accel(*h, scene_host_force_bvh());
     /* VertexCM::VertexCM vertexcm.hxx:222-244 */
     switch (algorithm) {
@@ -888,6 +890,16 @@ vcm_ctx *vcm_create_sharded6(const vcm_scene_desc6 *scene, int algorithm, float 
     return create_from_host(h, algorithm, radiusFactor, radiusAlpha, seed, device, rank, worldSize);
 }
 
+vcm_ctx *vcm_create_sharded7(const vcm_scene_desc7 *scene, int algorithm, float radiusFactor, float radiusAlpha,
+                             int seed, int device, int rank, int worldSize)
+{
+    if (!scene) { fail("vcm_create7", "scene is NULL"); return NULL; }
+    SceneHost *h = new (std::nothrow) SceneHost();
+    std::string err;
+    if (!h || !scene_host_from_desc7(*scene, *h, err)) { delete h; fail("vcm_create7", err.c_str()); return NULL; }
+    return create_from_host(h, algorithm, radiusFactor, radiusAlpha, seed, device, rank, worldSize);
+}
+
 /* Which device a renderer-per-host-core host puts its next renderer on (vcm_next_device).  The reference's driver
  * builds one renderer per host core and runs them concurrently (smallvcm.cxx:61-72, :99-108): on a multi-GPU node the
  * drop-in deals them round-robin over the visible devices -- every GPU renders whole iterations of its renderers
@@ -951,6 +963,11 @@ vcm_ctx *vcm_create5(const vcm_scene_desc5 *scene, int algorithm, float radiusFa
 vcm_ctx *vcm_create6(const vcm_scene_desc6 *scene, int algorithm, float radiusFactor, float radiusAlpha, int seed)
 {
     return vcm_create_sharded6(scene, algorithm, radiusFactor, radiusAlpha, seed, next_device(true), 0, 1);
+}
+
+vcm_ctx *vcm_create7(const vcm_scene_desc7 *scene, int algorithm, float radiusFactor, float radiusAlpha, int seed)
+{
+    return vcm_create_sharded7(scene, algorithm, radiusFactor, radiusAlpha, seed, next_device(true), 0, 1);
 }
 
 void vcm_destroy(vcm_ctx *c)
@@ -1243,7 +1260,7 @@ static int flush_light_splats(vcm_ctx *c)
         F4 *list = c->dSplatList;
         if (c->prezeroed) HIPCHK(hipStreamWaitEvent(q, c->evZero, 0));
         else if (zero_ranges(q, pixCount, ((size_t)c->N + 1) * sizeof(int))) return -1;
-        launch_kind<kWrapLens>(c, [&](auto tag) {
+        launch_kind<kWrapLens | kWrapSobol>(c, [&](auto tag) {
             using S = typename decltype(tag)::type;
             hipLaunchKernelGGL((k_connect_camera<S>), dim3(task_blocks(c->nLocal)), dim3(256), 0, q, c->dScene, c->P, c->store,
                                (const int *)c->dSlotOfVertex, (const int *)c->dLocalTotal, c->dFb, c->dSplat, pixCount,
@@ -1314,13 +1331,13 @@ static int vcm_trace_light_impl(vcm_ctx *c)
     const bool wf = !c->strictOrder;
     if (!wf && join_splats(c)) return -1;   /* the fused K1 splats straight into dFb: behind a K5 the last (aside) iteration left in flight */
     if (wf)
-        launch_kind<kWrapPick>(c, [&](auto tag) {
+        launch_kind<kWrapPick | kWrapSobol>(c, [&](auto tag) {
             using S = typename decltype(tag)::type;
             hipLaunchKernelGGL((k_light_trace<1, S>), dim3(blocks), dim3(VCM_TRACE_BLOCK), 0, c->stream, c->dScene, c->P, c->store,
                                c->dFb, c->dRngLight, c->dStats, chunk, take_stamps(c, c->stream), c->vs.count + 16, c->dHdr);
         });
     else
-        launch_kind<kWrapLens | kWrapPick>(c, [&](auto tag) {
+        launch_kind<kWrapLens | kWrapPick | kWrapSobol>(c, [&](auto tag) {
             using S = typename decltype(tag)::type;
             hipLaunchKernelGGL((k_light_trace<0, S>), dim3(blocks), dim3(VCM_TRACE_BLOCK), 0, c->stream, c->dScene, c->P, c->store,
                                c->dFb, c->dRngLight, c->dStats, chunk, take_stamps(c, c->stream), c->vs.count + 16, c->dHdr);
@@ -1720,13 +1737,13 @@ static int vcm_trace_camera_impl(vcm_ctx *c)
     if (mark(c, EV_CAMERA_K0)) return -1;
     if (c->renderer) {   /* PathTracer / EyeLight: colour + jittered pixel per path; K5 adds them in path order */
         if (c->renderer == 1)
-            launch_kind<kWrapLens | kWrapPick>(c, [&](auto tag) {
+            launch_kind<kWrapLens | kWrapPick | kWrapSobol>(c, [&](auto tag) {
                 using S = typename decltype(tag)::type;
                 hipLaunchKernelGGL((k_path_trace<S>), dim3(blocks), dim3(VCM_TRACE_BLOCK), 0, c->stream, c->dScene, c->P, c->dCamOut,
                                    c->dRngCam, c->dStats, chunk, take_stamps(c, c->stream), c->vs.count + 8);
             });
         else
-            launch_kind<kWrapLens>(c, [&](auto tag) {
+            launch_kind<kWrapLens | kWrapSobol>(c, [&](auto tag) {
                 using S = typename decltype(tag)::type;
                 hipLaunchKernelGGL((k_eye_light<S>), dim3(2048), dim3(256), 0, c->stream, c->dScene, c->P, c->dCamOut, c->dRngCam,
                                    c->dStats, take_stamps(c, c->stream));
@@ -1748,7 +1765,7 @@ static int vcm_trace_camera_impl(vcm_ctx *c)
             if (c->prezeroed) HIPCHK(hipStreamWaitEvent(c->stream, c->evZero, 0));
             else if (zero_ranges(c->stream, c->dQueryCount, ((size_t)c->P.nBuckets + 1) * sizeof(int))) return -1;
         }
-        launch_kind<kWrapLens | kWrapPick>(c, [&](auto tag) {
+        launch_kind<kWrapLens | kWrapPick | kWrapSobol>(c, [&](auto tag) {
             using S = typename decltype(tag)::type;
             hipLaunchKernelGGL((k_camera_trace<1, S>), dim3(blocks), dim3(VCM_TRACE_BLOCK), 0, c->stream, c->dScene, c->P,
                                c->store, grid_of(c), c->vs, c->dCamOut, c->dCamMask, c->dRngCam, c->dStats, chunk, take_stamps(c, c->stream));
@@ -1805,7 +1822,7 @@ static int vcm_trace_camera_impl(vcm_ctx *c)
                 HIPCHK(hipEventRecord(c->evSplatDone, c->splat));   /* also behind the light splats: same stream */
                 c->splatInFlight = true;
             }
-            launch_kind<kWrapPick>(c, [&](auto tag) {
+            launch_kind<kWrapPick | kWrapSobol>(c, [&](auto tag) {
                 using S = typename decltype(tag)::type;
                 hipLaunchKernelGGL((k_connect_di<S>), dim3(task_blocks(c->nLocal)), dim3(VCM_TASK_BLOCK), 0, c->stream, c->dScene, c->P, c->vs,
                                    c->dStats, c->scatteredInDI ? (const int *)c->dQueryStart : (const int *)NULL,
@@ -1815,7 +1832,7 @@ static int vcm_trace_camera_impl(vcm_ctx *c)
         if (mark(c, EV_CONNECT_K1)) return -1;
     } else {
         if (c->useVM && !c->gridBuilt) return fail("vcm_trace_camera", "strict mode merges inside the camera pass: call vcm_build_grid first");
-        launch_kind<kWrapLens | kWrapPick>(c, [&](auto tag) {
+        launch_kind<kWrapLens | kWrapPick | kWrapSobol>(c, [&](auto tag) {
             using S = typename decltype(tag)::type;
             hipLaunchKernelGGL((k_camera_trace<0, S>), dim3(blocks), dim3(VCM_TRACE_BLOCK), 0, c->stream, c->dScene, c->P,
                                c->store, grid_of(c), c->vs, c->dCamOut, c->dCamMask, c->dRngCam, c->dStats, chunk, take_stamps(c, c->stream));
@@ -3024,6 +3041,15 @@ __global__ void k_kat(const DScene *__restrict__ scp, int op, int n, const float
     kat_eval(*static_cast<const SC *>(scp), op, a, r);
     for (int k = 0; k < VCM_KAT_FLOATS; k++) out[(size_t)i * VCM_KAT_FLOATS + k] = r[k];
 }
+__global__ void k_kat_sampler(int n, const float *in, float *out)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    float a[VCM_KAT_FLOATS], r[VCM_KAT_FLOATS];
+    for (int k = 0; k < VCM_KAT_FLOATS; k++) a[k] = in[(size_t)i * VCM_KAT_FLOATS + k];
+    kat_sampler(a, r);
+    for (int k = 0; k < VCM_KAT_FLOATS; k++) out[(size_t)i * VCM_KAT_FLOATS + k] = r[k];
+}
 __global__ void k_philox_spec(uint32_t seed, uint32_t iter, uint32_t kind, int nPaths, int nFloats, float *out)
 {
     const int p = blockIdx.x * blockDim.x + threadIdx.x;
@@ -3063,10 +3089,13 @@ int vcm_debug_kat(vcm_ctx *c, int op, int n, const float *in, float *out)
     HIPCHK(hipMalloc((void **)&din, bytes));
     HIPCHK(hipMalloc((void **)&dout, bytes));
     HIPCHK(hipMemcpy(din, in, bytes, hipMemcpyHostToDevice));
-    launch_kind<kWrapLens | kWrapPick>(c, [&](auto tag) {
-        using S = typename decltype(tag)::type;
-        hipLaunchKernelGGL((k_kat<S>), dim3((n + 63) / 64), dim3(64), 0, 0, (const DScene *)c->dScene, op, n, (const float *)din, dout);
-    });
+    if (op == VCM_KAT_SAMPLER)
+        hipLaunchKernelGGL(k_kat_sampler, dim3((n + 63) / 64), dim3(64), 0, 0, n, (const float *)din, dout);
+    else
+        launch_kind<kWrapLens | kWrapPick>(c, [&](auto tag) {   /* no op of kat_eval draws: the kinds of the scene without its sampler */
+            using S = typename decltype(tag)::type;
+            hipLaunchKernelGGL((k_kat<S>), dim3((n + 63) / 64), dim3(64), 0, 0, (const DScene *)c->dScene, op, n, (const float *)din, dout);
+        });
     hipError_t e = hipGetLastError();
     if (e == hipSuccess) e = hipMemcpy(out, dout, bytes, hipMemcpyDeviceToHost);
     (void)hipFree(din); (void)hipFree(dout);
@@ -3098,6 +3127,13 @@ int vcm_debug_pixel_filter(vcm_ctx *c, int *kind, float *radius)
     if (!c) return fail("vcm_debug_pixel_filter", "bad argument");
     if (kind) *kind = c->scene->filterKind;
     if (radius) *radius = c->scene->filterRadius;
+    return 0;
+}
+
+int vcm_debug_sampler(vcm_ctx *c, int *kind)
+{
+    if (!c || !kind) return fail("vcm_debug_sampler", "bad argument");
+    *kind = c->sobol ? VCM_SAMPLER_SOBOL : VCM_SAMPLER_PHILOX;
     return 0;
 }
 

@@ -18,6 +18,7 @@
 #include "vcm_math.h"
 #include "detmath.h"
 #include "philox.h"
+#include "sobol.h"
 
 namespace vcm {
 
@@ -370,6 +371,7 @@ struct DScene {
     static constexpr bool kLens = false;
     static constexpr bool kPick = false;
     static constexpr bool kLights = false;
+    static constexpr bool kSobol = false;
     int nPrims, nMaterials, nLights, backgroundLight;
     float sceneCenter[3], sceneRadius, invSceneRadiusSqr;
     vcm_camera camera;
@@ -399,6 +401,8 @@ struct DScene {
        the kind of the offset density g and its support in pixels (filter_offset below) */
     int filterKind;
     float filterRadius;
+    /* the sampler (vcm_sampler; VCM_SAMPLER_PHILOX: philox.h's white noise, VCM_SAMPLER_SOBOL: sobol.h) */
+    int samplerKind;
     template <class T> VCM_HD const T *at(long long off) const { return reinterpret_cast<const T *>(reinterpret_cast<const char *>(this) + off); }
     VCM_HD const vcm_prim *prims() const { return at<vcm_prim>(offPrims); }
     VCM_HD const vcm_material *materials() const { return at<vcm_material>(offMaterials); }
@@ -479,7 +483,7 @@ template <class S> struct WithLens : S { static constexpr bool kLens = true; };
 template <class S> struct WithPick : S { static constexpr bool kPick = true; };
 #if defined(__HIP_DEVICE_COMPILE__)
 #define VCM_PICK_KIND(S) (S::kPick)
-#define VCM_PICK_ON(S, sc) (S::kPick)
+#define VCM_PICK_ON(S, sc) (S::kPick && (!S::kSobol || (sc).pickMode != 0))
 #else
 #define VCM_PICK_KIND(S) true
 #define VCM_PICK_ON(S, sc) ((sc).pickMode != 0)
@@ -495,6 +499,44 @@ template <class S> struct WithLights : S { static constexpr bool kLights = true;
 #else
 #define VCM_LIGHTS_KIND(S) true
 #endif
+
+/* kSobol: the paths draw from the Owen-scrambled Sobol sampler (DScene::samplerKind == VCM_SAMPLER_SOBOL; sobol.h,
+   DESIGN.md "Sampler").  Every kernel that draws exists in ONE such kind per kind of scene, over the widest chain of the
+   wrappers above it has instantiations for (scene_kind.h), whatever else the scene holds: inside it the lens, the
+   filter and the light-pick table are run-time branches on scene constants (the table only here: VCM_PICK_ON), and
+   the spot and sphere branches are present.  The kinds without the wrapper hold the Philox draws and nothing else --
+   their code is what it was before there was a second sampler.  The host builds take the branch at run time. */
+template <class S> struct WithSobol : S { static constexpr bool kSobol = true; };
+#if defined(__HIP_DEVICE_COMPILE__)
+#define VCM_SOBOL_ON(S, sc) (S::kSobol)
+#else
+#define VCM_SOBOL_ON(S, sc) ((sc).samplerKind == VCM_SAMPLER_SOBOL)
+#endif
+/* tests/host_emul_sampler records where the draw groups start (group 0 = light start, 1 = direct illumination,
+   2 = scattering) */
+#if !defined(VCM_SAMPLER_TRACE)
+#define VCM_SAMPLER_TRACE(group, kind, k0) ((void)0)
+#endif
+/* The floats k0 .. k0+n-1 of a path's stream under the scene's sampler, and the position a draw group starts at: under
+   Sobol the next one of parity `odd`, so that the group's 2-D uses are pairs of the sequence; under Philox k itself. */
+template <class S>
+VCM_HD void path_peek(const S &sc, const PathRng &r, uint32_t k0, float *out, int n)
+{
+    if (VCM_SOBOL_ON(S, sc)) sobol_peek(r, k0, out, n);
+    else rng_peek(r, k0, out, n);
+}
+template <class S>
+VCM_HD void path_peek_block(const S &sc, const PathRng &r, uint32_t k0, float *out, int n)
+{
+    if (VCM_SOBOL_ON(S, sc)) sobol_peek(r, k0, out, n);
+    else rng_peek_block(r, k0, out, n);
+}
+template <class S>
+VCM_HD uint32_t path_align(const S &sc, uint32_t k, uint32_t odd)
+{
+    if (VCM_SOBOL_ON(S, sc)) return sobol_align(k, odd);
+    return k;
+}
 
 /* ---- the scene's small tables in LDS ----
  * A lane's material, the primitive its ray ends on, the light it samples are GATHERS (the index is per lane): as global
@@ -617,7 +659,7 @@ VCM_HD void stage_pick_tables(const S &sc)
 {
 #if defined(__HIP_DEVICE_COMPILE__)
     if constexpr (S::kPick) {
-        if (sc.nLights <= VCM_LDS_PICK) {   /* wave-uniform */
+        if (VCM_PICK_ON(S, sc) && sc.nLights <= VCM_LDS_PICK) {   /* wave-uniform (a Sobol kind may have no table) */
             const int t = (int)threadIdx.x, nt = (int)blockDim.x;
             const uint32_t *cdf = (const uint32_t *)sc.pickCdf(), *pmf = (const uint32_t *)sc.pickPmf();
             for (int i = t; i <= sc.nLights; i += nt) g_ldsPick[i] = cdf[i];
@@ -2337,7 +2379,9 @@ VCM_HD bool sample_scattering(const S &sc, const IterParams &P, bool lightSample
        the sample is non-zero: 4 consecutive floats, generated at one site */
     float rnd[4];
     RC_DECL;
-    rng_peek(rng, rng.k, rnd, 4);
+    rng.k = path_align(sc, rng.k, 0u);   /* Sobol: (x, y), (z, rr) are pairs */
+    VCM_SAMPLER_TRACE(2, rng.kind, rng.k);
+    path_peek(sc, rng, rng.k, rnd, 4);
     RC_MARK(lightSample ? 23 : 27);
     rng.k += 3u;
     const float r0 = rnd[0], r1 = rnd[1], r2 = rnd[2];
@@ -2381,7 +2425,9 @@ VCM_HD void generate_light_sample(const S &sc, const IterParams &P, PathRng &rng
     const int lightCount = sc.nLights;
     float lightPickProb = 1.f / lightCount;
     float rnd[5];   /* :822-824 */
-    rng_peek(rng, rng.k, rnd, 5);
+    rng.k = path_align(sc, rng.k, 1u);   /* Sobol: starts at k = 1, direction = pair (2, 3), position = (4, 5) */
+    VCM_SAMPLER_TRACE(0, rng.kind, rng.k);
+    path_peek(sc, rng, rng.k, rnd, 5);
     rng.k += 5u;
     const int lightID = pick_light(sc, rnd[0], lightPickProb);
     const float dx = rnd[1];
@@ -2412,11 +2458,12 @@ VCM_HD void generate_light_sample(const S &sc, const IterParams &P, PathRng &rng
  * meaning: kind 2 = a camera path's lens point (block 0, keyed by the global path), kind 3 = the lens point of a light
  * vertex's connection to the camera (keyed by the global light path, block = the vertex's pathLength).  Both are
  * functions of (seed, local iteration, path, vertex), so strict and wavefront order and every shard draw the same. */
-VCM_HD void lens_rnd(const IterParams &P, uint32_t kind, uint32_t path, uint32_t block, float *r)
+template <class S>
+VCM_HD void lens_rnd(const S &sc, const IterParams &P, uint32_t kind, uint32_t path, uint32_t block, float *r)
 {
     PathRng rng;
     rng_init(rng, P.seed, P.localIter, path, kind);
-    rng_peek_block(rng, block << 2, r, 2);
+    path_peek_block(sc, rng, block << 2, r, 2);
 }
 /* the lens point of the sample (r0, r1): concentric disc, scaled by the aperture radius, in the lens plane */
 VCM_HD V3 lens_point(const DScene &sc, float r0, float r1)
@@ -2458,8 +2505,22 @@ VCM_HD bool lens_project(const DScene &sc, V3 l, V3 x, V3 &raster)
  * filters that read them, 2 * vertex + 1 (r[4..7]).  The eight floats travel as scalars: as an array behind a pointer
  * they cost every kernel that holds them 16 bytes of scratch per lane. */
 struct FilterDraw { float r0, r1, r2, r3, r4, r5, r6, r7; };
-VCM_HD void filter_rnd(const IterParams &P, uint32_t kind, uint32_t path, uint32_t vertex, int filterKind, FilterDraw &d)
+template <class S>
+VCM_HD void filter_rnd(const S &sc, const IterParams &P, uint32_t kind, uint32_t path, uint32_t vertex, int filterKind, FilterDraw &d)
 {
+    if (VCM_SOBOL_ON(S, sc)) {   /* the same positions 8 * vertex .. + 7 of the stream: four pairs, two for the filters that read four floats */
+        PathRng rng;
+        rng_init(rng, P.seed, P.localIter, path, kind);
+        float r[4];
+        sobol_peek(rng, vertex << 3, r, 4);
+        d.r0 = r[0]; d.r1 = r[1]; d.r2 = r[2]; d.r3 = r[3];
+        d.r4 = d.r5 = d.r6 = d.r7 = 0.5f;
+        if (filterKind == VCM_FILTER_BSPLINE) {
+            sobol_peek(rng, (vertex << 3) + 4u, r, 4);
+            d.r4 = r[0]; d.r5 = r[1]; d.r6 = r[2]; d.r7 = r[3];
+        }
+        return;
+    }
     uint32_t w0, w1, w2, w3;   /* PathRng's stream (philox.h): key = (seed, localIter), counter = (path, kind, block, 0) */
     philox4x32_10(path, kind, vertex << 1, 0u, P.seed, P.localIter, w0, w1, w2, w3);
     d.r0 = rng_word_to_float(w0); d.r1 = rng_word_to_float(w1); d.r2 = rng_word_to_float(w2); d.r3 = rng_word_to_float(w3);
@@ -2484,11 +2545,12 @@ VCM_HD void filter_offset(int filterKind, float radius, const FilterDraw &d, flo
     }
 }
 /* the raster point a camera path's ray goes through: its sample moved by a kind-4 draw */
-VCM_HD void filter_camera_sample(const DScene &sc, const IterParams &P, int pathIdx, float &rx, float &ry)
+template <class S>
+VCM_HD void filter_camera_sample(const S &sc, const IterParams &P, int pathIdx, float &rx, float &ry)
 {
     FilterDraw d;
     float ox, oy;
-    filter_rnd(P, 4u, (uint32_t)pathIdx, 0u, sc.filterKind, d);
+    filter_rnd(sc, P, 4u, (uint32_t)pathIdx, 0u, sc.filterKind, d);
     filter_offset(sc.filterKind, sc.filterRadius, d, ox, oy);
     rx = rx + ox; ry = ry + oy;
 }
@@ -2524,7 +2586,7 @@ VCM_HD void connect_to_camera(const SC &sc, const IterParams &P, const SubPathSt
     V3 ip;
     if (VCM_LENS_ON(SC, sc)) {
         float r[2];
-        lens_rnd(P, 3u, (uint32_t)lensPath, st.pathLength, r);
+        lens_rnd(sc, P, 3u, (uint32_t)lensPath, st.pathLength, r);
         camPos = lens_point(sc, r[0], r[1]);
         if (!lens_project(sc, camPos, hitpoint, ip)) return;
     }
@@ -2537,7 +2599,7 @@ VCM_HD void connect_to_camera(const SC &sc, const IterParams &P, const SubPathSt
         if (!(ip.x >= -fr && ip.y >= -fr && ip.x < cam.resolution[0] + fr && ip.y < cam.resolution[1] + fr)) return;
         FilterDraw d;
         float ox, oy;
-        filter_rnd(P, 5u, (uint32_t)lensPath, st.pathLength, sc.filterKind, d);
+        filter_rnd(sc, P, 5u, (uint32_t)lensPath, st.pathLength, sc.filterKind, d);
         filterPixel = filter_splat_pixel(sc, ip.x, ip.y, d, ox, oy);
         if (filterPixel < 0) return;
     } else if (!(ip.x >= 0 && ip.y >= 0 && ip.x < cam.resolution[0] && ip.y < cam.resolution[1])) return;
@@ -3236,7 +3298,7 @@ VCM_HD void camera_path_begin(const S &sc, const IterParams &P, CameraPath &cp, 
     const int x = pathIdx % P.resX;
     const int y = pathIdx / P.resX;
     float jit[2];   /* :576, the first two floats of the path */
-    rng_peek_block(cp.rng, 0u, jit, 2);
+    path_peek_block(sc, cp.rng, 0u, jit, 2);
     cp.rng.k = 2u;
     const float jx = jit[0];
     const float jy = jit[1];
@@ -3249,7 +3311,7 @@ VCM_HD void camera_path_begin(const S &sc, const IterParams &P, CameraPath &cp, 
     V3 dir = normalize(worldRaster - org);
     if (VCM_LENS_ON(S, sc)) {
         float r[2];
-        lens_rnd(P, 2u, (uint32_t)pathIdx, 0u, r);
+        lens_rnd(sc, P, 2u, (uint32_t)pathIdx, 0u, r);
         lens_ray(sc, dir, r[0], r[1], org, dir);
     }
     const float cosAtCamera = dot(ld3(cam.forward), dir);
@@ -3328,8 +3390,9 @@ VCM_HD bool camera_path_step(const SC &sc, const IterParams &P, CameraPath &cp, 
             uint32_t diK = 0u;
             int hasDI = 0;
             if (P.useVC && st.pathLength + 1 >= P.minLen) {
-                diK = cp.rng.k;
-                cp.rng.k += 3u;
+                diK = path_align(sc, cp.rng.k, 1u);   /* the ALIGNED position: K3b draws what the strict order draws */
+                VCM_SAMPLER_TRACE(1, cp.rng.kind, diK);
+                cp.rng.k = diK + 3u;
                 hasDI = 1;
             }
             /* the light vertices this camera vertex connects to (:508-521) */
@@ -3413,7 +3476,9 @@ VCM_HD bool camera_path_step(const SC &sc, const IterParams &P, CameraPath &cp, 
         if (!bsdf.isDelta && P.useVC) {   /* :487-494 */
             if (st.pathLength + 1 >= P.minLen) {
                 float rnd[3];
-                rng_peek(cp.rng, cp.rng.k, rnd, 3);
+                cp.rng.k = path_align(sc, cp.rng.k, 1u);   /* Sobol: (x, y) is a pair */
+                VCM_SAMPLER_TRACE(1, cp.rng.kind, cp.rng.k);
+                path_peek(sc, cp.rng, cp.rng.k, rnd, 3);
                 cp.rng.k += 3u;
                 cp.color = cp.color + st.throughput * direct_illumination(sc, P, rnd[0], rnd[1], rnd[2], st, hitPoint, bsdf, ls);
             }
@@ -3481,7 +3546,7 @@ VCM_HD V3 eval_di_task(const SC &sc, const IterParams &P, const VertexStore &vs,
     PathRng rng;
     rng_init(rng, P.seed, P.localIter, (uint32_t)(P.p0 + (int)v.lp), 1u);
     float rnd[3];
-    rng_peek(rng, v.diK, rnd, 3);
+    path_peek(sc, rng, VCM_SOBOL_ON(SC, sc) ? (v.diK | 1u) : v.diK, rnd, 3);   /* (| 1: the record holds an odd position; it tells the compiler) */
     return v.throughput * direct_illumination(sc, P, rnd[0], rnd[1], rnd[2], v.st, v.hit, v.bsdf, ls);
 }
 /* the addend of :523  (color += throughput * lightVertex.mThroughput * ConnectVertices(...)) */
@@ -3567,7 +3632,7 @@ VCM_HD void pt_path_begin(const S &sc, const IterParams &P, PtPath &pp, int loca
     pp.lp = localPath;
     rng_init(pp.rng, P.seed, P.localIter, (uint32_t)pathIdx, 1u);
     float jit[2];
-    rng_peek_block(pp.rng, 0u, jit, 2);
+    path_peek_block(sc, pp.rng, 0u, jit, 2);
     pp.rng.k = 2u;
     pp.sx = float(pathIdx % P.resX) + jit[0];   /* :56-59 */
     pp.sy = float(pathIdx / P.resX) + jit[1];
@@ -3578,7 +3643,7 @@ VCM_HD void pt_path_begin(const S &sc, const IterParams &P, PtPath &pp, int loca
     pp.dir = normalize(worldRaster - pp.org);
     if (VCM_LENS_ON(S, sc)) {   /* the thin lens: a kind-2 draw (camera_path_begin) */
         float r[2];
-        lens_rnd(P, 2u, (uint32_t)pathIdx, 0u, r);
+        lens_rnd(sc, P, 2u, (uint32_t)pathIdx, 0u, r);
         lens_ray(sc, pp.dir, r[0], r[1], pp.org, pp.dir);
     }
     pp.weight = sp3(1.f);
@@ -3630,7 +3695,9 @@ VCM_HD bool pt_path_step(const SC &sc, const IterParams &P, PtPath &pp, LaneStat
     if (bsdf.contProb == 0.f) return false;        /* :134 */
     if (!bsdf.isDelta && pp.pathLength + 1 >= P.minLen) {   /* next event estimation :138-179 */
         float rnd[3];
-        rng_peek(pp.rng, pp.rng.k, rnd, 3);
+        pp.rng.k = path_align(sc, pp.rng.k, 1u);   /* Sobol: (x, y) is a pair */
+        VCM_SAMPLER_TRACE(1, pp.rng.kind, pp.rng.k);
+        path_peek(sc, pp.rng, pp.rng.k, rnd, 3);
         pp.rng.k += 3u;
         float lightPickProb = uniformPickProb;
         const int lightID = pick_light(sc, rnd[0], lightPickProb);
@@ -3657,7 +3724,9 @@ VCM_HD bool pt_path_step(const SC &sc, const IterParams &P, PtPath &pp, LaneStat
     }
     {   /* continue the random walk :182-212 */
         float rnd[4];
-        rng_peek(pp.rng, pp.rng.k, rnd, 4);
+        pp.rng.k = path_align(sc, pp.rng.k, 0u);   /* Sobol: (x, y), (z, rr) are pairs */
+        VCM_SAMPLER_TRACE(2, pp.rng.kind, pp.rng.k);
+        path_peek(sc, pp.rng, pp.rng.k, rnd, 4);
         pp.rng.k += 3u;
         float pdf, cosThetaOut;
         uint32_t sampledEvent;
@@ -3693,7 +3762,7 @@ VCM_HD bool eyelight_path(const SC &sc, const IterParams &P, int localPath, V3 &
     if (P.iteration != 1) {   /* :60-61: iteration 1 samples the pixel centres and draws nothing */
         PathRng rng;
         rng_init(rng, P.seed, P.localIter, (uint32_t)pathIdx, 1u);
-        rng_peek_block(rng, 0u, jit, 2);
+        path_peek_block(sc, rng, 0u, jit, 2);
         floatsDrawn = 2u;
     }
     sx = float(pathIdx % P.resX) + jit[0];
@@ -3706,7 +3775,7 @@ VCM_HD bool eyelight_path(const SC &sc, const IterParams &P, int localPath, V3 &
     ray.dir = normalize(worldRaster - ray.org);
     if (VCM_LENS_ON(SC, sc)) {   /* the thin lens draws its kind-2 sample in every iteration, the first included */
         float r[2];
-        lens_rnd(P, 2u, (uint32_t)pathIdx, 0u, r);
+        lens_rnd(sc, P, 2u, (uint32_t)pathIdx, 0u, r);
         lens_ray(sc, ray.dir, r[0], r[1], ray.org, ray.dir);
     }
     ray.tmin = 0;

@@ -132,5 +132,15 @@ VCM_HD void kat_eval(const SC &sc, int op, const float *in, float *out)
     }
 }
 
+/* VCM_KAT_SAMPLER: the Sobol sampler's float and word for (seed, i, path, kind, k), integers carried as bit patterns.  A
+   function of its own, not a case of kat_eval: it needs no scene, and the kernels of kat_eval stay what they were. */
+VCM_HD void kat_sampler(const float *in, float *out)
+{
+    for (int i = 0; i < VCM_KAT_FLOATS; i++) out[i] = 0.f;
+    const uint32_t w = sobol_word(f2u(in[0]), f2u(in[1]), f2u(in[2]), f2u(in[3]), f2u(in[4]));
+    out[0] = rng_word_to_float(w);
+    out[1] = u2f(w);
+}
+
 } // namespace vcm
 #endif

@@ -12,7 +12,7 @@ import os
 
 import numpy as np
 
-from ._abi import PIXEL_FILTERS, PixelFilter, SceneDesc, Stats
+from ._abi import PIXEL_FILTERS, PixelFilter, SAMPLER_NAMES, SAMPLERS, Sampler, SceneDesc, Stats
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 FARM_LIB_PATH = os.environ.get("SMALLVCM_AMD_FARM_LIB") or os.path.join(_HERE, "host", "libsmallvcm_amd_farm.so")
@@ -24,7 +24,7 @@ class FarmConfig(C.Structure):
                 ("baseSeed", C.c_int), ("minLen", C.c_uint), ("maxLen", C.c_uint), ("iterations", C.c_int), ("warmup", C.c_int),
                 ("sameWindow", C.c_int), ("ranks", C.c_int), ("firstRank", C.c_int), ("localRanks", C.c_int),
                 ("devices", C.c_int * MAX_RANKS), ("shards", C.c_int), ("inflight", C.c_int), ("collectives", C.c_int),
-                ("uniqueIds", C.c_void_p), ("nUniqueIds", C.c_int), ("filter", PixelFilter)]
+                ("uniqueIds", C.c_void_p), ("nUniqueIds", C.c_int), ("filter", PixelFilter), ("sampler", Sampler)]
 
 
 class FarmResult(C.Structure):
@@ -62,10 +62,11 @@ def unique_ids(n):
 
 def farm_render(scene, algorithm, iterations, ranks, shards, inflight, devices=None, first_rank=0, warmup=0, same_window=False,
                 collectives="rccl", ids=None, radius_factor=0.003, radius_alpha=0.75, seed=1234, min_len=0, max_len=10,
-                want_image=True, pixel_filter=None):
-    """-> dict(wall_s, renderers, rccl_ranks, rank_iteration_ms, stats, image).  `devices`: the HIP device of each rank
+                want_image=True, pixel_filter=None, sampler=None):
+    """-> dict(wall_s, renderers, rccl_ranks, rank_iteration_ms, stats, image, sampler).  `devices`: the HIP device of each rank
     hosted by this process (default: all `ranks` ranks, device = rank).  `pixel_filter`: (kind, radius) with kind "tent" or
-    "bspline" (include/smallvcm_amd.h vcm_pixel_filter) for every renderer; None: the reference's box."""
+    "bspline" (include/smallvcm_amd.h vcm_pixel_filter) for every renderer; None: the reference's box.  `sampler`: "sobol" or "philox" (include/smallvcm_amd.h vcm_sampler) for every
+    renderer; None: philox."""
     L = load_farm_library()
     devices = list(range(ranks)) if devices is None else list(devices)
     cfg = FarmConfig()
@@ -78,6 +79,10 @@ def farm_render(scene, algorithm, iterations, ranks, shards, inflight, devices=N
     cfg.shards, cfg.inflight, cfg.collectives = shards, inflight, 0 if collectives == "rccl" else 1
     if pixel_filter is not None:
         cfg.filter = PixelFilter(PIXEL_FILTERS[pixel_filter[0]], float(pixel_filter[1]))
+    if sampler is not None:
+        if sampler not in SAMPLERS:
+            raise ValueError("farm_render: sampler must be 'sobol' or 'philox'")
+        cfg.sampler = Sampler(SAMPLERS[sampler])
     keep = None
     if ids is not None:
         keep = C.create_string_buffer(ids, len(ids))
@@ -90,4 +95,5 @@ def farm_render(scene, algorithm, iterations, ranks, shards, inflight, devices=N
     if rc != 0:
         raise RuntimeError("smallvcm_amd: vcm_farm_render failed: %s" % L.vcm_farm_last_error().decode())
     return {"wall_s": res.wallSeconds, "renderers": res.renderers, "rccl_ranks": res.rcclRanks,
-            "rank_iteration_ms": [float(res.rankIterationMs[r]) for r in range(ranks)], "stats": res.meanStats.asdict(), "image": img}
+            "rank_iteration_ms": [float(res.rankIterationMs[r]) for r in range(ranks)], "stats": res.meanStats.asdict(), "image": img,
+            "sampler": SAMPLER_NAMES[cfg.sampler.kind]}

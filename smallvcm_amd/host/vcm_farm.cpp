@@ -675,7 +675,15 @@ bool rank_main(RankArgs &a)
     for (int k = 0; k < cfg.inflight; k++) {
         Slot &sl = slots[(size_t)k];
         const int rid = a.group * cfg.inflight + k;
-        if (cfg.filter.kind != VCM_FILTER_BOX) {   // a pixel filter: the same scene as a version-6 description (the arrays stay in cfg.scene)
+        if (cfg.sampler.kind != VCM_SAMPLER_PHILOX) {   // a sampler: the same scene as a version-7 description (the arrays stay in cfg.scene)
+            vcm_scene_desc7 d7;
+            memset(&d7, 0, sizeof(d7));
+            scene_as_desc2(cfg.scene, d7.base.base.base.base.base);
+            d7.base.filter = cfg.filter.kind != VCM_FILTER_BOX ? &cfg.filter : NULL;
+            d7.sampler = &cfg.sampler;
+            sl.ctx = vcm_create_sharded7(&d7, cfg.algorithm, cfg.radiusFactor, cfg.radiusAlpha, cfg.baseSeed + rid, a.device,
+                                         a.shard, cfg.shards);
+        } else if (cfg.filter.kind != VCM_FILTER_BOX) {   // a pixel filter: the same scene as a version-6 description (the arrays stay in cfg.scene)
             vcm_scene_desc6 d6;
             memset(&d6, 0, sizeof(d6));
             vcm_scene_desc2 &b = d6.base.base.base.base;
@@ -909,6 +917,7 @@ int vcm_farm_render(const vcm_farm_config *c, vcm_farm_result *out, float *image
     fc.devices.assign(c->devices, c->devices + c->localRanks);
     fc.shards = c->shards; fc.inflight = c->inflight; fc.rccl = c->collectives == 0;
     fc.filter = c->filter;
+    fc.sampler = c->sampler;
     if (c->uniqueIds && c->nUniqueIds > 0)
         fc.uniqueIds.assign((const char *)c->uniqueIds, (const char *)c->uniqueIds + (size_t)c->nUniqueIds * sizeof(ncclUniqueId));
     const FarmResult r = farm_render(fc);

@@ -78,6 +78,7 @@ struct FarmConfig {
     bool sameWindow;
     std::vector<char> uniqueIds;   // empty: all ranks are local; else (1 + groups) ids of vcm_farm_unique_id_bytes() each
     vcm_pixel_filter filter = { VCM_FILTER_BOX, 0.f };   // the pixel filter of every renderer (vcm_create_sharded6); BOX: vcm_create_sharded
+    vcm_sampler sampler = { VCM_SAMPLER_PHILOX };        // the sampler of every renderer (vcm_create_sharded7); PHILOX: as without one
 };
 
 struct FarmResult {

@@ -40,6 +40,10 @@
 // and on the light splats; it overrides a scene file's `filter` directive, and with --gpus every renderer of the farm
 // takes it.  The guide images of --features-out stay unfiltered.
 //
+// --sampler sobol|philox: where the paths' random floats come from (vcm_sampler, vcm_scene_desc7): the Owen-scrambled
+// Sobol sequence or the default white noise; it overrides a scene file's `sampler` directive, and with --gpus every
+// renderer of the farm takes it.
+//
 // --denoise [passes]: the image goes through the edge-avoiding a-trous filter (vcm_denoise: vcm_denoise_defaults with
 // `passes`, --denoise-sigma's sigmaColor,sigmaNormal,sigmaDepth and --no-demodulate applied) before it is written to
 // -o; the unfiltered image is written beside it as <name>.noisy.<ext>.  --features-out P writes the first-hit guide
@@ -124,6 +128,7 @@ int main(int argc, char **argv)
     float pickMix = 0.f;
     bool havePickMix = false, pickReport = false;
     std::string filterName;
+    std::string samplerName;
     float filterRadius = 0.f;
     bool denoise = false;
     vcm_denoise_params dn;
@@ -183,6 +188,11 @@ int main(int argc, char **argv)
             char *e = NULL;
             filterRadius = strtof(argv[++i], &e);
             if ((filterName != "tent" && filterName != "bspline") || e == argv[i] || *e) { fprintf(stderr, "vcm_render: --filter tent|bspline R\n"); return 2; }
+        }
+        else if (a == "--sampler") {
+            need(1);
+            samplerName = argv[++i];
+            if (samplerName != "sobol" && samplerName != "philox") { fprintf(stderr, "vcm_render: --sampler sobol|philox\n"); return 2; }
         }
         else if (a == "--denoise") {
             denoise = true;
@@ -334,8 +344,26 @@ int main(int argc, char **argv)
         filterDesc.filter = filter;
         filterScene = &filterDesc;
     }
+    // the sampler (--sampler, else a scene file's `sampler`): the scene as a version-7 description
+    vcm_sampler flagSampler;
+    flagSampler.kind = samplerName == "sobol" ? VCM_SAMPLER_SOBOL : VCM_SAMPLER_PHILOX;
+    const vcm_sampler *sampler = !samplerName.empty() ? &flagSampler : loaded ? vcm_scene_file_desc7(loaded)->sampler : NULL;
+    vcm_scene_desc7 samplerDesc;
+    const vcm_scene_desc7 *samplerScene = NULL;
+    if (sampler && sampler->kind != VCM_SAMPLER_PHILOX && gpus <= 0) {
+        memset(&samplerDesc, 0, sizeof(samplerDesc));
+        if (filterScene) samplerDesc.base = *filterScene;
+        else if (pickScene) samplerDesc.base.base = *pickScene;
+        else if (lensScene) samplerDesc.base.base.base = *lensScene;
+        else if (envScene) samplerDesc.base.base.base.base = *envScene;
+        else if (loaded) samplerDesc.base.base.base.base = *vcm_scene_file_desc3(loaded);
+        else scene_as_desc2(scene, samplerDesc.base.base.base.base.base);   // the built-in scene (the arrays stay in `scene`)
+        samplerDesc.sampler = sampler;
+        samplerScene = &samplerDesc;
+    }
     auto create = [&](int s) {
-        return filterScene ? vcm_create_sharded6(filterScene, algorithm, radiusFactor, radiusAlpha, s, device, 0, 1)
+        return samplerScene ? vcm_create_sharded7(samplerScene, algorithm, radiusFactor, radiusAlpha, s, device, 0, 1)
+             : filterScene ? vcm_create_sharded6(filterScene, algorithm, radiusFactor, radiusAlpha, s, device, 0, 1)
              : pickScene ? vcm_create_sharded5(pickScene, algorithm, radiusFactor, radiusAlpha, s, device, 0, 1)
              : lensScene ? vcm_create_sharded4(lensScene, algorithm, radiusFactor, radiusAlpha, s, device, 0, 1)
              : envScene ? vcm_create_sharded3(envScene, algorithm, radiusFactor, radiusAlpha, s, device, 0, 1)
@@ -359,6 +387,7 @@ int main(int argc, char **argv)
         fc.firstRank = 0; fc.localRanks = gpus;   // every rank is a thread of this process
         fc.sameWindow = sameWindow != 0;
         if (filter) fc.filter = *filter;
+        if (sampler) fc.sampler = *sampler;
         const int visible = vcm_device_count();
         if (visible <= 0) { fprintf(stderr, "vcm_render: no HIP device available (this program has no CPU path)\n"); return 2; }
         for (int k = 0; k < gpus; k++) fc.devices.push_back(k < (int)devices.size() ? devices[(size_t)k] : (fc.rccl ? k : k % visible));

@@ -16,7 +16,7 @@ import math
 import numpy as np
 
 from ._abi import (Camera, EnvMap, Light, LightPick, Material, Prim, SceneDesc2, SceneDesc3, SceneDesc4, SceneDesc5, SceneDesc6, ThinLens,
-                   PixelFilter, FILTER_BOX, FILTER_MAX_RADIUS, LIGHT_PICK_CUSTOM, LIGHT_PICK_MODES, PIXEL_FILTERS)
+                   PixelFilter, SAMPLERS, with_sampler, FILTER_BOX, FILTER_MAX_RADIUS, LIGHT_PICK_CUSTOM, LIGHT_PICK_MODES, PIXEL_FILTERS)
 
 
 def _f3(v):
@@ -58,6 +58,7 @@ class SceneBuilder:
         self.lens = None
         self.pick = None
         self.filter = None
+        self.sampler_kind = None
 
     # ---- materials (materials.hxx:33-65) ----
     def material(self, diffuse=(0, 0, 0), phong=(0, 0, 0), exponent=1.0, mirror=(0, 0, 0), ior=-1.0):
@@ -194,8 +195,20 @@ class SceneBuilder:
             raise ValueError("pixel_filter: radius must be finite, > 0 and <= %g pixels" % FILTER_MAX_RADIUS)
         self.filter = (PIXEL_FILTERS[kind], r)
 
+    # ---- the sampler ----
+    def sampler(self, kind):
+        """where the paths' random floats come from (include/smallvcm_amd.h vcm_sampler): "philox" (white noise, the
+        default) or "sobol" (the Owen-scrambled Sobol sequence).  build() then returns a SceneDesc7."""
+        if kind not in SAMPLERS:
+            raise ValueError("sampler: kind must be 'sobol' or 'philox'")
+        self.sampler_kind = kind
+
     # ---- the description ----
     def build(self, position, forward, up, fov_deg, resx, resy):
+        d = self._build6(position, forward, up, fov_deg, resx, resy)
+        return d if self.sampler_kind is None else with_sampler(d, self.sampler_kind)
+
+    def _build6(self, position, forward, up, fov_deg, resx, resy):
         d = SceneDesc2()
         prims = (Prim * max(len(self.prims), 1))(*self.prims)
         mats = (Material * len(self.materials))(*self.materials)

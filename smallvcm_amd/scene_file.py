@@ -1,7 +1,8 @@
 """Scene files (include/smallvcm_amd.h: vcm_scene_load): `.vcmscene` / Wavefront `.obj` + `.mtl` -> SceneDesc2,
 SceneDesc3 when the file names an environment map (`light envmap <file> <scale>`), SceneDesc4 when it names a thin
 lens (`lens <apertureRadius> <focusDistance>`), SceneDesc5 when it says how lights are chosen (`lightpick
-uniform|power [uniformMix]`), or SceneDesc6 when it names a pixel filter (`filter tent|bspline <radius>`).
+uniform|power [uniformMix]`), SceneDesc6 when it names a pixel filter (`filter tent|bspline <radius>`), or SceneDesc7
+when it names a sampler (`sampler sobol|philox`).
 The parsing happens in the library (smallvcm_amd/csrc/scene_file.cpp documents the format); this is the ctypes binding.
 
     scene = load_scene("tests/scenes/bumpy_room.vcmscene", 1024, 1024)
@@ -9,7 +10,7 @@ The parsing happens in the library (smallvcm_amd/csrc/scene_file.cpp documents t
 """
 import ctypes as C
 
-from ._abi import SceneDesc2, SceneDesc3, SceneDesc4, SceneDesc5, SceneDesc6
+from ._abi import SceneDesc2, SceneDesc3, SceneDesc4, SceneDesc5, SceneDesc6, SceneDesc7
 
 
 class _Handle:
@@ -23,8 +24,9 @@ class _Handle:
 
 
 def load_scene(path, resx, resy):
-    """-> SceneDesc2, SceneDesc3 with an env map, SceneDesc4 with a lens, SceneDesc5 with a `lightpick` directive, or
-    SceneDesc6 with a `filter` directive (the arrays it points to live as long as the returned object)"""
+    """-> SceneDesc2, SceneDesc3 with an env map, SceneDesc4 with a lens, SceneDesc5 with a `lightpick` directive,
+    SceneDesc6 with a `filter` directive, or SceneDesc7 with a `sampler` directive (the arrays it points to live as long
+    as the returned object)"""
     from .renderer import load_library
     L = load_library(require_gpu=False)
     L.vcm_scene_load.restype = C.c_void_p
@@ -39,6 +41,8 @@ def load_scene(path, resx, resy):
     L.vcm_scene_file_desc5.argtypes = [C.c_void_p]
     L.vcm_scene_file_desc6.restype = C.POINTER(SceneDesc6)
     L.vcm_scene_file_desc6.argtypes = [C.c_void_p]
+    L.vcm_scene_file_desc7.restype = C.POINTER(SceneDesc7)
+    L.vcm_scene_file_desc7.argtypes = [C.c_void_p]
     L.vcm_scene_file_free.argtypes = [C.c_void_p]
     L.vcm_scene_file_free.restype = None
     L.vcm_scene_load_error.restype = C.c_char_p
@@ -49,7 +53,10 @@ def load_scene(path, resx, resy):
     d3 = L.vcm_scene_file_desc3(h).contents
     d5 = L.vcm_scene_file_desc5(h).contents
     d6 = L.vcm_scene_file_desc6(h).contents
-    if d6.filter:
+    d7 = L.vcm_scene_file_desc7(h).contents
+    if d7.sampler:
+        d = SceneDesc7.from_buffer_copy(d7)   # the struct (pointers into the handle's arrays, map, lens, pick, filter and sampler)
+    elif d6.filter:
         d = SceneDesc6.from_buffer_copy(d6)   # the struct (pointers into the handle's arrays, map, lens, pick and filter)
     elif d5.pick:
         d = SceneDesc5.from_buffer_copy(d5)   # the struct (pointers into the handle's arrays, map, lens and pick)
