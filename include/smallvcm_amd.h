@@ -514,7 +514,7 @@ int vcm_import_sorted_light_records(vcm_ctx *ctx, const void *gathered, const lo
  *                   powf of this library, so a byte can differ by one level from a glibc build of the reference.
  *   VCM_IMAGE_RGBE  Framebuffer::SaveHDR's pixel data (:229-247): rows top-down, R,G,B,E bytes; resX*resY*4
  *                   bytes, bit-identical to the reference's (frexp and IEEE double arithmetic only). */
-enum { VCM_IMAGE_BGR8 = 0, VCM_IMAGE_RGBE = 1 };
+enum { VCM_IMAGE_BGR8 = 0, VCM_IMAGE_RGBE = 1, VCM_IMAGE_RGBA8 = 2 /* vcm_read_display_image only */ };
 int vcm_read_image(vcm_ctx *ctx, int format, float scale, float gamma, unsigned char *outHost);
 /* Framebuffer = running SUM over iterations of this context (the reference's
  * mFramebuffer, src/renderer.hxx:68); W*H*3 floats, row-major, RGB. */
@@ -795,6 +795,63 @@ int vcm_track_parts(vcm_ctx *ctx, int on);
 int vcm_read_part(vcm_ctx *ctx, int part, float scale, float *rgbHost);   /* W*H*3 floats = plane * scale; scale 1 gives the raw sums */
 int vcm_part_device(vcm_ctx *ctx, int part, float scale, void **devPtr);  /* W*H float4 {rgb*scale, 1}, fit for vcm_denoise_buffers; valid until the next call */
 int vcm_get_parts_stats(vcm_ctx *ctx, vcm_parts_stats *out);              /* synchronises */
+
+/* ---- the display transform: auto-exposure, tone curves, bloom, sRGB ----
+ * What turns a linear HDR image into one a screen can show, on the device.  The pipeline on the linear pixel c * scale:
+ *   1 exposure    times m = (float)exp2(autoEV + exposureEV)
+ *   2 bloom       (1 - s) E + s B, s = bloomStrength; B = an energy-preserving pyramid blur of bloomLevels levels (2 x 2
+ *                 means down, the binomial [1 4 6 4 1] / 16 at every level, bilinear x 2 up, the levels' mean); no threshold.
+ *                 bloomStrength 0 launches nothing.  A pixel with a non-finite channel enters the blur as 0 and stays
+ *                 what it was.
+ *   3 tone curve  VCM_CURVE_CLAMP identity | VCM_CURVE_REINHARD extended Reinhard on the luminance, white point
+ *                 whitePoint | VCM_CURVE_ACES Narkowicz's fit | VCM_CURVE_HABLE Hable's filmic curve h(2x) / h(11.2); NaN
+ *                 and negative channels enter a curve as 0, +Inf as 2^40; the result is clamped to [0, 1]
+ *   4 transfer    VCM_TRANSFER_GAMMA c^(1 / gamma), as vcm_read_image | VCM_TRANSFER_SRGB the piecewise sRGB curve
+ *   5 bytes       vcm_read_display_image only: truncation (byte)min(255, v * 255) as vcm_read_image, or with dither == 1
+ *                 floor(v * 255 + d), d in [0, 1) an integer hash of (pixel index, channel, ditherSeed): unbiased
+ *                 stochastic rounding, no state, the same bytes on every run
+ * vcm_display_defaults reproduces vcm_read_image(BGR8, scale, 2.2) byte for byte: CLAMP, GAMMA 2.2, everything else off
+ * (whitePoint 4, key 0.18, percentiles 0.10 / 0.95, minEV -16, maxEV 16, bloomLevels 5 are what switching a stage on uses).
+ * autoExposure == 1 picks autoEV from a histogram of the log luminance Y = 0.2126 r + 0.7152 g + 0.0722 b of c * scale
+ * (eight bins per octave over 2^-20 .. 2^12, 64-bit counts: the same on every run): the mean log2 luminance of the pixels
+ * between the two percentiles goes to `key`, clamped to [minEV, maxEV].  Pixels with Y <= 0 or a non-finite Y are left
+ * out and counted apart.  This reads 2 KB back and waits for the stream; everything else of vcm_display is asynchronous on
+ * the context's stream.  Parameters out of range or not finite are refused with -1 (vcm_last_error says which).
+ * vcm_display(ctx, source, scale, p): source VCM_DISPLAY_FRAMEBUFFER = the running sum * scale, VCM_DISPLAY_DENOISED /
+ * VCM_DISPLAY_ROBUST = that image * scale (refused where vcm_denoise has not run / the robust estimate cannot be
+ * resolved).  Refused for a sharded context: reduce the frame and call vcm_display_buffers.  The result stays with the
+ * context until the next vcm_display: vcm_display_device gives the W*H float4 image { rgb in [0, 1], 1 }, vcm_read_display
+ * W*H*3 floats, vcm_read_display_image the bytes -- VCM_IMAGE_BGR8 bottom-up as vcm_read_image, VCM_IMAGE_RGBA8 top-down
+ * with alpha 255 (VCM_IMAGE_RGBE is refused: it is a linear format) -- and vcm_get_display_stats what the histogram saw
+ * (all zero but multiplier and clipped without autoExposure) and `clipped`, the channels that reached 1.0 after the curve;
+ * it synchronises.  Memory: 16 bytes per pixel, and about 16 more with bloom, from the first vcm_display to vcm_destroy.
+ * vcm_display_buffers needs no context: colorDev holds width * height pixels of `channels` (3 or 4) floats on `device`,
+ * outDev width * height float4 (16-byte aligned, not colorDev); scratch comes from hipMallocAsync / hipFreeAsync on the
+ * stream.  With statsOut != NULL it fills *statsOut and synchronises the stream; with NULL and autoExposure 0 the host
+ * does not wait. */
+enum { VCM_CURVE_CLAMP = 0, VCM_CURVE_REINHARD = 1, VCM_CURVE_ACES = 2, VCM_CURVE_HABLE = 3 };
+enum { VCM_TRANSFER_GAMMA = 0, VCM_TRANSFER_SRGB = 1 };
+enum { VCM_DISPLAY_FRAMEBUFFER = 0, VCM_DISPLAY_DENOISED = 1, VCM_DISPLAY_ROBUST = 2 };
+typedef struct vcm_display_params {
+    int curve; float whitePoint;
+    float exposureEV;
+    int autoExposure; float key, lowPercentile, highPercentile, minEV, maxEV;
+    int transfer; float gamma;
+    float bloomStrength; int bloomLevels;
+    int dither; unsigned int ditherSeed;
+} vcm_display_params;
+typedef struct vcm_display_stats {
+    double autoEV, multiplier, logAvgLuminance;   /* logAvgLuminance: log2 of the trimmed geometric mean luminance */
+    long long counted, zero, nonFinite, clampedLow, clampedHigh, clipped;
+} vcm_display_stats;
+void vcm_display_defaults(vcm_display_params *out);
+int vcm_display(vcm_ctx *ctx, int source, float scale, const vcm_display_params *p);
+int vcm_display_device(vcm_ctx *ctx, void **devPtr);              /* W*H float4 {rgb in [0, 1], 1} */
+int vcm_read_display(vcm_ctx *ctx, float *rgbHost);               /* W*H*3 floats */
+int vcm_read_display_image(vcm_ctx *ctx, int format, unsigned char *outHost);   /* BGR8: W*H*3 bytes, RGBA8: W*H*4 */
+int vcm_get_display_stats(vcm_ctx *ctx, vcm_display_stats *out);  /* synchronises */
+int vcm_display_buffers(int device, int width, int height, const void *colorDev, int channels, float scale,
+                        const vcm_display_params *p, void *outDev, vcm_display_stats *statsOut, void *hipStream);
 
 #ifdef __cplusplus
 }

@@ -131,6 +131,14 @@ int vcm_debug_read_robust_images(vcm_ctx *ctx, float *prevHost4, float *bucketsH
  * vcm_parts_stats.luminance, depend on it: not for production hosts. */
 void vcm_debug_parts_max_blocks(int blocks);
 
+/* The cap of the grid of the display transform's histogram kernel (0 restores the default, 2048 workgroups of 256 lanes),
+ * so that a test reaches the grid-stride path with a few hundred pixels.  Process-wide; the counts do not depend on it. */
+void vcm_debug_display_max_blocks(int blocks);
+
+/* The 256 bins of the last histogram this thread's vcm_display / vcm_display_buffers read back (autoExposure == 1); -1
+ * where there has been none. */
+int vcm_debug_read_display_histogram(unsigned long long *out256);
+
 /* sizeof the PODs of smallvcm_amd.h as the library was compiled */
 unsigned vcm_sizeof_scene_desc(void);
 unsigned vcm_sizeof_stats(void);

@@ -256,6 +256,35 @@ class PartsStats(C.Structure):
                 "luminance": dict(zip(PART_NAMES, list(self.luminance)))}
 
 
+# VCM_CURVE_*, VCM_TRANSFER_*, VCM_DISPLAY_*: the display transform (vcm_display)
+CURVES = {"clamp": 0, "reinhard": 1, "aces": 2, "hable": 3}
+TRANSFERS = {"gamma": 0, "srgb": 1}
+DISPLAY_SOURCES = {"framebuffer": 0, "denoised": 1, "robust": 2}
+IMAGE_BGR8, IMAGE_RGBE, IMAGE_RGBA8 = 0, 1, 2
+
+
+class DisplayParams(C.Structure):
+    """vcm_display_params: exposure, bloom, tone curve, transfer curve and dither of the display transform
+    (include/smallvcm_amd.h)"""
+    _fields_ = [("curve", C.c_int), ("whitePoint", C.c_float), ("exposureEV", C.c_float),
+                ("autoExposure", C.c_int), ("key", C.c_float), ("lowPercentile", C.c_float), ("highPercentile", C.c_float),
+                ("minEV", C.c_float), ("maxEV", C.c_float),
+                ("transfer", C.c_int), ("gamma", C.c_float),
+                ("bloomStrength", C.c_float), ("bloomLevels", C.c_int),
+                ("dither", C.c_int), ("ditherSeed", C.c_uint)]
+
+
+class DisplayStats(C.Structure):
+    """vcm_display_stats: the exposure the histogram picked and the multiplier applied, what the histogram counted and left
+    out, and the channels that reached 1.0 after the curve (include/smallvcm_amd.h)"""
+    _fields_ = [("autoEV", C.c_double), ("multiplier", C.c_double), ("logAvgLuminance", C.c_double),
+                ("counted", C.c_longlong), ("zero", C.c_longlong), ("nonFinite", C.c_longlong),
+                ("clampedLow", C.c_longlong), ("clampedHigh", C.c_longlong), ("clipped", C.c_longlong)]
+
+    def asdict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
 class Stats(C.Structure):
     _fields_ = [("lightVertices", C.c_longlong), ("gridVertices", C.c_longlong),
                 ("lightRays", C.c_longlong), ("cameraRays", C.c_longlong),

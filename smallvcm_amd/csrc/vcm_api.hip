@@ -24,6 +24,7 @@
 #include "vcm_variance.h"
 #include "vcm_robust.h"
 #include "vcm_parts.h"
+#include "vcm_display.h"
 
 using namespace vcm;
 
@@ -201,6 +202,13 @@ struct vcm_ctx : Scratch {
     bool trackParts;
     float *dParts;                    /* VCM_PART_COUNT planes of N x 3 floats, the framebuffer's layout */
     F4 *dPartOut;                     /* N: what the last vcm_part_device made (allocated by the first) */
+    /* the display transform (vcm_display.h): allocated by the first vcm_display */
+    F4 *dDisplay;                     /* N: the last vcm_display's image { rgb in [0, 1], 1 } */
+    unsigned long long *dDispCounters;   /* VCM_DISP_COUNTERS: the histogram and the clipped channels of the last vcm_display */
+    F4 *dDispScratch; size_t dispScratchCap;   /* the bloom's levels, kept from the first vcm_display with bloom on */
+    bool displayValid;
+    vcm_display_params dispParams;    /* of the last vcm_display (dither and ditherSeed: vcm_read_display_image) */
+    vcm_display_stats dispStats;      /* of the last vcm_display, but `clipped`: vcm_get_display_stats reads it */
     int fbIterations;                 /* iterations the framebuffer holds: those since the last vcm_clear_framebuffer; while
                                          tracking is on (it starts at 0 only) also the k of the two images */
     IterParams P;
@@ -1012,6 +1020,7 @@ void vcm_destroy(vcm_ctx *c)
         DFREE(c->dVarPrev); DFREE(c->dVarMom);
         DFREE(c->dRobPrev); DFREE(c->dRobBuckets); DFREE(c->dRobOut);
         DFREE(c->dParts); DFREE(c->dPartOut);
+        DFREE(c->dDisplay); DFREE(c->dDispCounters); DFREE(c->dDispScratch);
         c->dScene = NULL; DFREE(c->dSceneBlob); DFREE(c->dFb); DFREE(c->dRngLight); DFREE(c->dRngCam); DFREE(c->dHdr); DFREE(c->dStatsRing); DFREE(c->dStamps);
         for (int i = 0; i < EV_COUNT; i++) (void)hipEventDestroy(c->ev[i]);
         (void)hipStreamSynchronize(c->side);
@@ -2809,6 +2818,174 @@ int vcm_robust_stats_buffers(int device, long long n, const void *prevDev, const
     if (((uintptr_t)prevDev | (uintptr_t)bucketsDev) & 15) return fail("vcm_robust_stats_buffers", "prevDev and bucketsDev must be 16-byte aligned (float4 images)");
     if (robust_buffers_check("vcm_robust_stats_buffers", device, n, k, buckets, true)) return -1;
     return robust_stats_of("vcm_robust_stats_buffers", n, (const F4 *)prevDev, (const F4 *)bucketsDev, k, buckets, out, (hipStream_t)hipStream);
+}
+
+/* ---- the display transform (kernels: vcm_display.hip) ---- */
+void vcm_display_defaults(vcm_display_params *out)
+{
+    if (out) disp_defaults(out);
+}
+
+static thread_local unsigned long long g_dispHistogram[VCM_DISP_BINS];
+static thread_local bool g_dispHistogramValid;
+
+/* Steps 1-4 of width x height pixels of src * scale into out, on stream s of the current device.  counters:
+   VCM_DISP_COUNTERS device words.  With autoExposure the histogram is read back here (the one wait); *stats gets
+   everything but `clipped`. */
+static int display_run(const char *who, int width, int height, const float *src, int channels, float scale, const vcm_display_params &p,
+                       F4 *scratch, F4 *out, unsigned long long *counters, vcm_display_stats *stats, hipStream_t s)
+{
+    const long long n = (long long)width * height;
+    unsigned long long host[VCM_DISP_COUNTERS];
+    memset(host, 0, sizeof(host));
+    hipError_t e = hipMemsetAsync(counters, 0, VCM_DISP_COUNTERS * sizeof(unsigned long long), s);
+    if (e == hipSuccess && p.autoExposure) {
+        e = disp_launch_histogram(n, src, channels, scale, counters, s);
+        if (e == hipSuccess) e = hipMemcpyAsync(host, counters, sizeof(host), hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess) e = hipStreamSynchronize(s);
+        if (e == hipSuccess) { memcpy(g_dispHistogram, host, sizeof(g_dispHistogram)); g_dispHistogramValid = true; }
+    }
+    if (e != hipSuccess) { g_hipFailed = true; return fail(who, hipGetErrorString(e)); }
+    disp_auto_exposure(host, p, stats);
+    e = disp_launch_transform(width, height, src, channels, scale, (float)stats->multiplier, p, scratch, out, counters, s);
+    if (e != hipSuccess) { g_hipFailed = true; return fail(who, hipGetErrorString(e)); }
+    return 0;
+}
+
+int vcm_display(vcm_ctx *c, int source, float scale, const vcm_display_params *p)
+{
+    if (!c) return fail("vcm_display", "ctx is NULL");
+    if (refuse_sharded(c, "vcm_display")) return -1;
+    if (source != VCM_DISPLAY_FRAMEBUFFER && source != VCM_DISPLAY_DENOISED && source != VCM_DISPLAY_ROBUST) return fail("vcm_display", "unknown source");
+    if (const char *why = disp_check_params(p)) return fail("vcm_display", why);
+    if (!disp_finite(scale)) return fail("vcm_display", "scale is not finite");
+    g_hipFailed = false;
+    const float *src = NULL;
+    int channels = 4;
+    if (source == VCM_DISPLAY_DENOISED) {
+        if (need_denoised(c, "vcm_display")) return -1;
+        src = (const float *)c->dDenoised;
+    } else if (source == VCM_DISPLAY_ROBUST) {
+        if (vcm_robust_resolve(c)) return -1;
+        src = (const float *)c->dRobOut;
+    } else {
+        if (ensure_device(c)) return -1;
+        if (join_splats(c)) return -1;   /* the light splats / K5 of the last iteration add to the framebuffer on a stream of their own */
+        src = c->dFb; channels = 3;
+    }
+    if (!c->dDisplay && (dalloc(&c->dDisplay, (size_t)c->N) || dalloc(&c->dDispCounters, (size_t)VCM_DISP_COUNTERS))) return -1;
+    if (p->bloomStrength > 0.f) {
+        const size_t need = disp_bloom_scratch_f4(c->resX, c->resY, p->bloomLevels);
+        if (need > c->dispScratchCap) {
+            if (c->dDispScratch) { HIPCHK(hipStreamSynchronize(c->stream)); DFREE(c->dDispScratch); c->dispScratchCap = 0; }
+            if (dalloc(&c->dDispScratch, need)) return -1;
+            c->dispScratchCap = need;
+        }
+    }
+    c->displayValid = false;
+    if (display_run("vcm_display", c->resX, c->resY, src, channels, scale, *p, c->dDispScratch, c->dDisplay, c->dDispCounters, &c->dispStats, c->stream)) return -1;
+    c->dispParams = *p;
+    c->displayValid = true;
+    return 0;
+}
+
+static int need_display(vcm_ctx *c, const char *who)
+{
+    if (refuse_sharded(c, who)) return -1;
+    if (!c->displayValid) return fail(who, "vcm_display has not run");
+    return use_device(c);
+}
+
+int vcm_display_device(vcm_ctx *c, void **devPtr)
+{
+    if (!c || !devPtr) return fail("vcm_display_device", "NULL argument");
+    if (need_display(c, "vcm_display_device")) return -1;
+    *devPtr = c->dDisplay;
+    return 0;
+}
+
+int vcm_read_display(vcm_ctx *c, float *rgbHost)
+{
+    if (!c || !rgbHost) return fail("vcm_read_display", "NULL argument");
+    g_hipFailed = false;
+    if (need_display(c, "vcm_read_display")) return -1;
+    return read_f4_components(c, "vcm_read_display", c->dDisplay, 0, 3, rgbHost);
+}
+
+int vcm_read_display_image(vcm_ctx *c, int format, unsigned char *outHost)
+{
+    if (!c || !outHost) return fail("vcm_read_display_image", "NULL argument");
+    if (format == VCM_IMAGE_RGBE) return fail("vcm_read_display_image", "RGBE is a linear format: vcm_read_image writes it");
+    if (format != VCM_IMAGE_BGR8 && format != VCM_IMAGE_RGBA8) return fail("vcm_read_display_image", "unknown format");
+    g_hipFailed = false;
+    if (need_display(c, "vcm_read_display_image")) return -1;
+    const size_t bytes = (size_t)c->N * (format == VCM_IMAGE_BGR8 ? 3 : 4);
+    unsigned char *d = NULL;
+    if (dalloc(&d, bytes)) return -1;
+    hipError_t e = disp_launch_encode(c->resX, c->resY, c->dDisplay, format, c->dispParams.dither, c->dispParams.ditherSeed, d, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(outHost, d, bytes, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    (void)hipFree(d);
+    if (e != hipSuccess) { g_hipFailed = true; return fail("vcm_read_display_image", hipGetErrorString(e)); }
+    return 0;
+}
+
+int vcm_get_display_stats(vcm_ctx *c, vcm_display_stats *out)
+{
+    if (!c || !out) return fail("vcm_get_display_stats", "NULL argument");
+    g_hipFailed = false;
+    if (need_display(c, "vcm_get_display_stats")) return -1;
+    unsigned long long clipped = 0ull;
+    HIPCHK(hipMemcpyAsync(&clipped, c->dDispCounters + VCM_DISP_CLIPPED, sizeof(clipped), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    *out = c->dispStats;
+    out->clipped = (long long)clipped;
+    return 0;
+}
+
+int vcm_display_buffers(int device, int width, int height, const void *colorDev, int channels, float scale, const vcm_display_params *p,
+                        void *outDev, vcm_display_stats *statsOut, void *hipStream)
+{
+    if (!colorDev || !outDev) return fail("vcm_display_buffers", "NULL image");
+    if (width <= 0 || height <= 0 || (long long)width * height > 0x7fffffffll) return fail("vcm_display_buffers", "bad size");
+    if (channels != 3 && channels != 4) return fail("vcm_display_buffers", "channels must be 3 or 4");
+    if (outDev == colorDev) return fail("vcm_display_buffers", "outDev is the input");
+    if (((uintptr_t)outDev & 15) || ((uintptr_t)colorDev & 3)) return fail("vcm_display_buffers", "outDev must be 16-byte aligned (a float4 image), colorDev 4-byte aligned");
+    if (const char *why = disp_check_params(p)) return fail("vcm_display_buffers", why);
+    if (!disp_finite(scale)) return fail("vcm_display_buffers", "scale is not finite");
+    const int ndev = vcm_device_count();
+    if (ndev <= 0) return fail("vcm_display_buffers", "no HIP device available (this library has no CPU path)");
+    if (device < 0 || device >= ndev) return fail("vcm_display_buffers", "device index out of range");
+    g_hipFailed = false;
+    HIPCHK(hipSetDevice(device));
+    hipStream_t s = (hipStream_t)hipStream;
+    /* stream-ordered scratch: the counters, and behind them (256 bytes on) the bloom's levels; given back behind the last kernel */
+    const size_t head = 4096, levels = p->bloomStrength > 0.f ? disp_bloom_scratch_f4(width, height, p->bloomLevels) * sizeof(F4) : 0;
+    static_assert(VCM_DISP_COUNTERS * sizeof(unsigned long long) <= 4096, "the counters fit the scratch's head");
+    char *scratch = NULL;
+    HIPCHK(hipMallocAsync((void **)&scratch, head + levels, s));
+    vcm_display_stats st;
+    int rc = display_run("vcm_display_buffers", width, height, (const float *)colorDev, channels, scale, *p, (F4 *)(scratch + head), (F4 *)outDev,
+                         (unsigned long long *)scratch, &st, s);
+    if (rc == 0 && statsOut) {
+        unsigned long long clipped = 0ull;
+        hipError_t e = hipMemcpyAsync(&clipped, (unsigned long long *)scratch + VCM_DISP_CLIPPED, sizeof(clipped), hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess) e = hipStreamSynchronize(s);
+        if (e != hipSuccess) { g_hipFailed = true; rc = fail("vcm_display_buffers", hipGetErrorString(e)); }
+        else { *statsOut = st; statsOut->clipped = (long long)clipped; }
+    }
+    (void)hipFreeAsync(scratch, s);
+    return rc;
+}
+
+void vcm_debug_display_max_blocks(int blocks) { disp_set_max_blocks(blocks); }
+
+int vcm_debug_read_display_histogram(unsigned long long *out256)
+{
+    if (!out256) return fail("vcm_debug_read_display_histogram", "NULL argument");
+    if (!g_dispHistogramValid) return fail("vcm_debug_read_display_histogram", "no histogram has been read back on this thread");
+    memcpy(out256, g_dispHistogram, sizeof(g_dispHistogram));
+    return 0;
 }
 
 /* ---- the technique breakdown (kernels: vcm_parts.hip; the LIGHT_TRACE plane: flush_light_splats) ---- */

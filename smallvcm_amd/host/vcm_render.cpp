@@ -15,6 +15,8 @@
 //              [--filter tent|bspline R]
 //              [--denoise [passes]] [--denoise-sigma c,n,z] [--no-demodulate] [--features-out prefix]
 //              [--noise-target E [--check-every N] [--max-iterations M]] [--track-variance] [--robust [M]]
+//              [--tonemap clamp|reinhard|aces|hable] [--exposure EV] [--auto-exposure [key]] [--bloom S [levels]]
+//              [--srgb] [--dither]
 //              [--parts prefix]
 //              [--gpus N [--shards S] [--inflight K] [--devices 0,1,..] [--collectives rccl|threads] [--same-window]]
 //
@@ -68,6 +70,13 @@
 // adds "parts" to --json.  Wants one renderer on one GPU, a VertexCM algorithm (lt, ppm, bpm, bpt, vcm), no --strict and
 // --maxlen <= 31; anything else is refused with exit status 2 before any device call.
 //
+// --tonemap / --exposure / --auto-exposure / --bloom / --srgb / --dither (vcm_render_display.hpp): with any of them a .bmp
+// goes through the display transform on the device (vcm_display, then vcm_read_display_image) instead of the reference's
+// clamp-and-gamma encoding: the denoised image with --denoise (the .noisy.bmp beside it: the framebuffer, the same way),
+// the robust image with --robust, else the framebuffer / iterations.  What the transform saw (vcm_get_display_stats: the
+// exposure picked, the channels clipped) is printed, and is "display" in --json; .hdr and .pfm stay linear, and without
+// these flags every file is what it was.  They want one renderer on one GPU.
+//
 // -s / -a / -i keep the meaning they have in the reference's CLI
 // (src/config.hxx:246-395; scenes = g_SceneConfigs[0..3], :146-151).
 // --renderers R reproduces render() (src/smallvcm.cxx:52-151) with R "threads":
@@ -92,6 +101,7 @@
 #include "smallvcm_amd.h"
 #include "smallvcm_amd_debug.h"
 #include "vcm_farm.hpp"
+#include "vcm_render_display.hpp"
 
 static int die(const char *what)
 {
@@ -141,8 +151,13 @@ int main(int argc, char **argv)
     vcm_robust_stats rs = {};
     std::string partsOut;
     vcm_parts_stats ps = {};
+    DisplayFlags disp = {};
+    vcm_display_defaults(&disp.p);
+    vcm_display_stats ds = {};
+    bool displayed = false;
     for (int i = 1; i < argc; i++) {
         const std::string a(argv[i]);
+        if (const int taken = display_parse_flag(argc, argv, i, disp)) { if (taken < 0) return 2; continue; }
         auto need = [&](int n) { if (i + n >= argc) { fprintf(stderr, "vcm_render: %s needs %d argument(s)\n", a.c_str(), n); exit(2); } };
         if (a == "-s") { need(1); sceneID = atoi(argv[++i]); }
         else if (a == "-a") { need(1); algoName = argv[++i]; algorithm = algorithm_by_acronym(algoName); }
@@ -242,6 +257,10 @@ int main(int argc, char **argv)
     }
     if (robust && (renderers != 1 || gpus > 0)) {
         fprintf(stderr, "vcm_render: --robust wants one renderer on one GPU (a farm host reduces the frames and calls vcm_robust_update_buffers)\n");
+        return 2;
+    }
+    if (disp.any && (renderers != 1 || gpus > 0)) {
+        fprintf(stderr, "vcm_render: --tonemap, --exposure, --auto-exposure, --bloom, --srgb and --dither want one renderer on one GPU (a farm host reduces the frames and calls vcm_display_buffers)\n");
         return 2;
     }
     if (!partsOut.empty() && (renderers != 1 || gpus > 0)) {
@@ -534,6 +553,18 @@ int main(int argc, char **argv)
         const std::string ext = path.size() >= 4 ? path.substr(path.size() - 4) : "";
         const bool bmp = ext == ".bmp", hdr = ext == ".hdr";
         std::vector<unsigned char> px;
+        if (disp.any) {   // the display transform: its statistics in any case, its bytes for a .bmp
+            const int source = denoised ? VCM_DISPLAY_DENOISED : (robust ? VCM_DISPLAY_ROBUST : VCM_DISPLAY_FRAMEBUFFER);
+            if (vcm_display(r[0], source, source == VCM_DISPLAY_FRAMEBUFFER ? 1.f / vcm_iterations(r[0]) : 1.f, &disp.p)) return die("vcm_display");
+            if (vcm_get_display_stats(r[0], &ds)) return die("vcm_get_display_stats");
+            displayed = true;
+            if (bmp) {
+                px.resize((size_t)resX * resY * 3);
+                if (vcm_read_display_image(r[0], VCM_IMAGE_BGR8, px.data())) return die("vcm_read_display_image");
+                if (display_write_bmp(path.c_str(), resX, resY, px.data())) { fprintf(stderr, "vcm_render: cannot write %s\n", path.c_str()); return 2; }
+                return 0;
+            }
+        }
         if (bmp || hdr) {
             px.resize((size_t)resX * resY * (bmp ? 3 : 4));
             if (denoised) {
@@ -592,6 +623,14 @@ int main(int argc, char **argv)
             if (int rc = save(out, clean, true)) return rc;
         }
     }
+    if (disp.any && !displayed) {   // no -o: the statistics alone
+        const int source = denoise ? VCM_DISPLAY_DENOISED : (robust ? VCM_DISPLAY_ROBUST : VCM_DISPLAY_FRAMEBUFFER);
+        if (vcm_display(r[0], source, source == VCM_DISPLAY_FRAMEBUFFER ? 1.f / vcm_iterations(r[0]) : 1.f, &disp.p)) return die("vcm_display");
+        if (vcm_get_display_stats(r[0], &ds)) return die("vcm_get_display_stats");
+    }
+    if (disp.any && !json)
+        printf("display transform: exposure x %.9g (auto %+.4f EV over %lld pixel(s); %lld black, %lld non-finite left out), %lld channel(s) clipped\n",
+               ds.multiplier, ds.autoEV, ds.counted, ds.zero, ds.nonFinite, ds.clipped);
     for (size_t g = 0; g < r.size(); g++) vcm_destroy(r[g]);
     vcm_scene_file_free(loaded);
     vcm_envmap_free(envmap);
@@ -607,6 +646,8 @@ int main(int argc, char **argv)
         if (!partsOut.empty()) snprintf(partsJson, sizeof(partsJson), ", \"parts\": {\"iterations\": %d, \"pixels\": %lld, \"nonFinite\": %lld, \"luminance\": "
                                         "{\"emission\": %.17g, \"direct\": %.17g, \"connect\": %.17g, \"merge\": %.17g, \"lighttrace\": %.17g}}",
                                         ps.iterations, ps.pixels, ps.nonFinite, ps.luminance[0], ps.luminance[1], ps.luminance[2], ps.luminance[3], ps.luminance[4]);
+        char displayJson[480] = "";
+        if (disp.any) display_stats_json(ds, displayJson, sizeof(displayJson));
         std::string ms = "[";
         for (size_t i = 0; i < rankMs.size(); i++) { char b[32]; snprintf(b, sizeof(b), "%s%.3f", i ? ", " : "", rankMs[i]); ms += b; }
         ms += "]";
@@ -615,12 +656,12 @@ int main(int argc, char **argv)
                "\"last_iteration_ms\": %.3f, \"rank_iteration_ms\": %s, \"library\": \"%s\", "
                "\"last_iteration_kernel_ms\": {\"light\": %.3f, \"camera\": %.3f, \"connect_di\": %.3f, \"merge\": %.3f, \"grid_side\": %.3f, \"light_phase\": %.3f, \"camera_phase\": %.3f}, "
                "\"last_iteration_counters\": {\"lightVertices\": %lld, \"lightRays\": %lld, \"cameraRays\": %lld, \"shadowRays\": %lld, "
-               "\"mergeQueries\": %lld, \"mergeCandidates\": %lld, \"mergeAccepted\": %lld, \"connections\": %lld, \"lightSplats\": %lld}%s%s}\n",
+               "\"mergeQueries\": %lld, \"mergeCandidates\": %lld, \"mergeAccepted\": %lld, \"connections\": %lld, \"lightSplats\": %lld}%s%s%s}\n",
                sceneID, algoName.c_str(), resX, resY, iterations, renderers, seed, gpus > 0 ? gpus : 1, rcclRanks, wall, paths / wall / 1e6,
                mean[0] / (n3 / 3), mean[1] / (n3 / 3), mean[2] / (n3 / 3), st.msTotal, ms.c_str(), vcm_build_tag(),
                st.msLightKernel, st.msCameraKernel, st.msConnectKernels, st.msMergeKernel, st.msGrid, st.msLight, st.msCamera,
                st.lightVertices, st.lightRays, st.cameraRays, st.shadowRays, st.mergeQueries, st.mergeCandidates, st.mergeAccepted,
-               st.connections, st.lightSplats, robustJson, partsJson);
+               st.connections, st.lightSplats, robustJson, partsJson, displayJson);
     }
     else
         printf("scene %d, %s, %dx%d, %d iteration(s) on %d renderer(s): %.3f s wall clock, %.2f Mpaths/s\n", sceneID,

@@ -21,7 +21,7 @@ import os
 
 import numpy as np
 
-from ._abi import (DenoiseParams, DenoiseParams2, FEATURES, NoiseStats, PART_NAMES, PARTS, PartsStats, ROBUST_DEFAULT_BUCKETS, RobustStats, SceneDesc, SceneDesc2, SceneDesc3, SceneDesc4, SceneDesc5, SceneDesc6, SceneDesc7, Stats, SCENE_CONFIGS, VCM_MERGE_RECORD_FLOATS, ALGO_LIGHT_TRACE, ALGO_PPM, ALGO_BPM,
+from ._abi import (CURVES, DISPLAY_SOURCES, DenoiseParams, DenoiseParams2, DisplayParams, DisplayStats, FEATURES, IMAGE_BGR8, TRANSFERS, NoiseStats, PART_NAMES, PARTS, PartsStats, ROBUST_DEFAULT_BUCKETS, RobustStats, SceneDesc, SceneDesc2, SceneDesc3, SceneDesc4, SceneDesc5, SceneDesc6, SceneDesc7, Stats, SCENE_CONFIGS, VCM_MERGE_RECORD_FLOATS, ALGO_LIGHT_TRACE, ALGO_PPM, ALGO_BPM,
                    ALGO_BPT, ALGO_VCM)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -156,6 +156,18 @@ def load_library(require_gpu=True):
         L.vcm_denoise_defaults2.restype = None
         L.vcm_denoise2.argtypes = [vp, C.c_float, C.POINTER(DenoiseParams2)]
         L.vcm_denoise_buffers2.argtypes = [C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, C.c_int, vp, C.POINTER(DenoiseParams2), vp]
+        L.vcm_display_defaults.argtypes = [C.POINTER(DisplayParams)]
+        L.vcm_display_defaults.restype = None
+        L.vcm_display.argtypes = [vp, C.c_int, C.c_float, C.POINTER(DisplayParams)]
+        L.vcm_display_device.argtypes = [vp, C.POINTER(vp)]
+        L.vcm_read_display.argtypes = [vp, fp]
+        L.vcm_read_display_image.argtypes = [vp, C.c_int, C.POINTER(C.c_ubyte)]
+        L.vcm_get_display_stats.argtypes = [vp, C.POINTER(DisplayStats)]
+        L.vcm_display_buffers.argtypes = [C.c_int, C.c_int, C.c_int, vp, C.c_int, C.c_float, C.POINTER(DisplayParams), vp,
+                                          C.POINTER(DisplayStats), vp]
+        L.vcm_debug_display_max_blocks.argtypes = [C.c_int]
+        L.vcm_debug_display_max_blocks.restype = None
+        L.vcm_debug_read_display_histogram.argtypes = [C.POINTER(C.c_ulonglong)]
         L.vcm_sizeof_scene_desc.restype = C.c_uint
         L.vcm_sizeof_stats.restype = C.c_uint
         _lib = L
@@ -201,6 +213,44 @@ def denoise_params2(**kw):
             raise TypeError("unknown denoise parameter %r" % k)
         setattr(p, k, v)
     return p
+
+
+def display_params(**kw):
+    """vcm_display_defaults with some members replaced: curve ('clamp' / 'reinhard' / 'aces' / 'hable' or VCM_CURVE_*),
+    whitePoint, exposureEV, autoExposure, key, lowPercentile, highPercentile, minEV, maxEV, transfer ('gamma' / 'srgb' or
+    VCM_TRANSFER_*), gamma, bloomStrength, bloomLevels, dither, ditherSeed"""
+    L = load_library(require_gpu=False)
+    p = DisplayParams()
+    L.vcm_display_defaults(C.byref(p))
+    for k, v in kw.items():
+        if k not in [n for n, _ in DisplayParams._fields_]:
+            raise TypeError("unknown display parameter %r" % k)
+        if k == "curve" and isinstance(v, str):
+            v = CURVES[v]
+        if k == "transfer" and isinstance(v, str):
+            v = TRANSFERS[v]
+        setattr(p, k, v)
+    return p
+
+
+def display_tensors(color, out=None, scale=1.0, **params):
+    """vcm_display_buffers over torch tensors: color [H, W, 3] or [H, W, 4] float32, contiguous, on one GPU -> (out, stats):
+    out [H, W, 4] = {rgb in [0, 1], 1} (a new tensor when None), stats the dict of vcm_display_stats.  Runs on torch's
+    current stream of that device and waits for it (the stats); params: see display_params()"""
+    import torch
+    L = load_library()
+    if color.dtype != torch.float32 or not color.is_cuda or not color.is_contiguous() or color.dim() != 3 or color.shape[2] not in (3, 4):
+        raise ValueError("display_tensors wants a contiguous float32 GPU tensor [H, W, 3] or [H, W, 4]")
+    if out is None:
+        out = torch.empty((color.shape[0], color.shape[1], 4), dtype=torch.float32, device=color.device)
+    if out.dtype != torch.float32 or not out.is_cuda or not out.is_contiguous() or tuple(out.shape) != (color.shape[0], color.shape[1], 4):
+        raise ValueError("display_tensors wants out as a contiguous float32 GPU tensor [H, W, 4]")
+    dev = color.device.index if color.device.index is not None else torch.cuda.current_device()
+    p = display_params(**params)
+    st = DisplayStats()
+    _check(L, L.vcm_display_buffers(dev, int(color.shape[1]), int(color.shape[0]), color.data_ptr(), int(color.shape[2]), float(scale),
+                                    C.byref(p), out.data_ptr(), C.byref(st), torch.cuda.current_stream(dev).cuda_stream), "vcm_display_buffers")
+    return out, st.asdict()
 
 
 def denoise_tensors2(color, albedo, guide, mom, k, out=None, **params):
@@ -603,6 +653,40 @@ class HipBackend:
         _check(self.L, self.L.vcm_get_robust_stats(self.ctx, C.byref(st)), "vcm_get_robust_stats")
         return st.asdict()
 
+    # ---- the display transform ---------------------------------------------------
+    def display(self, source="framebuffer", scale=None, **params):
+        """vcm_display: `source` ('framebuffer', 'denoised', 'robust') * scale through exposure, bloom, tone curve and
+        transfer curve -> [H, W, 3] in [0, 1]; scale None: 1 / iterations for the framebuffer, 1 otherwise; params: see
+        display_params()"""
+        src = DISPLAY_SOURCES[source] if isinstance(source, str) else int(source)
+        if scale is None:
+            scale = 1.0 / self._fb_iterations if (src == DISPLAY_SOURCES["framebuffer"] and self._fb_iterations > 0) else 1.0
+        p = display_params(**params)
+        _check(self.L, self.L.vcm_display(self.ctx, src, scale, C.byref(p)), "vcm_display")
+        out = np.zeros((self.resy, self.resx, 3), np.float32)
+        _check(self.L, self.L.vcm_read_display(self.ctx, out.ctypes.data_as(C.POINTER(C.c_float))), "vcm_read_display")
+        return out
+
+    def display_device(self):
+        """device pointer of the last display()'s float4 image {rgb in [0, 1], 1}"""
+        p = C.c_void_p()
+        _check(self.L, self.L.vcm_display_device(self.ctx, C.byref(p)), "vcm_display_device")
+        return p.value
+
+    def display_stats(self):
+        """vcm_get_display_stats of the last display(): {autoEV, multiplier, logAvgLuminance, counted, zero, nonFinite,
+        clampedLow, clampedHigh, clipped}"""
+        st = DisplayStats()
+        _check(self.L, self.L.vcm_get_display_stats(self.ctx, C.byref(st)), "vcm_get_display_stats")
+        return st.asdict()
+
+    def read_display_image(self, fmt=IMAGE_BGR8):
+        """the last display() as bytes: fmt 0 BGR8 [H, W, 3], rows bottom-up (read_image's layout), fmt 2 RGBA8 [H, W, 4], rows
+        top-down, alpha 255"""
+        out = np.zeros((self.resy, self.resx, 3 if fmt == IMAGE_BGR8 else 4), np.uint8)
+        _check(self.L, self.L.vcm_read_display_image(self.ctx, fmt, out.ctypes.data_as(C.POINTER(C.c_ubyte))), "vcm_read_display_image")
+        return out
+
     # ---- the technique breakdown ------------------------------------------------
     def track_parts(self, on=True):
         """keep the five kinds of addends of the framebuffer -- emission, direct, connect, merge, lighttrace -- in planes of
@@ -714,6 +798,11 @@ class VertexCM:
         """GetFramebuffer() through the edge-avoiding denoiser (the reference has no such call); params: see
         denoise_params()"""
         return self.backend.denoise(1.0 / self.mIterations if self.mIterations > 0 else 1.0, **params)
+
+    def GetDisplay(self, **params):
+        """GetFramebuffer() through the display transform (the reference has no such call) -> [H, W, 3] in [0, 1]; params:
+        see display_params()"""
+        return self.backend.display("framebuffer", 1.0 / self.mIterations if self.mIterations > 0 else 1.0, **params)
 
     def render_until(self, noise, check_every=4, max_iterations=1024):
         """render_until() of this module on this renderer, which must be new: variance tracking is switched on first"""
