@@ -29,7 +29,6 @@
 using namespace vcm;
 
 static thread_local std::string g_err;
-static thread_local bool g_hipFailed;   /* the last failure on this thread came from the HIP runtime */
 static int fail(const char *what, const char *detail)
 {
     g_err = std::string(what) + ": " + (detail ? detail : "");
@@ -38,7 +37,7 @@ static int fail(const char *what, const char *detail)
 #define HIPCHK(expr)                                                            \
     do {                                                                        \
         hipError_t e_ = (expr);                                                 \
-        if (e_ != hipSuccess) { g_hipFailed = true; return fail(#expr, hipGetErrorString(e_)); } \
+        if (e_ != hipSuccess) return fail(#expr, hipGetErrorString(e_));        \
     } while (0)
 
 #define VCM_MAX_TRACE_WAVES (256 * 32)   /* upper bound of the persistent waves of K1 / K3 */
@@ -218,6 +217,10 @@ struct vcm_ctx : Scratch {
     unsigned long long *pend[2][4]; int nPend[2];   /* stamp slots waiting for the next kernel on [0] main, [1] side stream */
     vcm_stats lastStats;
 };
+/* the events that only order streams (no timing): ensure_device creates them, vcm_destroy destroys them */
+static hipEvent_t vcm_ctx::*const kOrderEvents[] = {
+    &vcm_ctx::evSortFork, &vcm_ctx::evSorted, &vcm_ctx::evZero, &vcm_ctx::evSplatFork, &vcm_ctx::evSplatDone, &vcm_ctx::evMergeDone,
+    &vcm_ctx::evSplatWork, &vcm_ctx::evResolved, &vcm_ctx::evPreMerge, &vcm_ctx::evFork, &vcm_ctx::evBbox, &vcm_ctx::evGrid };
 
 /* A ray-casting kernel is launched in the instantiation of the context's kind, under the wrappers it exists for (Wrap:
    scene_kind.h): f(tag) launches it with S = typename decltype(tag)::type.  What f evaluates, it evaluates once. */
@@ -480,40 +483,39 @@ static int ensure_device(vcm_ctx *c)
            for them cost 7-12 %: profiles/archive/r05k_prio.txt, r05r_configs.txt, profiles/archive/r07l_ab_2048_vcm_s1.txt; both switches retired in round 6) */
         HIPCHK(hipStreamCreateWithFlags(&c->side, hipStreamNonBlocking));
         HIPCHK(hipStreamCreateWithFlags(&c->splat, hipStreamNonBlocking));
-        HIPCHK(hipEventCreateWithFlags(&c->evSortFork, hipEventDisableTiming));
-        HIPCHK(hipEventCreateWithFlags(&c->evSorted, hipEventDisableTiming));
-        HIPCHK(hipEventCreateWithFlags(&c->evZero, hipEventDisableTiming));
-        HIPCHK(hipEventCreateWithFlags(&c->evSplatFork, hipEventDisableTiming));
-        HIPCHK(hipEventCreateWithFlags(&c->evSplatDone, hipEventDisableTiming));
-        HIPCHK(hipEventCreateWithFlags(&c->evMergeDone, hipEventDisableTiming));
-        HIPCHK(hipEventCreateWithFlags(&c->evSplatWork, hipEventDisableTiming));
-        HIPCHK(hipEventCreateWithFlags(&c->evResolved, hipEventDisableTiming));
-        HIPCHK(hipEventCreateWithFlags(&c->evPreMerge, hipEventDisableTiming));
-        HIPCHK(hipEventCreateWithFlags(&c->evFork, hipEventDisableTiming));
-        HIPCHK(hipEventCreateWithFlags(&c->evBbox, hipEventDisableTiming));
-        HIPCHK(hipEventCreateWithFlags(&c->evGrid, hipEventDisableTiming));
+        for (hipEvent_t vcm_ctx::*ev : kOrderEvents) HIPCHK(hipEventCreateWithFlags(&(c->*ev), hipEventDisableTiming));
         {   /* the scene in ONE device allocation: the DScene header, then the arrays it addresses by offset */
             const SceneHost &h = *c->scene;
-            struct Part { const void *src; size_t bytes; size_t off; } parts[21] = {
-                { h.prims.data(), h.prims.size() * sizeof(vcm_prim), 0 }, { h.materials.data(), h.materials.size() * sizeof(vcm_material), 0 },
-                { h.mat2light.data(), h.mat2light.size() * sizeof(int), 0 }, { h.lights.data(), h.lights.size() * sizeof(vcm_light), 0 },
-                { h.ops.data(), h.ops.size() * sizeof(PrimOp), 0 }, { h.pairs.data(), h.pairs.size() * sizeof(TriPair), 0 },
-                { h.nodes.data(), h.nodes.size() * sizeof(BvhNode), 0 }, { h.leafPrims.data(), h.leafPrims.size() * sizeof(int), 0 },
-                { h.fastPairs.data(), h.fastPairs.size() * sizeof(FastPair), 0 }, { h.fastSpheres.data(), h.fastSpheres.size() * sizeof(FastSphere), 0 },
-                { h.wide.data(), h.wide.size() * sizeof(BvhWide), 0 }, { h.leafData.data(), h.leafData.size() * sizeof(LeafPrim), 0 },
-                { h.fastRects.data(), h.fastRects.size() * sizeof(FastRect), 0 },
-                { h.envTexels.data(), h.envTexels.size() * sizeof(F4), 0 }, { h.envMarg.data(), h.envMarg.size() * sizeof(float), 0 },
-                { h.envCond.data(), h.envCond.size() * sizeof(float), 0 }, { h.envMargGuide.data(), h.envMargGuide.size() * sizeof(int), 0 },
-                { h.envCondGuide.data(), h.envCondGuide.size() * sizeof(int), 0 },
-                { h.pickPmf.data(), h.pickPmf.size() * sizeof(float), 0 }, { h.pickCdf.data(), h.pickCdf.size() * sizeof(float), 0 },
-                { h.pickGuideTable.data(), h.pickGuideTable.size() * sizeof(int), 0 } };
-            size_t total = (sizeof(DScene) + 255) & ~(size_t)255;
-            for (Part &p : parts) { p.off = total; total += (p.bytes + 255) & ~(size_t)255; }
-            if (dalloc(&c->dSceneBlob, total + 256)) return -1;
-            for (const Part &p : parts)
-                if (p.bytes) HIPCHK(hipMemcpy(c->dSceneBlob + p.off, p.src, p.bytes, hipMemcpyHostToDevice));
             DScene view;
             h.fill_scalars(view);
+            /* every array: its source, its bytes, and the member of the header that receives its offset in the blob */
+            const struct Part { const void *src; size_t bytes; long long DScene::*off; } parts[] = {
+                { h.prims.data(), h.prims.size() * sizeof(vcm_prim), &DScene::offPrims },
+                { h.materials.data(), h.materials.size() * sizeof(vcm_material), &DScene::offMaterials },
+                { h.mat2light.data(), h.mat2light.size() * sizeof(int), &DScene::offMat2light },
+                { h.lights.data(), h.lights.size() * sizeof(vcm_light), &DScene::offLights },
+                { h.ops.data(), h.ops.size() * sizeof(PrimOp), &DScene::offOps },
+                { h.pairs.data(), h.pairs.size() * sizeof(TriPair), &DScene::offPairs },
+                { h.nodes.data(), h.nodes.size() * sizeof(BvhNode), &DScene::offNodes },
+                { h.leafPrims.data(), h.leafPrims.size() * sizeof(int), &DScene::offLeafPrims },
+                { h.fastPairs.data(), h.fastPairs.size() * sizeof(FastPair), &DScene::offFastPairs },
+                { h.fastSpheres.data(), h.fastSpheres.size() * sizeof(FastSphere), &DScene::offFastSpheres },
+                { h.wide.data(), h.wide.size() * sizeof(BvhWide), &DScene::offWide },
+                { h.leafData.data(), h.leafData.size() * sizeof(LeafPrim), &DScene::offLeafData },
+                { h.fastRects.data(), h.fastRects.size() * sizeof(FastRect), &DScene::offFastRects },
+                { h.envTexels.data(), h.envTexels.size() * sizeof(F4), &DScene::offEnvTexels },
+                { h.envMarg.data(), h.envMarg.size() * sizeof(float), &DScene::offEnvMarg },
+                { h.envCond.data(), h.envCond.size() * sizeof(float), &DScene::offEnvCond },
+                { h.envMargGuide.data(), h.envMargGuide.size() * sizeof(int), &DScene::offEnvMargGuide },
+                { h.envCondGuide.data(), h.envCondGuide.size() * sizeof(int), &DScene::offEnvCondGuide },
+                { h.pickPmf.data(), h.pickPmf.size() * sizeof(float), &DScene::offPickPmf },
+                { h.pickCdf.data(), h.pickCdf.size() * sizeof(float), &DScene::offPickCdf },
+                { h.pickGuideTable.data(), h.pickGuideTable.size() * sizeof(int), &DScene::offPickGuide } };
+            size_t total = (sizeof(DScene) + 255) & ~(size_t)255;
+            for (const Part &p : parts) { view.*p.off = (long long)total; total += (p.bytes + 255) & ~(size_t)255; }
+            if (dalloc(&c->dSceneBlob, total + 256)) return -1;
+            for (const Part &p : parts)
+                if (p.bytes) HIPCHK(hipMemcpy(c->dSceneBlob + view.*p.off, p.src, p.bytes, hipMemcpyHostToDevice));
             c->intPhong = true;
             for (const vcm_material &m : h.materials)
                 if ((m.phong[0] != 0.f || m.phong[1] != 0.f || m.phong[2] != 0.f) && !dm_pow_is_int_case(m.phongExp)) c->intPhong = false;
@@ -523,15 +525,6 @@ static int ensure_device(vcm_ctx *c)
                 const bool rects = quads && (view.nFastRects[0] + view.nFastRects[1] + view.nFastRects[2]) > 0;
                 c->kind = scene_kind_of({ c->envMap, !h.nodes.empty(), c->intPhong, rects, quads });
             }
-            view.offPrims = (long long)parts[0].off; view.offMaterials = (long long)parts[1].off;
-            view.offMat2light = (long long)parts[2].off; view.offLights = (long long)parts[3].off;
-            view.offOps = (long long)parts[4].off; view.offPairs = (long long)parts[5].off;
-            view.offNodes = (long long)parts[6].off; view.offLeafPrims = (long long)parts[7].off;
-            view.offFastPairs = (long long)parts[8].off; view.offFastSpheres = (long long)parts[9].off;
-            view.offWide = (long long)parts[10].off; view.offLeafData = (long long)parts[11].off; view.offFastRects = (long long)parts[12].off;
-            view.offEnvTexels = (long long)parts[13].off; view.offEnvMarg = (long long)parts[14].off; view.offEnvCond = (long long)parts[15].off;
-            view.offEnvMargGuide = (long long)parts[16].off; view.offEnvCondGuide = (long long)parts[17].off;
-            view.offPickPmf = (long long)parts[18].off; view.offPickCdf = (long long)parts[19].off; view.offPickGuide = (long long)parts[20].off;
             c->dScene = reinterpret_cast<DScene *>(c->dSceneBlob);
             HIPCHK(hipMemcpy(c->dScene, &view, sizeof(DScene), hipMemcpyHostToDevice));
         }
@@ -749,6 +742,40 @@ static void trace_launch_shape(int nLocal, int *blocks, int *chunk, bool lightPa
     *chunk = ch < 64 ? 64 : (ch > 256 && !ce ? 256 : ch);
 }
 
+/* ---- what the read-back entry points of the image products share ---- */
+
+/* One read-back: a device temporary of `bytes`, `launch(temporary)` on the context's stream (it returns the HIP error of
+   what it launched), the copy to `host` (NULL: none), the wait for the stream.  The temporary is freed behind the wait, on
+   every path.  Whatever has to come before the launch (join_splats, need_*) is the caller's. */
+template <class Launch>
+static int read_back(vcm_ctx *c, const char *who, size_t bytes, void *host, Launch &&launch)
+{
+    char *d = NULL;
+    if (dalloc(&d, bytes)) return -1;
+    hipError_t e = launch((void *)d);
+    if (e == hipSuccess && host) e = hipMemcpyAsync(host, d, bytes, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    (void)hipFree(d);
+    if (e != hipSuccess) return fail(who, hipGetErrorString(e));
+    return 0;
+}
+
+/* One reduction to the host: stream-ordered scratch of `cap` partial accumulators and the result behind them,
+   `launch(partials, result)` on stream s, the result copied to *out.  The scratch goes back behind the copy; then the host
+   waits for s. */
+template <class Acc, class Launch>
+static int reduce_to_host(const char *who, int cap, Acc *out, hipStream_t s, Launch &&launch)
+{
+    Acc *scratch = NULL;
+    HIPCHK(hipMallocAsync((void **)&scratch, (size_t)(cap + 1) * sizeof(Acc), s));
+    hipError_t e = launch(scratch, scratch + cap);
+    if (e == hipSuccess) e = hipMemcpyAsync(out, scratch + cap, sizeof(Acc), hipMemcpyDeviceToHost, s);
+    (void)hipFreeAsync(scratch, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (e != hipSuccess) return fail(who, hipGetErrorString(e));
+    return 0;
+}
+
 extern "C" {
 
 const char *vcm_last_error(void) { return g_err.c_str(); }
@@ -838,74 +865,63 @@ static vcm_ctx *create_from_host(SceneHost *h, int algorithm, float radiusFactor
     return c;
 }
 
+} // extern "C"
+
+/* vcm_create_sharded .. vcm_create_sharded7: `convert` turns the level's description into the SceneHost, `who` names the
+   level in the refusals */
+template <class Desc>
+static vcm_ctx *create_from_desc(const char *who, bool (*convert)(const Desc &, SceneHost &, std::string &), const Desc *scene, int algorithm,
+                                 float radiusFactor, float radiusAlpha, int seed, int device, int rank, int worldSize)
+{
+    if (!scene) { fail(who, "scene is NULL"); return NULL; }
+    SceneHost *h = new (std::nothrow) SceneHost();
+    std::string err;
+    if (!h || !convert(*scene, *h, err)) { delete h; fail(who, err.c_str()); return NULL; }
+    return create_from_host(h, algorithm, radiusFactor, radiusAlpha, seed, device, rank, worldSize);
+}
+
+extern "C" {
+
 vcm_ctx *vcm_create_sharded(const vcm_scene_desc *scene, int algorithm, float radiusFactor, float radiusAlpha,
                             int seed, int device, int rank, int worldSize)
 {
-    if (!scene) { fail("vcm_create", "scene is NULL"); return NULL; }
-    SceneHost *h = new (std::nothrow) SceneHost();
-    std::string err;
-    if (!h || !scene_host_from_desc(*scene, *h, err)) { delete h; fail("vcm_create", err.c_str()); return NULL; }
-    return create_from_host(h, algorithm, radiusFactor, radiusAlpha, seed, device, rank, worldSize);
+    return create_from_desc("vcm_create", scene_host_from_desc, scene, algorithm, radiusFactor, radiusAlpha, seed, device, rank, worldSize);
 }
 
 vcm_ctx *vcm_create_sharded2(const vcm_scene_desc2 *scene, int algorithm, float radiusFactor, float radiusAlpha,
                              int seed, int device, int rank, int worldSize)
 {
-    if (!scene) { fail("vcm_create2", "scene is NULL"); return NULL; }
-    SceneHost *h = new (std::nothrow) SceneHost();
-    std::string err;
-    if (!h || !scene_host_from_desc2(*scene, *h, err)) { delete h; fail("vcm_create2", err.c_str()); return NULL; }
-    return create_from_host(h, algorithm, radiusFactor, radiusAlpha, seed, device, rank, worldSize);
+    return create_from_desc("vcm_create2", scene_host_from_desc2, scene, algorithm, radiusFactor, radiusAlpha, seed, device, rank, worldSize);
 }
 
 vcm_ctx *vcm_create_sharded3(const vcm_scene_desc3 *scene, int algorithm, float radiusFactor, float radiusAlpha,
                              int seed, int device, int rank, int worldSize)
 {
-    if (!scene) { fail("vcm_create3", "scene is NULL"); return NULL; }
-    SceneHost *h = new (std::nothrow) SceneHost();
-    std::string err;
-    if (!h || !scene_host_from_desc3(*scene, *h, err)) { delete h; fail("vcm_create3", err.c_str()); return NULL; }
-    return create_from_host(h, algorithm, radiusFactor, radiusAlpha, seed, device, rank, worldSize);
+    return create_from_desc("vcm_create3", scene_host_from_desc3, scene, algorithm, radiusFactor, radiusAlpha, seed, device, rank, worldSize);
 }
 
 vcm_ctx *vcm_create_sharded4(const vcm_scene_desc4 *scene, int algorithm, float radiusFactor, float radiusAlpha,
                              int seed, int device, int rank, int worldSize)
 {
-    if (!scene) { fail("vcm_create4", "scene is NULL"); return NULL; }
-    SceneHost *h = new (std::nothrow) SceneHost();
-    std::string err;
-    if (!h || !scene_host_from_desc4(*scene, *h, err)) { delete h; fail("vcm_create4", err.c_str()); return NULL; }
-    return create_from_host(h, algorithm, radiusFactor, radiusAlpha, seed, device, rank, worldSize);
+    return create_from_desc("vcm_create4", scene_host_from_desc4, scene, algorithm, radiusFactor, radiusAlpha, seed, device, rank, worldSize);
 }
 
 vcm_ctx *vcm_create_sharded5(const vcm_scene_desc5 *scene, int algorithm, float radiusFactor, float radiusAlpha,
                              int seed, int device, int rank, int worldSize)
 {
-    if (!scene) { fail("vcm_create5", "scene is NULL"); return NULL; }
-    SceneHost *h = new (std::nothrow) SceneHost();
-    std::string err;
-    if (!h || !scene_host_from_desc5(*scene, *h, err)) { delete h; fail("vcm_create5", err.c_str()); return NULL; }
-    return create_from_host(h, algorithm, radiusFactor, radiusAlpha, seed, device, rank, worldSize);
+    return create_from_desc("vcm_create5", scene_host_from_desc5, scene, algorithm, radiusFactor, radiusAlpha, seed, device, rank, worldSize);
 }
 
 vcm_ctx *vcm_create_sharded6(const vcm_scene_desc6 *scene, int algorithm, float radiusFactor, float radiusAlpha,
                              int seed, int device, int rank, int worldSize)
 {
-    if (!scene) { fail("vcm_create6", "scene is NULL"); return NULL; }
-    SceneHost *h = new (std::nothrow) SceneHost();
-    std::string err;
-    if (!h || !scene_host_from_desc6(*scene, *h, err)) { delete h; fail("vcm_create6", err.c_str()); return NULL; }
-    return create_from_host(h, algorithm, radiusFactor, radiusAlpha, seed, device, rank, worldSize);
+    return create_from_desc("vcm_create6", scene_host_from_desc6, scene, algorithm, radiusFactor, radiusAlpha, seed, device, rank, worldSize);
 }
 
 vcm_ctx *vcm_create_sharded7(const vcm_scene_desc7 *scene, int algorithm, float radiusFactor, float radiusAlpha,
                              int seed, int device, int rank, int worldSize)
 {
-    if (!scene) { fail("vcm_create7", "scene is NULL"); return NULL; }
-    SceneHost *h = new (std::nothrow) SceneHost();
-    std::string err;
-    if (!h || !scene_host_from_desc7(*scene, *h, err)) { delete h; fail("vcm_create7", err.c_str()); return NULL; }
-    return create_from_host(h, algorithm, radiusFactor, radiusAlpha, seed, device, rank, worldSize);
+    return create_from_desc("vcm_create7", scene_host_from_desc7, scene, algorithm, radiusFactor, radiusAlpha, seed, device, rank, worldSize);
 }
 
 /* Which device a renderer-per-host-core host puts its next renderer on (vcm_next_device).  The reference's driver
@@ -1025,11 +1041,7 @@ void vcm_destroy(vcm_ctx *c)
         for (int i = 0; i < EV_COUNT; i++) (void)hipEventDestroy(c->ev[i]);
         (void)hipStreamSynchronize(c->side);
         (void)hipStreamSynchronize(c->splat);
-        (void)hipEventDestroy(c->evSortFork); (void)hipEventDestroy(c->evSorted); (void)hipEventDestroy(c->evZero);
-        (void)hipEventDestroy(c->evFork); (void)hipEventDestroy(c->evBbox); (void)hipEventDestroy(c->evGrid);
-        (void)hipEventDestroy(c->evSplatFork); (void)hipEventDestroy(c->evSplatDone);
-        (void)hipEventDestroy(c->evMergeDone); (void)hipEventDestroy(c->evSplatWork); (void)hipEventDestroy(c->evResolved);
-        (void)hipEventDestroy(c->evPreMerge);
+        for (hipEvent_t vcm_ctx::*ev : kOrderEvents) (void)hipEventDestroy(c->*ev);
         (void)hipStreamDestroy(c->side);
         (void)hipStreamDestroy(c->splat);
         if (c->ownStream) (void)hipStreamDestroy(c->stream);
@@ -1622,12 +1634,10 @@ static int vcm_import_sorted_light_records_impl(vcm_ctx *c, const void *gathered
 }
 extern "C" int vcm_sort_light_records(vcm_ctx *c, void *dstDev, long long strideRecords)
 {
-    g_hipFailed = false;
     return abort_iteration(c, vcm_sort_light_records_impl(c, dstDev, strideRecords));
 }
 extern "C" int vcm_import_sorted_light_records(vcm_ctx *c, const void *gathered, const long long *counts, int nSeg, long long strideRecords)
 {
-    g_hipFailed = false;
     return abort_iteration(c, vcm_import_sorted_light_records_impl(c, gathered, counts, nSeg, strideRecords));
 }
 
@@ -2016,12 +2026,12 @@ static int vcm_space_import_results_impl(vcm_ctx *c, const void *resultsDev, lon
     c->mergeImported = true;
     return 0;
 }
-extern "C" int vcm_space_histogram(vcm_ctx *c, int axis, float *lo, float *binWidth, int *hist256) { g_hipFailed = false; return abort_iteration(c, vcm_space_histogram_impl(c, axis, lo, binWidth, hist256)); }
-extern "C" int vcm_space_set_slabs(vcm_ctx *c, int axis, const float *splits, int nSlabs) { g_hipFailed = false; return abort_iteration(c, vcm_space_set_slabs_impl(c, axis, splits, nSlabs)); }
-extern "C" int vcm_space_partition_light(vcm_ctx *c, void *dstDev, long long strideRecords, long long *counts) { g_hipFailed = false; return abort_iteration(c, vcm_space_partition_light_impl(c, dstDev, strideRecords, counts)); }
-extern "C" int vcm_space_partition_queries(vcm_ctx *c, void *dstDev, long long strideQueries, long long *counts) { g_hipFailed = false; return abort_iteration(c, vcm_space_partition_queries_impl(c, dstDev, strideQueries, counts)); }
-extern "C" int vcm_space_merge(vcm_ctx *c, const void *queriesDev, const long long *counts, int nSeg, long long stride, void *resultsDev) { g_hipFailed = false; return abort_iteration(c, vcm_space_merge_impl(c, queriesDev, counts, nSeg, stride, resultsDev)); }
-extern "C" int vcm_space_import_results(vcm_ctx *c, const void *resultsDev, long long stride) { g_hipFailed = false; return abort_iteration(c, vcm_space_import_results_impl(c, resultsDev, stride)); }
+extern "C" int vcm_space_histogram(vcm_ctx *c, int axis, float *lo, float *binWidth, int *hist256) { return abort_iteration(c, vcm_space_histogram_impl(c, axis, lo, binWidth, hist256)); }
+extern "C" int vcm_space_set_slabs(vcm_ctx *c, int axis, const float *splits, int nSlabs) { return abort_iteration(c, vcm_space_set_slabs_impl(c, axis, splits, nSlabs)); }
+extern "C" int vcm_space_partition_light(vcm_ctx *c, void *dstDev, long long strideRecords, long long *counts) { return abort_iteration(c, vcm_space_partition_light_impl(c, dstDev, strideRecords, counts)); }
+extern "C" int vcm_space_partition_queries(vcm_ctx *c, void *dstDev, long long strideQueries, long long *counts) { return abort_iteration(c, vcm_space_partition_queries_impl(c, dstDev, strideQueries, counts)); }
+extern "C" int vcm_space_merge(vcm_ctx *c, const void *queriesDev, const long long *counts, int nSeg, long long stride, void *resultsDev) { return abort_iteration(c, vcm_space_merge_impl(c, queriesDev, counts, nSeg, stride, resultsDev)); }
+extern "C" int vcm_space_import_results(vcm_ctx *c, const void *resultsDev, long long stride) { return abort_iteration(c, vcm_space_import_results_impl(c, resultsDev, stride)); }
 
 static int vcm_merge_impl(vcm_ctx *c)
 {   /* vertexcm.hxx:530-538 for all camera vertices, then :544 */
@@ -2150,7 +2160,6 @@ static int vcm_merge_impl(vcm_ctx *c)
 /* a HIP failure inside a phase ends the iteration and returns the arena */
 int vcm_begin_iteration(vcm_ctx *c, int iteration, unsigned minLen, unsigned maxLen)
 {
-    g_hipFailed = false;
     if (c && c->inIteration) return fail("vcm_begin_iteration", "previous iteration not ended");   /* it stays open */
     return abort_iteration(c, vcm_begin_iteration_impl(c, iteration, minLen, maxLen));
 }
@@ -2163,17 +2172,14 @@ int vcm_is_wavefront(vcm_ctx *c, unsigned maxLen)
 }
 int vcm_import_light_records(vcm_ctx *c, const void *devPtr, const long long *counts, int nSeg, long long strideRecords)
 {
-    g_hipFailed = false;
     return abort_iteration(c, vcm_import_light_records_impl(c, devPtr, counts, nSeg, strideRecords));
 }
 int vcm_local_light_bbox(vcm_ctx *c, float *min3, float *max3, long long *count)
 {
-    g_hipFailed = false;
     return abort_iteration(c, vcm_local_light_bbox_impl(c, min3, max3, count));
 }
 int vcm_set_grid_bbox(vcm_ctx *c, const float *min3, const float *max3)
 {
-    g_hipFailed = false;
     return abort_iteration(c, vcm_set_grid_bbox_impl(c, min3, max3));
 }
 /* allocate now what the first iteration would allocate (context buffers, the device's scratch arena) */
@@ -2182,7 +2188,6 @@ int vcm_reserve(vcm_ctx *c, unsigned maxLen)
     if (!c) return fail("vcm_reserve", "ctx is NULL");
     if (c->inIteration) return fail("vcm_reserve", "iteration in progress");
     if (maxLen > 255) return fail("vcm_reserve", "maxPathLength > 255 unsupported");
-    g_hipFailed = false;
     if (ensure_device(c)) return -1;
     const int S = c->renderer ? 1 : ((maxLen >= 2) ? (int)maxLen - 1 : 1);
     const int L = c->renderer ? 1 : ((maxLen >= 1) ? (int)maxLen : 1);
@@ -2190,10 +2195,10 @@ int vcm_reserve(vcm_ctx *c, unsigned maxLen)
     if (c->holdsArena) arena_release(c, false);
     return rc;
 }
-int vcm_trace_light(vcm_ctx *c) { g_hipFailed = false; return abort_iteration(c, vcm_trace_light_impl(c)); }
-int vcm_build_grid(vcm_ctx *c) { g_hipFailed = false; return abort_iteration(c, vcm_build_grid_impl(c)); }
-int vcm_trace_camera(vcm_ctx *c) { g_hipFailed = false; return abort_iteration(c, vcm_trace_camera_impl(c)); }
-int vcm_merge(vcm_ctx *c) { g_hipFailed = false; return abort_iteration(c, vcm_merge_impl(c)); }
+int vcm_trace_light(vcm_ctx *c) { return abort_iteration(c, vcm_trace_light_impl(c)); }
+int vcm_build_grid(vcm_ctx *c) { return abort_iteration(c, vcm_build_grid_impl(c)); }
+int vcm_trace_camera(vcm_ctx *c) { return abort_iteration(c, vcm_trace_camera_impl(c)); }
+int vcm_merge(vcm_ctx *c) { return abort_iteration(c, vcm_merge_impl(c)); }
 
 static int vcm_end_iteration_impl(vcm_ctx *c)
 {
@@ -2201,18 +2206,14 @@ static int vcm_end_iteration_impl(vcm_ctx *c)
     if (join_grid(c)) return -1;
     if (!c->resolveInFlight && join_splats(c)) return -1;   /* (a merge-free algorithm never waited; K5 aside: the next camera pass waits) */
     if (flush_stamps(c, c->stream) || (c->deviceReady && flush_stamps(c, c->side))) return -1;
-    if (c->trackVariance) {
-        /* behind this iteration's last write to the framebuffer: K5 on the splat stream (the next iteration's splats and K5
-           follow on that stream; every reader joins it through evSplatDone), else the main stream, which has joined */
-        hipStream_t s = c->resolveInFlight ? c->splat : c->stream;
-        HIPCHK(var_launch_update(c->N, c->dFb, c->fbIterations + 1, c->dVarPrev, c->dVarMom, s));
-        if (c->resolveInFlight) HIPCHK(hipEventRecord(c->evSplatDone, c->splat));
-    }
-    if (c->robustBuckets) {   /* the same place on the same stream, behind the variance update when both are on */
-        hipStream_t s = c->resolveInFlight ? c->splat : c->stream;
+    /* the trackers' updates run behind this iteration's last write to the framebuffer: K5 on the splat stream (the next
+       iteration's splats and K5 follow on that stream; every reader joins it through evSplatDone, recorded anew behind the
+       last update), else the main stream, which has joined */
+    hipStream_t s = c->resolveInFlight ? c->splat : c->stream;
+    if (c->trackVariance) HIPCHK(var_launch_update(c->N, c->dFb, c->fbIterations + 1, c->dVarPrev, c->dVarMom, s));
+    if (c->robustBuckets)   /* behind the variance update when both are on */
         HIPCHK(robust_launch_update(c->N, c->dFb, c->fbIterations + 1, c->robustBuckets, c->dRobPrev, c->dRobBuckets, s));
-        if (c->resolveInFlight) HIPCHK(hipEventRecord(c->evSplatDone, c->splat));
-    }
+    if ((c->trackVariance || c->robustBuckets) && c->resolveInFlight) HIPCHK(hipEventRecord(c->evSplatDone, c->splat));
     c->fbIterations++;
     c->iterations++;   /* :547 */
     c->inIteration = false;
@@ -2226,7 +2227,6 @@ int vcm_end_iteration(vcm_ctx *c)
     /* a mis-ordered call is refused and the iteration stays open (the host can still call vcm_merge): tearing it down
        here would leave the light splats in the framebuffer without counting the iteration */
     if (!c->merged) return fail("vcm_end_iteration", "vcm_merge has not run");
-    g_hipFailed = false;
     return abort_iteration(c, vcm_end_iteration_impl(c));   /* a HIP failure ends the iteration like every other phase call */
 }
 
@@ -2278,24 +2278,21 @@ int vcm_unpin_host_memory(void *hostPtr)
     return 0;
 }
 
+/* k_encode_image of the N x 3 floats `rgb` into `out`, on the context's stream */
+static hipError_t launch_encode_image(vcm_ctx *c, const float *rgb, int format, float scale, float gamma, void *out)
+{
+    hipLaunchKernelGGL(k_encode_image, dim3(1024), dim3(256), 0, c->stream, rgb, c->resX, c->resY, format, scale, 1.f / gamma, (unsigned char *)out);
+    return hipGetLastError();
+}
+
 int vcm_read_image(vcm_ctx *c, int format, float scale, float gamma, unsigned char *outHost)
 {
     if (!c || !outHost) return fail("vcm_read_image", "NULL argument");
     if (format != VCM_IMAGE_BGR8 && format != VCM_IMAGE_RGBE) return fail("vcm_read_image", "unknown format");
     if (!(gamma > 0.f)) return fail("vcm_read_image", "gamma must be positive");
-    if (ensure_device(c)) return -1;
+    if (ensure_device(c) || join_splats(c)) return -1;
     const size_t bytes = (size_t)c->N * (format == VCM_IMAGE_BGR8 ? 3 : 4);
-    unsigned char *d = NULL;
-    if (dalloc(&d, bytes)) return -1;
-    if (join_splats(c)) { (void)hipFree(d); return -1; }
-    hipLaunchKernelGGL(k_encode_image, dim3(1024), dim3(256), 0, c->stream, (const float *)c->dFb, c->resX, c->resY, format,
-                       scale, 1.f / gamma, d);
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess) e = hipMemcpyAsync(outHost, d, bytes, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    (void)hipFree(d);
-    if (e != hipSuccess) { g_hipFailed = true; return fail("vcm_read_image", hipGetErrorString(e)); }
-    return 0;
+    return read_back(c, "vcm_read_image", bytes, outHost, [&](void *d) { return launch_encode_image(c, c->dFb, format, scale, gamma, d); });
 }
 
 int vcm_framebuffer_device(vcm_ctx *c, void **devPtr)
@@ -2361,7 +2358,6 @@ static int ensure_feature_buffers(vcm_ctx *c)
 int vcm_render_features(vcm_ctx *c)
 {
     if (!c) return fail("vcm_render_features", "ctx is NULL");
-    g_hipFailed = false;
     if (ensure_device(c)) return -1;
     if (ensure_feature_buffers(c)) return -1;
     HIPCHK(dn_launch_features(c->dScene, c->kind, c->resX, c->p0, c->nLocal, c->dGuide, c->dAlbedo, c->stream));
@@ -2372,21 +2368,14 @@ int vcm_render_features(vcm_ctx *c)
 /* n pixels x nComp floats of the float4 image `src`, from component comp0 on, to the host */
 static int read_f4_components(vcm_ctx *c, const char *who, const F4 *src, int comp0, int nComp, float *host)
 {
-    float *d = NULL;
-    if (dalloc(&d, (size_t)c->N * nComp)) return -1;
-    hipError_t e = dn_launch_unpack(c->N, src, comp0, nComp, d, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(host, d, (size_t)c->N * nComp * sizeof(float), hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    (void)hipFree(d);
-    if (e != hipSuccess) { g_hipFailed = true; return fail(who, hipGetErrorString(e)); }
-    return 0;
+    return read_back(c, who, (size_t)c->N * nComp * sizeof(float), host,
+                     [&](void *d) { return dn_launch_unpack(c->N, src, comp0, nComp, (float *)d, c->stream); });
 }
 
 int vcm_read_feature(vcm_ctx *c, int which, float *host)
 {
     if (!c || !host) return fail("vcm_read_feature", "NULL argument");
     if (which != VCM_FEATURE_ALBEDO && which != VCM_FEATURE_NORMAL && which != VCM_FEATURE_DEPTH) return fail("vcm_read_feature", "unknown feature");
-    g_hipFailed = false;
     if (!c->featuresValid && vcm_render_features(c)) return -1;
     if (use_device(c)) return -1;
     if (which == VCM_FEATURE_ALBEDO) return read_f4_components(c, "vcm_read_feature", c->dAlbedo, 0, 3, host);
@@ -2397,7 +2386,6 @@ int vcm_read_feature(vcm_ctx *c, int which, float *host)
 int vcm_features_device(vcm_ctx *c, void **albedoDev, void **guideDev)
 {
     if (!c || !albedoDev || !guideDev) return fail("vcm_features_device", "NULL argument");
-    g_hipFailed = false;
     if (!c->featuresValid && vcm_render_features(c)) return -1;
     *albedoDev = c->dAlbedo; *guideDev = c->dGuide;
     return 0;
@@ -2410,16 +2398,22 @@ static int refuse_sharded(vcm_ctx *c, const char *who)
     return 0;
 }
 
+/* the result and the two images the passes ping-pong between: allocated by the first vcm_denoise / vcm_denoise2 */
+static int ensure_denoise_buffers(vcm_ctx *c)
+{
+    if (c->dDenoised) return 0;
+    return (dalloc(&c->dDnA, (size_t)c->N) || dalloc(&c->dDnB, (size_t)c->N) || dalloc(&c->dDenoised, (size_t)c->N)) ? -1 : 0;
+}
+
 int vcm_denoise(vcm_ctx *c, float scale, const vcm_denoise_params *p)
 {
     if (!c) return fail("vcm_denoise", "ctx is NULL");
     if (refuse_sharded(c, "vcm_denoise")) return -1;
     if (const char *why = dn_check_params(p)) return fail("vcm_denoise", why);
     if (!dn_finite(scale)) return fail("vcm_denoise", "scale is not finite");
-    g_hipFailed = false;
     if (!c->featuresValid && vcm_render_features(c)) return -1;
     if (use_device(c)) return -1;
-    if (!c->dDenoised && (dalloc(&c->dDnA, (size_t)c->N) || dalloc(&c->dDnB, (size_t)c->N) || dalloc(&c->dDenoised, (size_t)c->N))) return -1;
+    if (ensure_denoise_buffers(c)) return -1;
     if (join_splats(c)) return -1;   /* the light splats / K5 of the last iteration add to the framebuffer on a stream of their own */
     HIPCHK(dn_launch_denoise(c->resX, c->resY, NULL, c->dFb, scale, c->dAlbedo, c->dGuide, c->dDenoised, c->dDnA, c->dDnB, *p, c->stream));
     c->denoisedValid = true;
@@ -2436,7 +2430,6 @@ static int need_denoised(vcm_ctx *c, const char *who)
 int vcm_read_denoised(vcm_ctx *c, float *rgbHost)
 {
     if (!c || !rgbHost) return fail("vcm_read_denoised", "NULL argument");
-    g_hipFailed = false;
     if (need_denoised(c, "vcm_read_denoised")) return -1;
     return read_f4_components(c, "vcm_read_denoised", c->dDenoised, 0, 3, rgbHost);
 }
@@ -2454,21 +2447,58 @@ int vcm_read_denoised_image(vcm_ctx *c, int format, float gamma, unsigned char *
     if (!c || !outHost) return fail("vcm_read_denoised_image", "NULL argument");
     if (format != VCM_IMAGE_BGR8 && format != VCM_IMAGE_RGBE) return fail("vcm_read_denoised_image", "unknown format");
     if (!(gamma > 0.f)) return fail("vcm_read_denoised_image", "gamma must be positive");
-    g_hipFailed = false;
     if (need_denoised(c, "vcm_read_denoised_image")) return -1;
     const size_t bytes = (size_t)c->N * (format == VCM_IMAGE_BGR8 ? 3 : 4);
-    float *rgb = NULL; unsigned char *d = NULL;
-    if (dalloc(&rgb, (size_t)c->N * 3)) return -1;
-    if (dalloc(&d, bytes)) { (void)hipFree(rgb); return -1; }
-    hipError_t e = dn_launch_unpack(c->N, c->dDenoised, 0, 3, rgb, c->stream);
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(k_encode_image, dim3(1024), dim3(256), 0, c->stream, (const float *)rgb, c->resX, c->resY, format, 1.f, 1.f / gamma, d);
-        e = hipGetLastError();
+    /* two temporaries, nested: the float3 image the encoder reads lives until the encoded one has been read back */
+    int rc = 0;
+    if (read_back(c, "vcm_read_denoised_image", (size_t)c->N * 3 * sizeof(float), NULL, [&](void *rgb) {
+            const hipError_t e = dn_launch_unpack(c->N, c->dDenoised, 0, 3, (float *)rgb, c->stream);
+            if (e == hipSuccess)
+                rc = read_back(c, "vcm_read_denoised_image", bytes, outHost,
+                               [&](void *d) { return launch_encode_image(c, (const float *)rgb, format, 1.f, gamma, d); });
+            return e;
+        })) return -1;
+    return rc;
+}
+
+/* ---- what the _buffers entry points share: they work on a caller's images, on a device and a stream it names ---- */
+static int buffers_size_ok(const char *who, long long width, long long height)   /* (an image of n pixels: n x 1) */
+{
+    if (width <= 0 || height <= 0 || width * height > 0x7fffffffll) return fail(who, "bad size");
+    return 0;
+}
+/* the last refusals of every _buffers call, behind those of its arguments; makes the device current */
+static int buffers_device(const char *who, int device)
+{
+    const int ndev = vcm_device_count();
+    if (ndev <= 0) return fail(who, "no HIP device available (this library has no CPU path)");
+    if (device < 0 || device >= ndev) return fail(who, "device index out of range");
+    HIPCHK(hipSetDevice(device));
+    return 0;
+}
+
+/* vcm_denoise_buffers (its parameters in `fixed`) and vcm_denoise_buffers2 (in `guided`, with the moments image and its
+   factor), behind the refusals of their arguments: the device, the two images the passes ping-pong between, the launch */
+static int denoise_buffers_run(const char *who, int device, int width, int height, const void *colorDev, const void *albedoDev, const void *guideDev,
+                               void *outDev, const vcm_denoise_params *fixed, const vcm_denoise_params2 *guided, const void *momDev,
+                               float varFactor, void *hipStream)
+{
+    if (buffers_device(who, device)) return -1;
+    hipStream_t s = (hipStream_t)hipStream;
+    const size_t bytes = (size_t)width * height * sizeof(F4);
+    F4 *a = NULL, *b = NULL;
+    if ((guided ? guided->passes : fixed->passes) > 0) {   /* stream-ordered scratch: it is given back behind the last pass, the host does not wait */
+        HIPCHK(hipMallocAsync((void **)&a, bytes, s));
+        const hipError_t e = hipMallocAsync((void **)&b, bytes, s);
+        if (e != hipSuccess) { (void)hipFreeAsync(a, s); return fail(who, hipGetErrorString(e)); }
     }
-    if (e == hipSuccess) e = hipMemcpyAsync(outHost, d, bytes, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    (void)hipFree(d); (void)hipFree(rgb);
-    if (e != hipSuccess) { g_hipFailed = true; return fail("vcm_read_denoised_image", hipGetErrorString(e)); }
+    const hipError_t e = guided
+        ? dn_launch_denoise2(width, height, (const F4 *)colorDev, NULL, 1.f, (const F4 *)albedoDev, (const F4 *)guideDev, (const F4 *)momDev, varFactor,
+                             (F4 *)outDev, a, b, *guided, s)
+        : dn_launch_denoise(width, height, (const F4 *)colorDev, NULL, 1.f, (const F4 *)albedoDev, (const F4 *)guideDev, (F4 *)outDev, a, b, *fixed, s);
+    if (a) (void)hipFreeAsync(a, s);
+    if (b) (void)hipFreeAsync(b, s);
+    if (e != hipSuccess) return fail(who, hipGetErrorString(e));
     return 0;
 }
 
@@ -2476,43 +2506,38 @@ int vcm_denoise_buffers(int device, int width, int height, const void *colorDev,
                         void *outDev, const vcm_denoise_params *p, void *hipStream)
 {
     if (!colorDev || !albedoDev || !guideDev || !outDev) return fail("vcm_denoise_buffers", "NULL image");
-    if (width <= 0 || height <= 0 || (long long)width * height > 0x7fffffffll) return fail("vcm_denoise_buffers", "bad size");
+    if (buffers_size_ok("vcm_denoise_buffers", width, height)) return -1;
     if (outDev == colorDev || outDev == albedoDev || outDev == guideDev) return fail("vcm_denoise_buffers", "outDev is one of the inputs");
     if (const char *why = dn_check_params(p)) return fail("vcm_denoise_buffers", why);
-    const int ndev = vcm_device_count();
-    if (ndev <= 0) return fail("vcm_denoise_buffers", "no HIP device available (this library has no CPU path)");
-    if (device < 0 || device >= ndev) return fail("vcm_denoise_buffers", "device index out of range");
-    g_hipFailed = false;
-    HIPCHK(hipSetDevice(device));
-    hipStream_t s = (hipStream_t)hipStream;
-    const size_t bytes = (size_t)width * height * sizeof(F4);
-    void *a = NULL, *b = NULL;
-    if (p->passes > 0) {   /* stream-ordered scratch: it is given back behind the last pass, the host does not wait */
-        HIPCHK(hipMallocAsync(&a, bytes, s));
-        hipError_t e = hipMallocAsync(&b, bytes, s);
-        if (e != hipSuccess) { (void)hipFreeAsync(a, s); g_hipFailed = true; return fail("vcm_denoise_buffers", hipGetErrorString(e)); }
-    }
-    hipError_t e = dn_launch_denoise(width, height, (const F4 *)colorDev, NULL, 1.f, (const F4 *)albedoDev, (const F4 *)guideDev, (F4 *)outDev,
-                                     (F4 *)a, (F4 *)b, *p, s);
-    if (a) (void)hipFreeAsync(a, s);
-    if (b) (void)hipFreeAsync(b, s);
-    if (e != hipSuccess) { g_hipFailed = true; return fail("vcm_denoise_buffers", hipGetErrorString(e)); }
+    return denoise_buffers_run("vcm_denoise_buffers", device, width, height, colorDev, albedoDev, guideDev, outDev, p, NULL, NULL, 0.f, hipStream);
+}
+
+/* ---- the three tracking switches (vcm_track_variance, vcm_track_robust, vcm_track_parts) ---- */
+/* what each of them refuses first, on or off */
+static int track_refuse(vcm_ctx *c, const char *who)
+{
+    if (!c) return fail(who, "ctx is NULL");
+    if (refuse_sharded(c, who)) return -1;
+    if (c->inIteration) return fail(who, "iteration in progress");
     return 0;
+}
+/* switching on, behind the switch's own refusals: only an empty framebuffer; then the device, and the stream behind
+   whatever still adds to the framebuffer, so that the switch can allocate and reset its images */
+static int track_prepare(vcm_ctx *c, const char *who)
+{
+    if (c->fbIterations != 0) return fail(who, "the framebuffer holds iterations already: switch tracking on before the first "
+                                               "iteration or right after vcm_clear_framebuffer");
+    if (ensure_device(c)) return -1;
+    return join_splats(c);
 }
 
 /* ---- per-pixel variance and the noise statistic (kernels: vcm_variance.hip) ---- */
 int vcm_track_variance(vcm_ctx *c, int on)
 {
-    if (!c) return fail("vcm_track_variance", "ctx is NULL");
-    if (refuse_sharded(c, "vcm_track_variance")) return -1;
-    if (c->inIteration) return fail("vcm_track_variance", "iteration in progress");
+    if (track_refuse(c, "vcm_track_variance")) return -1;
     if (!on) { c->trackVariance = false; return 0; }   /* the images stay until vcm_destroy; switching on again wants a clear */
-    if (c->fbIterations != 0) return fail("vcm_track_variance", "the framebuffer holds iterations already: switch tracking on before the first "
-                                                                 "iteration or right after vcm_clear_framebuffer");
-    g_hipFailed = false;
-    if (ensure_device(c)) return -1;
+    if (track_prepare(c, "vcm_track_variance")) return -1;
     if (!c->dVarPrev && (dalloc(&c->dVarPrev, (size_t)c->N) || dalloc(&c->dVarMom, (size_t)c->N))) return -1;
-    if (join_splats(c)) return -1;
     if (var_reset_images(c)) return -1;
     c->trackVariance = true;
     return 0;
@@ -2541,23 +2566,15 @@ int vcm_variance_device(vcm_ctx *c, void **momDev)
 int vcm_read_variance(vcm_ctx *c, float *rgbHost)
 {
     if (!c || !rgbHost) return fail("vcm_read_variance", "NULL argument");
-    g_hipFailed = false;
     if (need_variance(c, "vcm_read_variance")) return -1;
-    float *d = NULL;
-    if (dalloc(&d, (size_t)c->N * 3)) return -1;
-    hipError_t e = var_launch_read(c->N, c->dVarMom, c->fbIterations, d, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(rgbHost, d, (size_t)c->N * 3 * sizeof(float), hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    (void)hipFree(d);
-    if (e != hipSuccess) { g_hipFailed = true; return fail("vcm_read_variance", hipGetErrorString(e)); }
-    return 0;
+    return read_back(c, "vcm_read_variance", (size_t)c->N * 3 * sizeof(float), rgbHost,
+                     [&](void *d) { return var_launch_read(c->N, c->dVarMom, c->fbIterations, (float *)d, c->stream); });
 }
 
 int vcm_debug_read_variance_images(vcm_ctx *c, float *prevHost4, float *momHost4)
 {
     if (!c) return fail("vcm_debug_read_variance_images", "ctx is NULL");
     if (!c->trackVariance) return fail("vcm_debug_read_variance_images", "vcm_track_variance is off");
-    g_hipFailed = false;
     if (use_device(c) || join_splats(c)) return -1;
     if (prevHost4) HIPCHK(hipMemcpyAsync(prevHost4, c->dVarPrev, (size_t)c->N * sizeof(F4), hipMemcpyDeviceToHost, c->stream));
     if (momHost4) HIPCHK(hipMemcpyAsync(momHost4, c->dVarMom, (size_t)c->N * sizeof(F4), hipMemcpyDeviceToHost, c->stream));
@@ -2570,13 +2587,9 @@ static int noise_stats_of(const char *who, long long n, const F4 *prev, const F4
                           hipStream_t s)
 {
     const int cap = var_max_blocks();
-    VarAcc *scratch = NULL, result;   /* cap partials and the result behind them */
-    HIPCHK(hipMallocAsync((void **)&scratch, (size_t)(cap + 1) * sizeof(VarAcc), s));
-    hipError_t e = var_launch_stats(n, prev, mom, k, threshold, cap, scratch, scratch + cap, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(&result, scratch + cap, sizeof(VarAcc), hipMemcpyDeviceToHost, s);
-    (void)hipFreeAsync(scratch, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    if (e != hipSuccess) { g_hipFailed = true; return fail(who, hipGetErrorString(e)); }
+    VarAcc result;
+    if (reduce_to_host(who, cap, &result, s, [&](VarAcc *partials, VarAcc *total) {
+            return var_launch_stats(n, prev, mom, k, threshold, cap, partials, total, s); })) return -1;
     var_finish_stats(result, k, n, out);
     return 0;
 }
@@ -2584,20 +2597,8 @@ static int noise_stats_of(const char *who, long long n, const F4 *prev, const F4
 int vcm_get_noise_stats(vcm_ctx *c, float threshold, vcm_noise_stats *out)
 {
     if (!c || !out) return fail("vcm_get_noise_stats", "NULL argument");
-    g_hipFailed = false;
     if (need_variance(c, "vcm_get_noise_stats")) return -1;
     return noise_stats_of("vcm_get_noise_stats", c->N, c->dVarPrev, c->dVarMom, c->fbIterations, threshold, out, c->stream);
-}
-
-static int var_buffers_device(const char *who, int device, long long n)
-{
-    if (n <= 0 || n > 0x7fffffffll) return fail(who, "bad size");
-    const int ndev = vcm_device_count();
-    if (ndev <= 0) return fail(who, "no HIP device available (this library has no CPU path)");
-    if (device < 0 || device >= ndev) return fail(who, "device index out of range");
-    g_hipFailed = false;
-    HIPCHK(hipSetDevice(device));
-    return 0;
 }
 
 int vcm_variance_update_buffers(int device, long long n, const void *sumDev3, int k, void *prevDev, void *momDev, void *hipStream)
@@ -2606,7 +2607,7 @@ int vcm_variance_update_buffers(int device, long long n, const void *sumDev3, in
     if (k < 1) return fail("vcm_variance_update_buffers", "k counts the iterations from 1");
     if (prevDev == momDev || prevDev == sumDev3 || momDev == sumDev3) return fail("vcm_variance_update_buffers", "the three images must differ");
     if ((((uintptr_t)prevDev | (uintptr_t)momDev) & 15) || ((uintptr_t)sumDev3 & 3)) return fail("vcm_variance_update_buffers", "prevDev and momDev must be 16-byte aligned (float4 images), sumDev3 4-byte aligned");
-    if (var_buffers_device("vcm_variance_update_buffers", device, n)) return -1;
+    if (buffers_size_ok("vcm_variance_update_buffers", n, 1) || buffers_device("vcm_variance_update_buffers", device)) return -1;
     HIPCHK(var_launch_update(n, (const float *)sumDev3, k, (F4 *)prevDev, (F4 *)momDev, (hipStream_t)hipStream));
     return 0;
 }
@@ -2617,7 +2618,7 @@ int vcm_noise_stats_buffers(int device, long long n, const void *prevDev, const 
     if (!prevDev || !momDev || !out) return fail("vcm_noise_stats_buffers", "NULL argument");
     if (k < 2) return fail("vcm_noise_stats_buffers", "the variance needs at least two iterations");
     if (((uintptr_t)prevDev | (uintptr_t)momDev) & 15) return fail("vcm_noise_stats_buffers", "prevDev and momDev must be 16-byte aligned (float4 images)");
-    if (var_buffers_device("vcm_noise_stats_buffers", device, n)) return -1;
+    if (buffers_size_ok("vcm_noise_stats_buffers", n, 1) || buffers_device("vcm_noise_stats_buffers", device)) return -1;
     return noise_stats_of("vcm_noise_stats_buffers", n, (const F4 *)prevDev, (const F4 *)momDev, k, threshold, out, (hipStream_t)hipStream);
 }
 
@@ -2641,10 +2642,9 @@ int vcm_denoise2(vcm_ctx *c, float scale, const vcm_denoise_params2 *p)
     if (const char *why = dn_check_params2(p)) return fail("vcm_denoise2", why);
     if (!dn_finite(scale)) return fail("vcm_denoise2", "scale is not finite");
     if (!p->varianceGuided) { const vcm_denoise_params base = dn_base_params(*p); return vcm_denoise(c, scale, &base); }
-    g_hipFailed = false;
     if (need_variance(c, "vcm_denoise2")) return -1;   /* tracking on, k >= 2; joins the splat stream */
     if (!c->featuresValid && vcm_render_features(c)) return -1;
-    if (!c->dDenoised && (dalloc(&c->dDnA, (size_t)c->N) || dalloc(&c->dDnB, (size_t)c->N) || dalloc(&c->dDenoised, (size_t)c->N))) return -1;
+    if (ensure_denoise_buffers(c)) return -1;
     /* the colour is S scale = mean (k scale): its variance is M2 / (k (k - 1)) (k scale)^2 = M2 scale^2 k / (k - 1) */
     const float kf = (float)c->fbIterations, varFactor = (scale * scale) * (kf / (kf - 1.f));
     HIPCHK(dn_launch_denoise2(c->resX, c->resY, NULL, c->dFb, scale, c->dAlbedo, c->dGuide, c->dVarMom, varFactor, c->dDenoised, c->dDnA,
@@ -2663,43 +2663,19 @@ int vcm_denoise_buffers2(int device, int width, int height, const void *colorDev
     }
     if (!colorDev || !albedoDev || !guideDev || !momDev || !outDev) return fail("vcm_denoise_buffers2", "NULL image");
     if (k < 2) return fail("vcm_denoise_buffers2", "the variance needs at least two iterations");
-    if (width <= 0 || height <= 0 || (long long)width * height > 0x7fffffffll) return fail("vcm_denoise_buffers2", "bad size");
+    if (buffers_size_ok("vcm_denoise_buffers2", width, height)) return -1;
     if (outDev == colorDev || outDev == albedoDev || outDev == guideDev || outDev == momDev) return fail("vcm_denoise_buffers2", "outDev is one of the inputs");
-    const int ndev = vcm_device_count();
-    if (ndev <= 0) return fail("vcm_denoise_buffers2", "no HIP device available (this library has no CPU path)");
-    if (device < 0 || device >= ndev) return fail("vcm_denoise_buffers2", "device index out of range");
-    g_hipFailed = false;
-    HIPCHK(hipSetDevice(device));
-    hipStream_t s = (hipStream_t)hipStream;
-    const size_t bytes = (size_t)width * height * sizeof(F4);
-    void *a = NULL, *b = NULL;
-    if (p->passes > 0) {
-        HIPCHK(hipMallocAsync(&a, bytes, s));
-        hipError_t e = hipMallocAsync(&b, bytes, s);
-        if (e != hipSuccess) { (void)hipFreeAsync(a, s); g_hipFailed = true; return fail("vcm_denoise_buffers2", hipGetErrorString(e)); }
-    }
     const float varFactor = 1.f / (float)((double)k * (double)(k - 1));
-    hipError_t e = dn_launch_denoise2(width, height, (const F4 *)colorDev, NULL, 1.f, (const F4 *)albedoDev, (const F4 *)guideDev,
-                                      (const F4 *)momDev, varFactor, (F4 *)outDev, (F4 *)a, (F4 *)b, *p, s);
-    if (a) (void)hipFreeAsync(a, s);
-    if (b) (void)hipFreeAsync(b, s);
-    if (e != hipSuccess) { g_hipFailed = true; return fail("vcm_denoise_buffers2", hipGetErrorString(e)); }
-    return 0;
+    return denoise_buffers_run("vcm_denoise_buffers2", device, width, height, colorDev, albedoDev, guideDev, outDev, NULL, p, momDev, varFactor, hipStream);
 }
 
 /* ---- the firefly-robust estimate (kernels: vcm_robust.hip) ---- */
 int vcm_track_robust(vcm_ctx *c, int buckets)
 {
-    if (!c) return fail("vcm_track_robust", "ctx is NULL");
-    if (refuse_sharded(c, "vcm_track_robust")) return -1;
-    if (c->inIteration) return fail("vcm_track_robust", "iteration in progress");
+    if (track_refuse(c, "vcm_track_robust")) return -1;
     if (!buckets) { c->robustBuckets = 0; return 0; }   /* the images stay until vcm_destroy; switching on again wants a clear */
     if (!robust_buckets_ok(buckets)) return fail("vcm_track_robust", "buckets must be odd, 3 .. 15 (0 switches tracking off)");
-    if (c->fbIterations != 0) return fail("vcm_track_robust", "the framebuffer holds iterations already: switch tracking on before the first "
-                                                               "iteration or right after vcm_clear_framebuffer");
-    g_hipFailed = false;
-    if (ensure_device(c)) return -1;
-    if (join_splats(c)) return -1;
+    if (track_prepare(c, "vcm_track_robust")) return -1;
     if (c->dRobBuckets && c->robustAlloc != buckets) {   /* another M than last time: the planes are allocated anew */
         HIPCHK(hipStreamSynchronize(c->stream));
         (void)hipFree(c->dRobBuckets);
@@ -2726,7 +2702,6 @@ static int need_robust(vcm_ctx *c, const char *who)
 int vcm_robust_resolve(vcm_ctx *c)
 {
     if (!c) return fail("vcm_robust_resolve", "ctx is NULL");
-    g_hipFailed = false;
     if (need_robust(c, "vcm_robust_resolve")) return -1;
     HIPCHK(robust_launch_resolve(c->N, c->dRobPrev, c->dRobBuckets, c->fbIterations, c->robustBuckets, c->dRobOut, c->stream));
     return 0;
@@ -2751,7 +2726,6 @@ int vcm_debug_read_robust_images(vcm_ctx *c, float *prevHost4, float *bucketsHos
 {
     if (!c) return fail("vcm_debug_read_robust_images", "ctx is NULL");
     if (!c->robustBuckets) return fail("vcm_debug_read_robust_images", "vcm_track_robust is off");
-    g_hipFailed = false;
     if (use_device(c) || join_splats(c)) return -1;
     if (prevHost4) HIPCHK(hipMemcpyAsync(prevHost4, c->dRobPrev, (size_t)c->N * sizeof(F4), hipMemcpyDeviceToHost, c->stream));
     if (bucketsHost4) HIPCHK(hipMemcpyAsync(bucketsHost4, c->dRobBuckets, (size_t)c->N * (size_t)c->robustBuckets * sizeof(F4), hipMemcpyDeviceToHost, c->stream));
@@ -2763,13 +2737,9 @@ int vcm_debug_read_robust_images(vcm_ctx *c, float *prevHost4, float *bucketsHos
 static int robust_stats_of(const char *who, long long n, const F4 *prev, const F4 *buckets, int k, int M, vcm_robust_stats *out, hipStream_t s)
 {
     const int cap = var_max_blocks();
-    VarAcc *scratch = NULL, result;   /* cap partials and the result behind them */
-    HIPCHK(hipMallocAsync((void **)&scratch, (size_t)(cap + 1) * sizeof(VarAcc), s));
-    hipError_t e = robust_launch_stats(n, prev, buckets, k, M, cap, scratch, scratch + cap, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(&result, scratch + cap, sizeof(VarAcc), hipMemcpyDeviceToHost, s);
-    (void)hipFreeAsync(scratch, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    if (e != hipSuccess) { g_hipFailed = true; return fail(who, hipGetErrorString(e)); }
+    VarAcc result;
+    if (reduce_to_host(who, cap, &result, s, [&](VarAcc *partials, VarAcc *total) {
+            return robust_launch_stats(n, prev, buckets, k, M, cap, partials, total, s); })) return -1;
     robust_finish_stats(result, k, M, n, out);
     return 0;
 }
@@ -2777,7 +2747,6 @@ static int robust_stats_of(const char *who, long long n, const F4 *prev, const F
 int vcm_get_robust_stats(vcm_ctx *c, vcm_robust_stats *out)
 {
     if (!c || !out) return fail("vcm_get_robust_stats", "NULL argument");
-    g_hipFailed = false;
     if (need_robust(c, "vcm_get_robust_stats")) return -1;
     return robust_stats_of("vcm_get_robust_stats", c->N, c->dRobPrev, c->dRobBuckets, c->fbIterations, c->robustBuckets, out, c->stream);
 }
@@ -2788,7 +2757,8 @@ static int robust_buffers_check(const char *who, int device, long long n, int k,
     if (!robust_buckets_ok(buckets)) return fail(who, "buckets must be odd, 3 .. 15");
     if (k < 1) return fail(who, "k counts the iterations from 1");
     if (resolving && k < buckets) return fail(who, "the robust estimate needs at least as many iterations as buckets");
-    return var_buffers_device(who, device, n);
+    if (buffers_size_ok(who, n, 1)) return -1;
+    return buffers_device(who, device);
 }
 
 int vcm_robust_update_buffers(int device, long long n, const void *sumDev3, int k, int buckets, void *prevDev, void *bucketsDev, void *hipStream)
@@ -2845,10 +2815,10 @@ static int display_run(const char *who, int width, int height, const float *src,
         if (e == hipSuccess) e = hipStreamSynchronize(s);
         if (e == hipSuccess) { memcpy(g_dispHistogram, host, sizeof(g_dispHistogram)); g_dispHistogramValid = true; }
     }
-    if (e != hipSuccess) { g_hipFailed = true; return fail(who, hipGetErrorString(e)); }
+    if (e != hipSuccess) return fail(who, hipGetErrorString(e));
     disp_auto_exposure(host, p, stats);
     e = disp_launch_transform(width, height, src, channels, scale, (float)stats->multiplier, p, scratch, out, counters, s);
-    if (e != hipSuccess) { g_hipFailed = true; return fail(who, hipGetErrorString(e)); }
+    if (e != hipSuccess) return fail(who, hipGetErrorString(e));
     return 0;
 }
 
@@ -2859,7 +2829,6 @@ int vcm_display(vcm_ctx *c, int source, float scale, const vcm_display_params *p
     if (source != VCM_DISPLAY_FRAMEBUFFER && source != VCM_DISPLAY_DENOISED && source != VCM_DISPLAY_ROBUST) return fail("vcm_display", "unknown source");
     if (const char *why = disp_check_params(p)) return fail("vcm_display", why);
     if (!disp_finite(scale)) return fail("vcm_display", "scale is not finite");
-    g_hipFailed = false;
     const float *src = NULL;
     int channels = 4;
     if (source == VCM_DISPLAY_DENOISED) {
@@ -2907,7 +2876,6 @@ int vcm_display_device(vcm_ctx *c, void **devPtr)
 int vcm_read_display(vcm_ctx *c, float *rgbHost)
 {
     if (!c || !rgbHost) return fail("vcm_read_display", "NULL argument");
-    g_hipFailed = false;
     if (need_display(c, "vcm_read_display")) return -1;
     return read_f4_components(c, "vcm_read_display", c->dDisplay, 0, 3, rgbHost);
 }
@@ -2917,23 +2885,15 @@ int vcm_read_display_image(vcm_ctx *c, int format, unsigned char *outHost)
     if (!c || !outHost) return fail("vcm_read_display_image", "NULL argument");
     if (format == VCM_IMAGE_RGBE) return fail("vcm_read_display_image", "RGBE is a linear format: vcm_read_image writes it");
     if (format != VCM_IMAGE_BGR8 && format != VCM_IMAGE_RGBA8) return fail("vcm_read_display_image", "unknown format");
-    g_hipFailed = false;
     if (need_display(c, "vcm_read_display_image")) return -1;
     const size_t bytes = (size_t)c->N * (format == VCM_IMAGE_BGR8 ? 3 : 4);
-    unsigned char *d = NULL;
-    if (dalloc(&d, bytes)) return -1;
-    hipError_t e = disp_launch_encode(c->resX, c->resY, c->dDisplay, format, c->dispParams.dither, c->dispParams.ditherSeed, d, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(outHost, d, bytes, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    (void)hipFree(d);
-    if (e != hipSuccess) { g_hipFailed = true; return fail("vcm_read_display_image", hipGetErrorString(e)); }
-    return 0;
+    return read_back(c, "vcm_read_display_image", bytes, outHost, [&](void *d) {
+        return disp_launch_encode(c->resX, c->resY, c->dDisplay, format, c->dispParams.dither, c->dispParams.ditherSeed, (unsigned char *)d, c->stream); });
 }
 
 int vcm_get_display_stats(vcm_ctx *c, vcm_display_stats *out)
 {
     if (!c || !out) return fail("vcm_get_display_stats", "NULL argument");
-    g_hipFailed = false;
     if (need_display(c, "vcm_get_display_stats")) return -1;
     unsigned long long clipped = 0ull;
     HIPCHK(hipMemcpyAsync(&clipped, c->dDispCounters + VCM_DISP_CLIPPED, sizeof(clipped), hipMemcpyDeviceToHost, c->stream));
@@ -2947,17 +2907,13 @@ int vcm_display_buffers(int device, int width, int height, const void *colorDev,
                         void *outDev, vcm_display_stats *statsOut, void *hipStream)
 {
     if (!colorDev || !outDev) return fail("vcm_display_buffers", "NULL image");
-    if (width <= 0 || height <= 0 || (long long)width * height > 0x7fffffffll) return fail("vcm_display_buffers", "bad size");
+    if (buffers_size_ok("vcm_display_buffers", width, height)) return -1;
     if (channels != 3 && channels != 4) return fail("vcm_display_buffers", "channels must be 3 or 4");
     if (outDev == colorDev) return fail("vcm_display_buffers", "outDev is the input");
     if (((uintptr_t)outDev & 15) || ((uintptr_t)colorDev & 3)) return fail("vcm_display_buffers", "outDev must be 16-byte aligned (a float4 image), colorDev 4-byte aligned");
     if (const char *why = disp_check_params(p)) return fail("vcm_display_buffers", why);
     if (!disp_finite(scale)) return fail("vcm_display_buffers", "scale is not finite");
-    const int ndev = vcm_device_count();
-    if (ndev <= 0) return fail("vcm_display_buffers", "no HIP device available (this library has no CPU path)");
-    if (device < 0 || device >= ndev) return fail("vcm_display_buffers", "device index out of range");
-    g_hipFailed = false;
-    HIPCHK(hipSetDevice(device));
+    if (buffers_device("vcm_display_buffers", device)) return -1;
     hipStream_t s = (hipStream_t)hipStream;
     /* stream-ordered scratch: the counters, and behind them (256 bytes on) the bloom's levels; given back behind the last kernel */
     const size_t head = 4096, levels = p->bloomStrength > 0.f ? disp_bloom_scratch_f4(width, height, p->bloomLevels) * sizeof(F4) : 0;
@@ -2971,7 +2927,7 @@ int vcm_display_buffers(int device, int width, int height, const void *colorDev,
         unsigned long long clipped = 0ull;
         hipError_t e = hipMemcpyAsync(&clipped, (unsigned long long *)scratch + VCM_DISP_CLIPPED, sizeof(clipped), hipMemcpyDeviceToHost, s);
         if (e == hipSuccess) e = hipStreamSynchronize(s);
-        if (e != hipSuccess) { g_hipFailed = true; rc = fail("vcm_display_buffers", hipGetErrorString(e)); }
+        if (e != hipSuccess) rc = fail("vcm_display_buffers", hipGetErrorString(e));
         else { *statsOut = st; statsOut->clipped = (long long)clipped; }
     }
     (void)hipFreeAsync(scratch, s);
@@ -2991,18 +2947,12 @@ int vcm_debug_read_display_histogram(unsigned long long *out256)
 /* ---- the technique breakdown (kernels: vcm_parts.hip; the LIGHT_TRACE plane: flush_light_splats) ---- */
 int vcm_track_parts(vcm_ctx *c, int on)
 {
-    if (!c) return fail("vcm_track_parts", "ctx is NULL");
-    if (refuse_sharded(c, "vcm_track_parts")) return -1;
-    if (c->inIteration) return fail("vcm_track_parts", "iteration in progress");
+    if (track_refuse(c, "vcm_track_parts")) return -1;
     if (!on) { c->trackParts = false; return 0; }   /* the planes stay until vcm_destroy; switching on again wants a clear */
     if (c->renderer) return fail("vcm_track_parts", "VCM_ALGO_PATH_TRACE and VCM_ALGO_EYE_LIGHT have no technique split: the breakdown is that of the VertexCM algorithms");
     if (c->strictOrder) return fail("vcm_track_parts", "the context is in strict order: the technique breakdown reads what wavefront mode keeps apart");
-    if (c->fbIterations != 0) return fail("vcm_track_parts", "the framebuffer holds iterations already: switch tracking on before the first "
-                                                              "iteration or right after vcm_clear_framebuffer");
-    g_hipFailed = false;
-    if (ensure_device(c)) return -1;
+    if (track_prepare(c, "vcm_track_parts")) return -1;
     if (!c->dParts && dalloc(&c->dParts, (size_t)VCM_PART_COUNT * (size_t)c->N * 3)) return -1;
-    if (join_splats(c)) return -1;
     if (parts_reset_planes(c)) return -1;
     c->trackParts = true;
     return 0;
@@ -3027,22 +2977,14 @@ static int part_args_ok(const char *who, int part, float scale)
 int vcm_read_part(vcm_ctx *c, int part, float scale, float *rgbHost)
 {
     if (!c || !rgbHost) return fail("vcm_read_part", "NULL argument");
-    g_hipFailed = false;
     if (part_args_ok("vcm_read_part", part, scale) || need_parts(c, "vcm_read_part")) return -1;
-    float *d = NULL;
-    if (dalloc(&d, (size_t)c->N * 3)) return -1;
-    hipError_t e = parts_launch_read3(c->N, c->dParts + (size_t)part * (size_t)c->N * 3, scale, d, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(rgbHost, d, (size_t)c->N * 3 * sizeof(float), hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    (void)hipFree(d);
-    if (e != hipSuccess) { g_hipFailed = true; return fail("vcm_read_part", hipGetErrorString(e)); }
-    return 0;
+    return read_back(c, "vcm_read_part", (size_t)c->N * 3 * sizeof(float), rgbHost, [&](void *d) {
+        return parts_launch_read3(c->N, c->dParts + (size_t)part * (size_t)c->N * 3, scale, (float *)d, c->stream); });
 }
 
 int vcm_part_device(vcm_ctx *c, int part, float scale, void **devPtr)
 {
     if (!c || !devPtr) return fail("vcm_part_device", "NULL argument");
-    g_hipFailed = false;
     if (part_args_ok("vcm_part_device", part, scale) || need_parts(c, "vcm_part_device")) return -1;
     if (!c->dPartOut && dalloc(&c->dPartOut, (size_t)c->N)) return -1;
     HIPCHK(parts_launch_read4(c->N, c->dParts + (size_t)part * (size_t)c->N * 3, scale, c->dPartOut, c->stream));
@@ -3053,17 +2995,11 @@ int vcm_part_device(vcm_ctx *c, int part, float scale, void **devPtr)
 int vcm_get_parts_stats(vcm_ctx *c, vcm_parts_stats *out)
 {
     if (!c || !out) return fail("vcm_get_parts_stats", "NULL argument");
-    g_hipFailed = false;
     if (need_parts(c, "vcm_get_parts_stats")) return -1;
     const int cap = parts_max_blocks();
-    hipStream_t s = c->stream;
-    PartsAcc *scratch = NULL, result;   /* cap partials and the result behind them */
-    HIPCHK(hipMallocAsync((void **)&scratch, (size_t)(cap + 1) * sizeof(PartsAcc), s));
-    hipError_t e = parts_launch_stats(c->N, c->dParts, (size_t)c->N * 3, cap, scratch, scratch + cap, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(&result, scratch + cap, sizeof(PartsAcc), hipMemcpyDeviceToHost, s);
-    (void)hipFreeAsync(scratch, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    if (e != hipSuccess) { g_hipFailed = true; return fail("vcm_get_parts_stats", hipGetErrorString(e)); }
+    PartsAcc result;
+    if (reduce_to_host("vcm_get_parts_stats", cap, &result, c->stream, [&](PartsAcc *partials, PartsAcc *total) {
+            return parts_launch_stats(c->N, c->dParts, (size_t)c->N * 3, cap, partials, total, c->stream); })) return -1;
     parts_finish_stats(result, c->fbIterations, c->N, out);
     return 0;
 }

@@ -119,6 +119,21 @@ def test_no_cpu_fallback():
         VertexCM(sc, VertexCM.kVcm, 0.003, 0.75)
 
 
+def test_every_creator_refuses_a_null_scene_under_its_own_name():
+    """vcm_create .. vcm_create7 and vcm_create_sharded .. vcm_create_sharded7 return NULL for a NULL scene and name the
+    description level in the refusal: `vcm_create:` for level 1, `vcm_createN:` for N = 2 .. 7, in both families.  The NULL
+    check precedes the device check, so this needs no device."""
+    L = C.CDLL(LIB_PATH)   # a handle of its own: the prototypes set here are not the renderer's
+    L.vcm_last_error.restype = C.c_char_p
+    for level in ["", "2", "3", "4", "5", "6", "7"]:
+        for name, extra in (("vcm_create" + level, []), ("vcm_create_sharded" + level, [C.c_int] * 3)):
+            f = getattr(L, name)
+            f.restype = C.c_void_p
+            f.argtypes = [C.c_void_p, C.c_int, C.c_float, C.c_float, C.c_int] + extra
+            assert f(None, 4, 0.003, 0.75, 1234, *([0, 0, 1] if extra else [])) is None, name
+            assert L.vcm_last_error().decode() == "vcm_create%s: scene is NULL" % level, name
+
+
 def test_product_does_not_reference_oracle():
     """Nothing under smallvcm_amd/ (the shipped path) may include, import or link oracle/."""
     bad = []
