@@ -250,6 +250,24 @@ typedef struct vcm_scene_desc7 {
     const vcm_sampler *sampler;
 } vcm_scene_desc7;
 
+/* The optional fifth BSDF component of a material: a GGX microfacet lobe (reflection only, non-delta, one-sided like the
+ * Phong lobe; Schlick's Fresnel term over F0, the height-correlated Smith masking term, visible-normal sampling by the
+ * spherical cap, Dupuy & Benyoub 2023).  `ggx` is F0, the reflectance at normal incidence, each channel in [0, 1];
+ * `alpha` the GGX width in [0.01, 1] (alpha = roughness^2 of the usual artists' parameter).  ggx = {0, 0, 0}: the material
+ * has no such lobe, and alpha is not looked at.  DESIGN.md "Microfacet materials". */
+typedef struct vcm_material_ext {
+    float ggx[3];
+    float alpha;
+} vcm_material_ext;
+
+/* Scene description, version 8: a version-7 scene and one vcm_material_ext per material (nMaterials entries, copied).
+ * `materialExt` NULL, or every ggx zero, renders exactly what vcm_create7 renders, with the kernels it launches.  A lobe
+ * on a material that mat2light maps to a light is refused. */
+typedef struct vcm_scene_desc8 {
+    vcm_scene_desc7         base;
+    const vcm_material_ext *materialExt;
+} vcm_scene_desc8;
+
 /* VertexCM::AlgorithmType (src/vertexcm.hxx:182-204) -- same values */
 enum {
     VCM_ALGO_LIGHT_TRACE = 0,
@@ -367,6 +385,15 @@ vcm_ctx *vcm_create_sharded6(const vcm_scene_desc6 *scene, int algorithm,
 vcm_ctx *vcm_create7(const vcm_scene_desc7 *scene, int algorithm,
                      float radiusFactor, float radiusAlpha, int seed);
 vcm_ctx *vcm_create_sharded7(const vcm_scene_desc7 *scene, int algorithm,
+                             float radiusFactor, float radiusAlpha, int seed,
+                             int device, int rank, int worldSize);
+
+/* The same for a version-8 scene description (GGX lobes).  NULL with vcm_last_error() for a non-finite field, an F0
+ * channel outside [0, 1], an alpha outside [0.01, 1] on a material with a lobe, a lobe on an emitting material, or a bad
+ * version-7 scene; checked before a device is looked for. */
+vcm_ctx *vcm_create8(const vcm_scene_desc8 *scene, int algorithm,
+                     float radiusFactor, float radiusAlpha, int seed);
+vcm_ctx *vcm_create_sharded8(const vcm_scene_desc8 *scene, int algorithm,
                              float radiusFactor, float radiusAlpha, int seed,
                              int device, int rank, int worldSize);
 
@@ -613,6 +640,10 @@ const vcm_scene_desc6 *vcm_scene_file_desc6(const vcm_scene_file *scene);
 /* The same scene as a version-7 description: its base is vcm_scene_file_desc6's, its sampler that of the file's
  * `sampler sobol|philox` directive, NULL without one.  Points into the handle, like vcm_scene_file_desc. */
 const vcm_scene_desc7 *vcm_scene_file_desc7(const vcm_scene_file *scene);
+/* The same scene as a version-8 description: its base is vcm_scene_file_desc7's, materialExt is set when a material in
+ * use has a `Pr` line in its .mtl (Ks is then the F0 of a GGX lobe of alpha = max(Pr^2, 0.01)), NULL otherwise.  Points
+ * into the handle, like vcm_scene_file_desc. */
+const vcm_scene_desc8 *vcm_scene_file_desc8(const vcm_scene_file *scene);
 
 /* Environment maps from files: Radiance RGBE (.hdr: "#?RADIANCE" / "#?RGBE", FORMAT=32-bit_rle_rgbe, "-Y H +X W", flat
  * or new-style run-length scanlines) or PFM (.pfm: "PF", either byte order; its bottom-up rows are flipped), picked by

@@ -106,6 +106,10 @@ int vcm_debug_pixel_filter(vcm_ctx *ctx, int *kind, float *radius);
  * kernels of vcm_create6, VCM_SAMPLER_SOBOL: the WithSobol kinds). */
 int vcm_debug_sampler(vcm_ctx *ctx, int *kind);
 
+/* Whether a context launches the WithGgx kinds (1: some material has a GGX lobe; 0: it launches exactly the kernels of
+ * vcm_create7), and in *nLobes, if not NULL, how many materials have one. */
+int vcm_debug_ggx(vcm_ctx *ctx, int *nLobes);
+
 /* The rule that picks a context's kind from the five facts about its scene (csrc/scene_kind.h, scene_kind_of), for a
  * test of the rule itself: 0 SceneList, 1 SceneQuads, 2 SceneRects, 3 SceneBvh, 4 SceneBvhG, 5 SceneRectsE, 6 SceneListE,
  * 7 SceneBvhE.  A pure host function: it touches no device. */

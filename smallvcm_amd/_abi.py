@@ -197,6 +197,44 @@ def with_sampler(desc, kind):
     return d
 
 
+class MaterialExt(C.Structure):
+    """vcm_material_ext: the optional GGX lobe of a material -- F0 per channel in [0, 1] and the width alpha in
+    [0.01, 1]; ggx = (0, 0, 0): no lobe (include/smallvcm_amd.h)"""
+    _fields_ = [("ggx", C.c_float * 3), ("alpha", C.c_float)]
+
+
+class SceneDesc8(C.Structure):
+    """vcm_scene_desc8: a version-7 scene and one MaterialExt per material.  Like SceneDesc2 the arrays are owned by the
+    Python object that built it."""
+    _fields_ = [("base", SceneDesc7), ("materialExt", C.POINTER(MaterialExt))]
+
+    @property
+    def camera(self):
+        return self.base.camera
+
+
+def with_material_ext(desc, ext):
+    """a SceneDesc2 .. SceneDesc7 as a SceneDesc8 with the lobes `ext`: one (r, g, b, alpha) per material, or None
+    (materialExt = NULL).  The result keeps `desc` alive."""
+    if isinstance(desc, SceneDesc8):
+        desc = desc.base
+    d7 = desc if isinstance(desc, SceneDesc7) else with_sampler(desc, None)
+    d8 = SceneDesc8()
+    d8.base = d7
+    d8._keep = (getattr(d7, "_keep", None), d7)
+    if ext is not None:
+        n = int(d7.base.base.base.base.base.nMaterials)
+        if len(ext) != n:
+            raise ValueError("with_material_ext: %d entries for %d materials" % (len(ext), n))
+        arr = (MaterialExt * n)()
+        for m, e in enumerate(ext):
+            arr[m].ggx[:] = [float(x) for x in e[:3]]
+            arr[m].alpha = float(e[3])
+        d8.materialExt = C.cast(arr, C.POINTER(MaterialExt))
+        d8._keep = d8._keep + (arr,)
+    return d8
+
+
 class DenoiseParams(C.Structure):
     """vcm_denoise_params: a-trous passes (0 .. 12), the three edge-stopping sigmas, and whether the albedo is divided
     out before the first pass and multiplied back after the last (include/smallvcm_amd.h)"""

@@ -42,6 +42,8 @@
 //   .obj        v, f (triangles; polygons are fanned around their first vertex; v, v/vt, v/vt/vn, v//vn; negative
 //               = relative indices), usemtl, mtllib; everything else is skipped
 //   .mtl        newmtl, Kd -> mDiffuseReflectance, Ks + Ns -> mPhongReflectance / mPhongExponent (materials.hxx:54-65),
+//               Pr <r> (roughness, 0 .. 1) -> Ks becomes the F0 of a GGX lobe of alpha = max(r^2, 0.01) instead of a Phong
+//               lobe with Ns (vcm_material_ext, vcm_scene_file_desc8); illum mirror and glass keep their meaning;
 //               illum 3 | 5 -> mirror: mMirrorReflectance = Ks;  illum 4 | 6 | 7 | 9 -> glass: mIOR = Ni and
 //               mMirrorReflectance = Ks;  Ke != 0 -> every triangle of the material is an AreaLight of that intensity:
 //               a primitive with a material of its own whose mat2light entry names the light, and no reflectance,
@@ -87,6 +89,9 @@ struct vcm_scene_file {
     bool haveSampler = false;         /* `sampler` */
     vcm_sampler sampler;
     vcm_scene_desc7 desc7;
+    std::vector<vcm_material_ext> materialExt;   /* one per material once a `Pr` material is in use, else empty */
+    bool haveGgx = false;
+    vcm_scene_desc8 desc8;
     ~vcm_scene_file() { vcm_envmap_free(envmap); }
 };
 
@@ -230,7 +235,7 @@ vcm_envmap *envmap_load(const std::string &path)
     return m;
 }
 
-struct MtlEntry { vcm_material m; float ke[3]; bool emissive; int index; /* in materials, -1: not added yet */ };
+struct MtlEntry { vcm_material m; float ke[3]; bool emissive; int index; /* in materials, -1: not added yet */ vcm_material_ext x; /* `Pr`: its GGX lobe, else zero */ };
 
 struct Loader {
     vcm_scene_file *out;
@@ -278,6 +283,13 @@ struct Loader {
             it->second.index = (int)out->materials.size();
             out->materials.push_back(it->second.m);
             out->mat2light.push_back(-1);
+            const vcm_material_ext &x = it->second.x;
+            if (x.ggx[0] != 0.f || x.ggx[1] != 0.f || x.ggx[2] != 0.f) {
+                const vcm_material_ext none = { { 0.f, 0.f, 0.f }, 0.f };
+                out->materialExt.resize(out->materials.size(), none);
+                out->materialExt.back() = x;
+                out->haveGgx = true;
+            }
         }
         return it->second.index;
     }
@@ -305,14 +317,17 @@ struct Loader {
         std::string lineBuf;
         MtlEntry *cur = NULL;
         int illum = 2;
-        float ks[3] = { 0, 0, 0 }, ni = 1.f;
-        bool haveKs = false;
+        float ks[3] = { 0, 0, 0 }, ni = 1.f, pr = 0.f;
+        bool haveKs = false, havePr = false;
         auto finish = [&]() {
             if (!cur) return;
             const bool mirror = illum == 3 || illum == 5, glass = illum == 4 || illum == 6 || illum == 7 || illum == 9;
             if (mirror || glass) {
                 for (int k = 0; k < 3; k++) { cur->m.mirror[k] = haveKs ? ks[k] : 1.f; cur->m.phong[k] = 0.f; }
                 if (glass) cur->m.ior = ni;
+            } else if (haveKs && havePr) {   /* a GGX lobe: Ks is its F0, Ns is not looked at */
+                for (int k = 0; k < 3; k++) cur->x.ggx[k] = ks[k];
+                cur->x.alpha = pr * pr < 0.01f ? 0.01f : pr * pr;
             } else if (haveKs) {
                 for (int k = 0; k < 3; k++) cur->m.phong[k] = ks[k];
             }
@@ -328,13 +343,18 @@ struct Loader {
                 MtlEntry e;
                 vcm_make_material(&e.m);
                 e.ke[0] = e.ke[1] = e.ke[2] = 0.f; e.emissive = false; e.index = -1;
+                e.x.ggx[0] = e.x.ggx[1] = e.x.ggx[2] = 0.f; e.x.alpha = 0.f;
                 cur = &(mtl[name] = e);
-                illum = 2; haveKs = false; ni = 1.f;
+                illum = 2; haveKs = false; ni = 1.f; havePr = false;
             } else if (!cur) {
                 continue;
             } else if (key == "Kd") { if (!floats(p, cur->m.diffuse, 3)) { fclose(f); return fail(path + ": bad Kd"); } }
             else if (key == "Ks") { if (!floats(p, ks, 3)) { fclose(f); return fail(path + ": bad Ks"); } haveKs = true; }
             else if (key == "Ns") { if (!floats(p, &cur->m.phongExp, 1)) { fclose(f); return fail(path + ": bad Ns"); } }
+            else if (key == "Pr") {
+                if (!floats(p, &pr, 1) || !(pr >= 0.f && pr <= 1.f)) { fclose(f); return fail(path + ": bad Pr (a roughness in [0, 1])"); }
+                havePr = true;
+            }
             else if (key == "Ni") { if (!floats(p, &ni, 1)) { fclose(f); return fail(path + ": bad Ni"); } }
             else if (key == "illum") { illum = atoi(p); }
             else if (key == "Ke") {
@@ -555,6 +575,9 @@ struct Loader {
         out->desc6.filter = out->haveFilter ? &out->filter : NULL;
         out->desc7.base = out->desc6;
         out->desc7.sampler = out->haveSampler ? &out->sampler : NULL;
+        if (out->haveGgx) { const vcm_material_ext none = { { 0.f, 0.f, 0.f }, 0.f }; out->materialExt.resize(out->materials.size(), none); }
+        out->desc8.base = out->desc7;
+        out->desc8.materialExt = out->haveGgx ? out->materialExt.data() : NULL;
         return true;
     }
 };
@@ -597,6 +620,7 @@ const vcm_scene_desc4 *vcm_scene_file_desc4(const vcm_scene_file *s) { return s 
 const vcm_scene_desc5 *vcm_scene_file_desc5(const vcm_scene_file *s) { return s ? &s->desc5 : NULL; }
 const vcm_scene_desc6 *vcm_scene_file_desc6(const vcm_scene_file *s) { return s ? &s->desc6 : NULL; }
 const vcm_scene_desc7 *vcm_scene_file_desc7(const vcm_scene_file *s) { return s ? &s->desc7 : NULL; }
+const vcm_scene_desc8 *vcm_scene_file_desc8(const vcm_scene_file *s) { return s ? &s->desc8 : NULL; }
 
 vcm_envmap *vcm_envmap_load(const char *path)
 {

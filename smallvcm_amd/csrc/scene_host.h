@@ -55,6 +55,9 @@ struct SceneHost {
     float filterRadius = 0.f;
     /* the sampler (scene_host_set_sampler; PHILOX: the default), DScene::samplerKind */
     int sampler = VCM_SAMPLER_PHILOX;
+    /* the GGX lobes (scene_host_set_material_ext): one entry per material when some material has a lobe, else empty,
+       DScene::ggxOn */
+    std::vector<vcm_material_ext> materialExt;
     /* how lights are chosen (scene_host_set_pick; pickMode UNIFORM: no tables), DScene::pickMode ...; pickWeights are
        the weights before the mix and pickQuanta the m_i of pmf[i] = m_i 2^-23 (for reports and tests) */
     int pickMode = VCM_LIGHT_PICK_UNIFORM, pickGuide = 0;
@@ -81,6 +84,7 @@ struct SceneHost {
         d.offEnvCondGuide = (const char *)envCondGuide.data() - base;
         d.offPickPmf = (const char *)pickPmf.data() - base; d.offPickCdf = (const char *)pickCdf.data() - base;
         d.offPickGuide = (const char *)pickGuideTable.data() - base;
+        d.offMaterialExt = (const char *)materialExt.data() - base;
     }
     void fill_scalars(DScene &d) const
     {
@@ -104,6 +108,7 @@ struct SceneHost {
         d.pickMode = pickMode; d.pickGuide = pickGuide;
         d.filterKind = filterKind; d.filterRadius = filterRadius;
         d.samplerKind = sampler;
+        d.ggxOn = materialExt.empty() ? 0 : 1; d.offMaterialExt = 0;
         { const char *e = getenv("SMALLVCM_AMD_NO_RECTS"); if (e && e[0] == '1') d.nFastRects[0] = d.nFastRects[1] = d.nFastRects[2] = 0; }   /* measurement switch */
     }
 };
@@ -524,6 +529,32 @@ inline bool scene_host_set_sampler(SceneHost &s, const vcm_sampler *sampler, std
 inline bool scene_host_from_desc7(const vcm_scene_desc7 &sc, SceneHost &s, std::string &err)
 {
     return scene_host_from_desc6(sc.base, s, err) && scene_host_set_sampler(s, sc.sampler, err);
+}
+
+/* ---- the GGX lobes (vcm_core.h bsdf_eval_ggx) ---- */
+inline bool scene_host_set_material_ext(SceneHost &s, const vcm_material_ext *ext, std::string &err)
+{
+    s.materialExt.clear();
+    if (!ext) return true;
+    bool any = false;
+    for (size_t m = 0; m < s.materials.size(); m++) {
+        const vcm_material_ext &x = ext[m];
+        const std::string who = "materialExt[" + std::to_string(m) + "]: ";
+        if (!std::isfinite(x.ggx[0]) || !std::isfinite(x.ggx[1]) || !std::isfinite(x.ggx[2]) || !std::isfinite(x.alpha)) { err = who + "a field is not finite"; return false; }
+        for (int k = 0; k < 3; k++)
+            if (x.ggx[k] < 0.f || x.ggx[k] > 1.f) { err = who + "ggx (F0) must lie in [0, 1]"; return false; }
+        if (x.ggx[0] == 0.f && x.ggx[1] == 0.f && x.ggx[2] == 0.f) continue;
+        if (x.alpha < 0.01f || x.alpha > 1.f) { err = who + "alpha must lie in [0.01, 1]"; return false; }
+        if (s.mat2light[m] >= 0) { err = who + "a material that is a light cannot have a GGX lobe"; return false; }
+        any = true;
+    }
+    if (any) s.materialExt.assign(ext, ext + s.materials.size());   /* else: the version-7 scene */
+    return true;
+}
+
+inline bool scene_host_from_desc8(const vcm_scene_desc8 &sc, SceneHost &s, std::string &err)
+{
+    return scene_host_from_desc7(sc.base, s, err) && scene_host_set_material_ext(s, sc.materialExt, err);
 }
 
 /* ---- brute-force list: consecutive triangles in pairs, fields interleaved (vcm_core.h TriPair) ---- */

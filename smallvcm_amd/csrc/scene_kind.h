@@ -9,7 +9,10 @@
 // light (such a scene always has a table, so WithLights exists over the WithPick kinds alone).  A scene with the Sobol
 // sampler takes, in every kernel that draws (kWrapSobol), ONE kind per kind of scene: WithSobol over the widest chain
 // of the other wrappers the kernel has, whatever else the scene holds; there lens, filter and table are run-time
-// branches (vcm_core.h WithSobol).  Kernels that draw nothing are launched as without it.
+// branches (vcm_core.h WithSobol).  Kernels that draw nothing are launched as without it.  A scene with a GGX lobe
+// takes, in every kernel that handles a BSDF (kWrapGgx), WithGgx over that same widest chain, or over its WithSobol kind
+// when the scene also asks for the Sobol sampler and the kernel draws: at most two kinds per kernel and kind of scene,
+//     WithGgx<C>  and  WithGgx<WithSobol<C>>,   C = WidestChain<the kernel's lens / pick wrappers, S>::type.
 #ifndef SMALLVCM_AMD_SCENE_KIND_H
 #define SMALLVCM_AMD_SCENE_KIND_H
 
@@ -60,10 +63,10 @@ constexpr bool scene_kind_is_rects(SceneKind k) { return k == SceneKind::Rects |
 template <class S> struct SceneTag { using type = S; };
 
 /* the wrappers a kernel is instantiated for */
-enum : unsigned { kWrapNone = 0, kWrapLens = 1, kWrapPick = 2, kWrapSobol = 4 };
+enum : unsigned { kWrapNone = 0, kWrapLens = 1, kWrapPick = 2, kWrapSobol = 4, kWrapGgx = 8 };
 
 /* the wrappers a context launches with; lights implies pick (wrappers_valid) */
-struct SceneWrappers { bool lens, pick, lights; bool sobol = false; };
+struct SceneWrappers { bool lens, pick, lights; bool sobol = false; bool ggx = false; };
 constexpr bool wrappers_valid(SceneWrappers w) { return !w.lights || w.pick; }
 static_assert(wrappers_valid({ false, false, false }) && wrappers_valid({ true, true, false }) && wrappers_valid({ false, true, true }),
               "what a scene without / with the spot and sphere lights launches");
@@ -82,9 +85,29 @@ static_assert(WithSobol<WidestChain<kWrapLens | kWrapPick, SceneListE>::type>::k
               WithSobol<WidestChain<kWrapLens | kWrapPick, SceneListE>::type>::kEnvMap, "the Sobol kind carries every branch");
 static_assert(!WithLights<WithPick<WithLens<SceneRects>>>::kSobol && !SceneRects::kSobol, "no other kind draws from it");
 
+/* the kinds of a scene with GGX lobes */
+template <unsigned Wrap, class S> struct GgxChain {
+    using C = typename WidestChain<Wrap & (kWrapLens | kWrapPick), S>::type;
+    using philox = WithGgx<C>;
+    using sobol = WithGgx<WithSobol<C>>;
+};
+static_assert(std::is_same_v<GgxChain<kWrapLens | kWrapPick | kWrapSobol | kWrapGgx, SceneRects>::philox, WithGgx<WithLights<WithPick<WithLens<SceneRects>>>>>, "K3, the path tracer, strict K1, k_kat");
+static_assert(std::is_same_v<GgxChain<kWrapPick | kWrapSobol | kWrapGgx, SceneBvh>::sobol, WithGgx<WithSobol<WithLights<WithPick<SceneBvh>>>>>, "K1, k_connect_di under Sobol");
+static_assert(std::is_same_v<GgxChain<kWrapGgx, SceneList>::philox, WithGgx<SceneList>>, "k_connect_vc");
+static_assert(GgxChain<kWrapLens | kWrapPick, SceneListE>::sobol::kGgx && GgxChain<kWrapLens | kWrapPick, SceneListE>::sobol::kSobol &&
+              GgxChain<kWrapLens | kWrapPick, SceneListE>::sobol::kLens && GgxChain<kWrapLens | kWrapPick, SceneListE>::sobol::kPick &&
+              GgxChain<kWrapLens | kWrapPick, SceneListE>::sobol::kLights && GgxChain<kWrapLens | kWrapPick, SceneListE>::sobol::kEnvMap, "the GGX kind carries every branch");
+static_assert(GgxChain<kWrapLens, SceneBvh>::philox::kGgx && !GgxChain<kWrapLens, SceneBvh>::philox::kSobol, "under Philox it holds no Sobol draw");
+static_assert(!WithSobol<WithLights<WithPick<WithLens<SceneRects>>>>::kGgx && !SceneRects::kGgx && !DScene::kGgx, "no other kind holds the lobe");
+
 template <unsigned Wrap, class S, class F> void with_wrappers(SceneWrappers w, F &f)
 {
-    if constexpr (Wrap & kWrapSobol) {
+    if constexpr (Wrap & kWrapGgx) {
+        if (w.ggx) {
+            if constexpr (Wrap & kWrapSobol) { if (w.sobol) { f(SceneTag<typename GgxChain<Wrap, S>::sobol>{}); return; } }
+            f(SceneTag<typename GgxChain<Wrap, S>::philox>{});
+        } else with_wrappers<Wrap & ~kWrapGgx, S>(w, f);
+    } else if constexpr (Wrap & kWrapSobol) {
         if (w.sobol) f(SceneTag<WithSobol<typename WidestChain<Wrap & ~kWrapSobol, S>::type>>{});
         else with_wrappers<Wrap & ~kWrapSobol, S>(w, f);
     } else if constexpr (Wrap & kWrapLens) {

@@ -185,6 +185,8 @@ struct vcm_ctx : Scratch {
     bool pick;                        /* lights are chosen from a table: the WithPick kernels */
     bool lights;                      /* the scene holds a spot or a sphere light: WithLights over WithPick (then pick is set) */
     bool sobol;                       /* the scene asks for the Sobol sampler: the WithSobol kind of every kernel that draws */
+    bool ggx;                         /* some material has a GGX lobe: the WithGgx kind of every kernel that handles a BSDF, the _ggx twins of
+                                         the grid kernels, and k_merge_pairs_ggx / k_merge_walk_ggx as K4 */
     bool intPhong;                    /* every Phong exponent in use is an integer in [1, 65536]: the kernels whose pow is the binary
                                          exponentiation alone (detmath.h); otherwise the SceneList / SceneBvhG kernels and the general merge */
     /* feature buffers and denoiser (vcm_denoise.h): allocated by the first vcm_render_features / vcm_denoise */
@@ -224,12 +226,16 @@ static hipEvent_t vcm_ctx::*const kOrderEvents[] = {
 
 /* A ray-casting kernel is launched in the instantiation of the context's kind, under the wrappers it exists for (Wrap:
    scene_kind.h): f(tag) launches it with S = typename decltype(tag)::type.  What f evaluates, it evaluates once. */
-template <unsigned Wrap, class F> static void launch_kind(const vcm_ctx *c, F &&f) { with_scene_kind<Wrap>(c->kind, SceneWrappers{ c->lens || c->filter, c->pick, c->lights, c->sobol }, f); }
+template <unsigned Wrap, class F> static void launch_kind(const vcm_ctx *c, F &&f) { with_scene_kind<Wrap>(c->kind, SceneWrappers{ c->lens || c->filter, c->pick, c->lights, c->sobol, c->ggx }, f); }
 
 /* K4 of a context: k_merge_pairs or k_merge_walk (VCM_MERGE_*), with the pow its exponents allow */
 typedef void (*MergeKernel)(const DScene *, IterParams, GridStore, VertexStore, const int *, const int *, unsigned long long *, int, StampArgs);
-static MergeKernel merge_kernel(int mergeKind, bool intPhong)
+static MergeKernel merge_kernel(int mergeKind, bool intPhong, bool ggx)
 {
+    if (ggx) {
+        if (mergeKind == VCM_MERGE_PAIRS) return intPhong ? k_merge_pairs_ggx<true> : k_merge_pairs_ggx<false>;
+        return intPhong ? k_merge_walk_ggx<true> : k_merge_walk_ggx<false>;
+    }
     if (mergeKind == VCM_MERGE_PAIRS) return intPhong ? k_merge_pairs<true> : k_merge_pairs<false>;
     return intPhong ? k_merge_walk<true> : k_merge_walk<false>;
 }
@@ -510,7 +516,8 @@ static int ensure_device(vcm_ctx *c)
                 { h.envCondGuide.data(), h.envCondGuide.size() * sizeof(int), &DScene::offEnvCondGuide },
                 { h.pickPmf.data(), h.pickPmf.size() * sizeof(float), &DScene::offPickPmf },
                 { h.pickCdf.data(), h.pickCdf.size() * sizeof(float), &DScene::offPickCdf },
-                { h.pickGuideTable.data(), h.pickGuideTable.size() * sizeof(int), &DScene::offPickGuide } };
+                { h.pickGuideTable.data(), h.pickGuideTable.size() * sizeof(int), &DScene::offPickGuide },
+                { h.materialExt.data(), h.materialExt.size() * sizeof(vcm_material_ext), &DScene::offMaterialExt } };
             size_t total = (sizeof(DScene) + 255) & ~(size_t)255;
             for (const Part &p : parts) { view.*p.off = (long long)total; total += (p.bytes + 255) & ~(size_t)255; }
             if (dalloc(&c->dSceneBlob, total + 256)) return -1;
@@ -812,6 +819,7 @@ static vcm_ctx *create_from_host(SceneHost *h, int algorithm, float radiusFactor
     c->pick = h->pickMode != VCM_LIGHT_PICK_UNIFORM;
     c->lights = c->pick && scene_host_has_new_lights(*h);   /* such a scene always has a table (scene_host_lights_need_table) */
     c->sobol = h->sampler == VCM_SAMPLER_SOBOL;
+    c->ggx = !h->materialExt.empty();
     scene_host_build_accel(*h, scene_host_force_bvh());
     /* VertexCM::VertexCM vertexcm.hxx:222-244 */
     switch (algorithm) {
@@ -924,6 +932,12 @@ vcm_ctx *vcm_create_sharded7(const vcm_scene_desc7 *scene, int algorithm, float 
     return create_from_desc("vcm_create7", scene_host_from_desc7, scene, algorithm, radiusFactor, radiusAlpha, seed, device, rank, worldSize);
 }
 
+vcm_ctx *vcm_create_sharded8(const vcm_scene_desc8 *scene, int algorithm, float radiusFactor, float radiusAlpha,
+                             int seed, int device, int rank, int worldSize)
+{
+    return create_from_desc("vcm_create8", scene_host_from_desc8, scene, algorithm, radiusFactor, radiusAlpha, seed, device, rank, worldSize);
+}
+
 /* Which device a renderer-per-host-core host puts its next renderer on (vcm_next_device).  The reference's driver
  * builds one renderer per host core and runs them concurrently (smallvcm.cxx:61-72, :99-108): on a multi-GPU node the
  * drop-in deals them round-robin over the visible devices -- every GPU renders whole iterations of its renderers
@@ -992,6 +1006,11 @@ vcm_ctx *vcm_create6(const vcm_scene_desc6 *scene, int algorithm, float radiusFa
 vcm_ctx *vcm_create7(const vcm_scene_desc7 *scene, int algorithm, float radiusFactor, float radiusAlpha, int seed)
 {
     return vcm_create_sharded7(scene, algorithm, radiusFactor, radiusAlpha, seed, next_device(true), 0, 1);
+}
+
+vcm_ctx *vcm_create8(const vcm_scene_desc8 *scene, int algorithm, float radiusFactor, float radiusAlpha, int seed)
+{
+    return vcm_create_sharded8(scene, algorithm, radiusFactor, radiusAlpha, seed, next_device(true), 0, 1);
 }
 
 void vcm_destroy(vcm_ctx *c)
@@ -1281,7 +1300,7 @@ static int flush_light_splats(vcm_ctx *c)
         F4 *list = c->dSplatList;
         if (c->prezeroed) HIPCHK(hipStreamWaitEvent(q, c->evZero, 0));
         else if (zero_ranges(q, pixCount, ((size_t)c->N + 1) * sizeof(int))) return -1;
-        launch_kind<kWrapLens | kWrapSobol>(c, [&](auto tag) {
+        launch_kind<kWrapLens | kWrapSobol | kWrapGgx>(c, [&](auto tag) {
             using S = typename decltype(tag)::type;
             hipLaunchKernelGGL((k_connect_camera<S>), dim3(task_blocks(c->nLocal)), dim3(256), 0, q, c->dScene, c->P, c->store,
                                (const int *)c->dSlotOfVertex, (const int *)c->dLocalTotal, c->dFb, c->dSplat, pixCount,
@@ -1352,13 +1371,13 @@ static int vcm_trace_light_impl(vcm_ctx *c)
     const bool wf = !c->strictOrder;
     if (!wf && join_splats(c)) return -1;   /* the fused K1 splats straight into dFb: behind a K5 the last (aside) iteration left in flight */
     if (wf)
-        launch_kind<kWrapPick | kWrapSobol>(c, [&](auto tag) {
+        launch_kind<kWrapPick | kWrapSobol | kWrapGgx>(c, [&](auto tag) {
             using S = typename decltype(tag)::type;
             hipLaunchKernelGGL((k_light_trace<1, S>), dim3(blocks), dim3(VCM_TRACE_BLOCK), 0, c->stream, c->dScene, c->P, c->store,
                                c->dFb, c->dRngLight, c->dStats, chunk, take_stamps(c, c->stream), c->vs.count + 16, c->dHdr);
         });
     else
-        launch_kind<kWrapLens | kWrapPick | kWrapSobol>(c, [&](auto tag) {
+        launch_kind<kWrapLens | kWrapPick | kWrapSobol | kWrapGgx>(c, [&](auto tag) {
             using S = typename decltype(tag)::type;
             hipLaunchKernelGGL((k_light_trace<0, S>), dim3(blocks), dim3(VCM_TRACE_BLOCK), 0, c->stream, c->dScene, c->P, c->store,
                                c->dFb, c->dRngLight, c->dStats, chunk, take_stamps(c, c->stream), c->vs.count + 16, c->dHdr);
@@ -1380,7 +1399,7 @@ static int vcm_trace_light_impl(vcm_ctx *c)
            also publishes the counts and the box K1 kept (k_set_counts / k_bbox_finalize folded in). */
         c->recordsValid = c->useVM && c->world > 1 && !c->sortedExchange;   /* (vcm_export_light_records still materialises them on demand) */
         const bool fold = c->world == 1;
-        hipLaunchKernelGGL(k_compact_records, dim3(aux_blocks(c->nLocal)), dim3(256), 0, c->stream, (const DScene *)c->dScene, c->P, c->store, c->dPathStart,
+        hipLaunchKernelGGL((c->ggx ? k_compact_records_ggx : k_compact_records), dim3(aux_blocks(c->nLocal)), dim3(256), 0, c->stream, (const DScene *)c->dScene, c->P, c->store, c->dPathStart,
                            c->dRecordsLocal, c->dSlotOfVertex, c->recordsValid ? 1 : 0, fold ? c->dHdr : (GridHeader *)NULL,
                            (const int *)c->dLocalTotal, (fold && c->bboxFromLight) ? 1 : 0);
         HIPCHK(hipGetLastError());
@@ -1403,7 +1422,7 @@ static int vcm_trace_light_impl(vcm_ctx *c)
 static int ensure_records(vcm_ctx *c)
 {
     if (c->recordsValid || !c->useVM) return 0;
-    hipLaunchKernelGGL(k_compact_records, dim3(aux_blocks(c->nLocal)), dim3(256), 0, c->stream, (const DScene *)c->dScene, c->P, c->store, c->dPathStart,
+    hipLaunchKernelGGL((c->ggx ? k_compact_records_ggx : k_compact_records), dim3(aux_blocks(c->nLocal)), dim3(256), 0, c->stream, (const DScene *)c->dScene, c->P, c->store, c->dPathStart,
                        c->dRecordsLocal, c->dSlotOfVertex, 1, (GridHeader *)NULL, (const int *)c->dLocalTotal, 0);
     HIPCHK(hipGetLastError());
     c->recordsValid = true;
@@ -1603,7 +1622,7 @@ static int vcm_sort_light_records_impl(vcm_ctx *c, void *dstDev, long long strid
                            (const int *)c->dCellStart, recs.records ? (const int *)NULL : (const int *)c->dSlotOfVertex, c->dUnsorted);
     }
     uint32_t *slab = (uint32_t *)dstDev;
-    hipLaunchKernelGGL(k_cell_rank_pack, g, b, 0, c->stream, (const DScene *)c->dScene, (const GridHeader *)c->dHdr, recs, (const int *)c->dCellStart,
+    hipLaunchKernelGGL((c->ggx ? k_cell_rank_pack_ggx : k_cell_rank_pack), g, b, 0, c->stream, (const DScene *)c->dScene, (const GridHeader *)c->dHdr, recs, (const int *)c->dCellStart,
                        (const I4 *)c->dUnsorted, sorted, slab, (int *)(slab + (size_t)strideRecords * VCM_SORTED_WORDS), nCells, K, nBlocks);
     HIPCHK(hipGetLastError());
     return 0;
@@ -1714,7 +1733,7 @@ static int vcm_build_grid_impl(vcm_ctx *c)
                                (const int *)c->dSortedIndex, (const int *)c->dCellStart,
                                recs.records ? (const int *)NULL : (const int *)c->dSlotOfVertex, c->dUnsorted);
         }
-        hipLaunchKernelGGL(k_cell_rank_gather, g, b, 0, q, (const DScene *)c->dScene, (const GridHeader *)c->dHdr, recs,
+        hipLaunchKernelGGL((c->ggx ? k_cell_rank_gather_ggx : k_cell_rank_gather), g, b, 0, q, (const DScene *)c->dScene, (const GridHeader *)c->dHdr, recs,
                            (const int *)c->dCellStart, (const I4 *)c->dUnsorted, sorted, c->dGx,
                            c->dGy, c->dGz, c->dGb, c->dG1, c->dG2, c->dG3, c->dSortedIndex);
         if (mark_on(c, EV_GRID, q)) return -1;
@@ -1756,7 +1775,7 @@ static int vcm_trace_camera_impl(vcm_ctx *c)
     if (mark(c, EV_CAMERA_K0)) return -1;
     if (c->renderer) {   /* PathTracer / EyeLight: colour + jittered pixel per path; K5 adds them in path order */
         if (c->renderer == 1)
-            launch_kind<kWrapLens | kWrapPick | kWrapSobol>(c, [&](auto tag) {
+            launch_kind<kWrapLens | kWrapPick | kWrapSobol | kWrapGgx>(c, [&](auto tag) {
                 using S = typename decltype(tag)::type;
                 hipLaunchKernelGGL((k_path_trace<S>), dim3(blocks), dim3(VCM_TRACE_BLOCK), 0, c->stream, c->dScene, c->P, c->dCamOut,
                                    c->dRngCam, c->dStats, chunk, take_stamps(c, c->stream), c->vs.count + 8);
@@ -1784,7 +1803,7 @@ static int vcm_trace_camera_impl(vcm_ctx *c)
             if (c->prezeroed) HIPCHK(hipStreamWaitEvent(c->stream, c->evZero, 0));
             else if (zero_ranges(c->stream, c->dQueryCount, ((size_t)c->P.nBuckets + 1) * sizeof(int))) return -1;
         }
-        launch_kind<kWrapLens | kWrapPick | kWrapSobol>(c, [&](auto tag) {
+        launch_kind<kWrapLens | kWrapPick | kWrapSobol | kWrapGgx>(c, [&](auto tag) {
             using S = typename decltype(tag)::type;
             hipLaunchKernelGGL((k_camera_trace<1, S>), dim3(blocks), dim3(VCM_TRACE_BLOCK), 0, c->stream, c->dScene, c->P,
                                c->store, grid_of(c), c->vs, c->dCamOut, c->dCamMask, c->dRngCam, c->dStats, chunk, take_stamps(c, c->stream));
@@ -1833,7 +1852,7 @@ static int vcm_trace_camera_impl(vcm_ctx *c)
                    critical path (profiles/archive/r07f_timeline1024.txt) */
                 HIPCHK(hipEventRecord(c->evSplatFork, c->stream));
                 HIPCHK(hipStreamWaitEvent(c->splat, c->evSplatFork, 0));
-                launch_kind<kWrapNone>(c, [&](auto tag) {
+                launch_kind<kWrapGgx>(c, [&](auto tag) {
                     using S = typename decltype(tag)::type;
                     hipLaunchKernelGGL((k_connect_vc<S>), dim3(task_blocks(c->nLocal)), dim3(VCM_TASK_BLOCK), 0, c->splat, c->dScene, c->P, c->vs,
                                        c->store, c->dStats);
@@ -1841,7 +1860,7 @@ static int vcm_trace_camera_impl(vcm_ctx *c)
                 HIPCHK(hipEventRecord(c->evSplatDone, c->splat));   /* also behind the light splats: same stream */
                 c->splatInFlight = true;
             }
-            launch_kind<kWrapPick | kWrapSobol>(c, [&](auto tag) {
+            launch_kind<kWrapPick | kWrapSobol | kWrapGgx>(c, [&](auto tag) {
                 using S = typename decltype(tag)::type;
                 hipLaunchKernelGGL((k_connect_di<S>), dim3(task_blocks(c->nLocal)), dim3(VCM_TASK_BLOCK), 0, c->stream, c->dScene, c->P, c->vs,
                                    c->dStats, c->scatteredInDI ? (const int *)c->dQueryStart : (const int *)NULL,
@@ -1851,7 +1870,7 @@ static int vcm_trace_camera_impl(vcm_ctx *c)
         if (mark(c, EV_CONNECT_K1)) return -1;
     } else {
         if (c->useVM && !c->gridBuilt) return fail("vcm_trace_camera", "strict mode merges inside the camera pass: call vcm_build_grid first");
-        launch_kind<kWrapLens | kWrapPick | kWrapSobol>(c, [&](auto tag) {
+        launch_kind<kWrapLens | kWrapPick | kWrapSobol | kWrapGgx>(c, [&](auto tag) {
             using S = typename decltype(tag)::type;
             hipLaunchKernelGGL((k_camera_trace<0, S>), dim3(blocks), dim3(VCM_TRACE_BLOCK), 0, c->stream, c->dScene, c->P,
                                c->store, grid_of(c), c->vs, c->dCamOut, c->dCamMask, c->dRngCam, c->dStats, chunk, take_stamps(c, c->stream));
@@ -2006,7 +2025,7 @@ static int vcm_space_merge_impl(vcm_ctx *c, const void *queriesDev, const long l
         if (kind == VCM_MERGE_PAIRS && (int)c->scene->materials.size() > VCM_PAIR_MATERIALS) kind = VCM_MERGE_WALK;
         c->lastMergeKernel = kind;
         const int chunk = shape_knob("merge_chunk") ? shape_knob("merge_chunk") : 16;
-        hipLaunchKernelGGL(merge_kernel(kind, c->intPhong), dim3(blocks), dim3(VCM_MERGE_BLOCK), 0, c->stream, c->dScene, P2, grid_of(c), fvs, (const int *)c->fSorted, (const int *)(c->dQueryStart + nb), c->dStats, chunk, none);
+        hipLaunchKernelGGL(merge_kernel(kind, c->intPhong, c->ggx), dim3(blocks), dim3(VCM_MERGE_BLOCK), 0, c->stream, c->dScene, P2, grid_of(c), fvs, (const int *)c->fSorted, (const int *)(c->dQueryStart + nb), c->dStats, chunk, none);
         HIPCHK(hipGetLastError());
     }
     at = 0;
@@ -2099,7 +2118,7 @@ static int vcm_merge_impl(vcm_ctx *c)
             /* k_merge_pairs keeps a material table of VCM_PAIR_MATERIALS rows in LDS */
             if (mergeStaged == VCM_MERGE_PAIRS && (int)c->scene->materials.size() > VCM_PAIR_MATERIALS) mergeStaged = VCM_MERGE_WALK;
             c->lastMergeKernel = mergeStaged;
-            hipLaunchKernelGGL(merge_kernel(mergeStaged, c->intPhong), dim3(merge_blocks(c->nLocal, c->N)), dim3(VCM_MERGE_BLOCK), 0, ks, c->dScene, c->P, grid_of(c),
+            hipLaunchKernelGGL(merge_kernel(mergeStaged, c->intPhong, c->ggx), dim3(merge_blocks(c->nLocal, c->N)), dim3(VCM_MERGE_BLOCK), 0, ks, c->dScene, c->P, grid_of(c),
                                c->vs, (const int *)c->dSortedVertex, (const int *)(c->dQueryStart + nb), c->dStats, mergeChunk, take_stamps(c, c->stream));
         } else {
             if (mark(c, EV_SORT_K1)) return -1;
@@ -2360,7 +2379,7 @@ int vcm_render_features(vcm_ctx *c)
     if (!c) return fail("vcm_render_features", "ctx is NULL");
     if (ensure_device(c)) return -1;
     if (ensure_feature_buffers(c)) return -1;
-    HIPCHK(dn_launch_features(c->dScene, c->kind, c->resX, c->p0, c->nLocal, c->dGuide, c->dAlbedo, c->stream));
+    HIPCHK(dn_launch_features(c->dScene, c->kind, c->ggx, c->resX, c->p0, c->nLocal, c->dGuide, c->dAlbedo, c->stream));
     c->featuresValid = true;
     return 0;
 }
@@ -3145,7 +3164,7 @@ __global__ void k_numeric_spec(int op, int n, const float *a, const float *b, fl
 template <class SC>
 __global__ void k_kat(const DScene *__restrict__ scp, int op, int n, const float *in, float *out)
 {
-    stage_scene_tables(*scp);   /* before any thread leaves: it holds a barrier */
+    stage_scene_tables(*static_cast<const SC *>(scp));   /* before any thread leaves: it holds a barrier */
     stage_pick_tables(*static_cast<const SC *>(scp));
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
@@ -3205,7 +3224,7 @@ int vcm_debug_kat(vcm_ctx *c, int op, int n, const float *in, float *out)
     if (op == VCM_KAT_SAMPLER)
         hipLaunchKernelGGL(k_kat_sampler, dim3((n + 63) / 64), dim3(64), 0, 0, n, (const float *)din, dout);
     else
-        launch_kind<kWrapLens | kWrapPick>(c, [&](auto tag) {   /* no op of kat_eval draws: the kinds of the scene without its sampler */
+        launch_kind<kWrapLens | kWrapPick | kWrapGgx>(c, [&](auto tag) {   /* no op of kat_eval draws: the kinds of the scene without its sampler */
             using S = typename decltype(tag)::type;
             hipLaunchKernelGGL((k_kat<S>), dim3((n + 63) / 64), dim3(64), 0, 0, (const DScene *)c->dScene, op, n, (const float *)din, dout);
         });
@@ -3248,6 +3267,16 @@ int vcm_debug_sampler(vcm_ctx *c, int *kind)
     if (!c || !kind) return fail("vcm_debug_sampler", "bad argument");
     *kind = c->sobol ? VCM_SAMPLER_SOBOL : VCM_SAMPLER_PHILOX;
     return 0;
+}
+
+int vcm_debug_ggx(vcm_ctx *c, int *nLobes)
+{
+    if (!c) return fail("vcm_debug_ggx", "bad argument");
+    if (nLobes) {
+        *nLobes = 0;
+        for (const vcm_material_ext &x : c->scene->materialExt) *nLobes += ggx_has_lobe(x) ? 1 : 0;
+    }
+    return c->ggx ? 1 : 0;
 }
 
 int vcm_debug_lights_kind(vcm_ctx *c)

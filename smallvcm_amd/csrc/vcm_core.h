@@ -372,6 +372,7 @@ struct DScene {
     static constexpr bool kPick = false;
     static constexpr bool kLights = false;
     static constexpr bool kSobol = false;
+    static constexpr bool kGgx = false;
     int nPrims, nMaterials, nLights, backgroundLight;
     float sceneCenter[3], sceneRadius, invSceneRadiusSqr;
     vcm_camera camera;
@@ -403,7 +404,11 @@ struct DScene {
     float filterRadius;
     /* the sampler (vcm_sampler; VCM_SAMPLER_PHILOX: philox.h's white noise, VCM_SAMPLER_SOBOL: sobol.h) */
     int samplerKind;
+    /* the GGX lobes (vcm_material_ext, one per material; ggxOn == 0: no material has one and the table is absent) */
+    int ggxOn;
+    long long offMaterialExt;
     template <class T> VCM_HD const T *at(long long off) const { return reinterpret_cast<const T *>(reinterpret_cast<const char *>(this) + off); }
+    VCM_HD const vcm_material_ext *materialExt() const { return at<vcm_material_ext>(offMaterialExt); }
     VCM_HD const vcm_prim *prims() const { return at<vcm_prim>(offPrims); }
     VCM_HD const vcm_material *materials() const { return at<vcm_material>(offMaterials); }
     VCM_HD const int *mat2light() const { return at<int>(offMat2light); }
@@ -483,7 +488,7 @@ template <class S> struct WithLens : S { static constexpr bool kLens = true; };
 template <class S> struct WithPick : S { static constexpr bool kPick = true; };
 #if defined(__HIP_DEVICE_COMPILE__)
 #define VCM_PICK_KIND(S) (S::kPick)
-#define VCM_PICK_ON(S, sc) (S::kPick && (!S::kSobol || (sc).pickMode != 0))
+#define VCM_PICK_ON(S, sc) (S::kPick && (!(S::kSobol || S::kGgx) || (sc).pickMode != 0))
 #else
 #define VCM_PICK_KIND(S) true
 #define VCM_PICK_ON(S, sc) ((sc).pickMode != 0)
@@ -511,6 +516,17 @@ template <class S> struct WithSobol : S { static constexpr bool kSobol = true; }
 #define VCM_SOBOL_ON(S, sc) (S::kSobol)
 #else
 #define VCM_SOBOL_ON(S, sc) ((sc).samplerKind == VCM_SAMPLER_SOBOL)
+#endif
+/* kGgx: some material of the scene has a GGX lobe (DScene::ggxOn; vcm_material_ext, DESIGN.md "Microfacet materials").
+   Every kernel that sets up, restores, evaluates or samples a BSDF exists in such a kind, placed as WithSobol is: over
+   the widest chain of the other wrappers the kernel has (scene_kind.h), once under Philox and once under WithSobol;
+   lens, filter and table are run-time branches there (VCM_PICK_ON above looks at kGgx as it looks at kSobol).  The
+   kinds without the wrapper hold no instruction of the lobe.  The host builds take the branch at run time. */
+template <class S> struct WithGgx : S { static constexpr bool kGgx = true; };
+#if defined(__HIP_DEVICE_COMPILE__)
+#define VCM_GGX_ON(S, sc) (S::kGgx)
+#else
+#define VCM_GGX_ON(S, sc) ((sc).ggxOn != 0)
 #endif
 /* tests/host_emul_sampler records where the draw groups start (group 0 = light start, 1 = direct illumination,
    2 = scattering) */
@@ -564,9 +580,22 @@ __shared__ uint32_t g_ldsScene[VCM_LDS_SCENE_WORDS];
 typedef const __attribute__((address_space(3))) uint32_t *LdsWords;
 __device__ __forceinline__ LdsWords lds_scene(int offset) { return (LdsWords)g_ldsScene + offset; }
 #endif
-VCM_HD void stage_scene_tables(const DScene &sc)
+/* the GGX lobes beside them, in the WithGgx kinds alone: a second array, so that the other kernels' LDS stays what it was */
+#define VCM_LDS_EXT_WORDS 4
+#if defined(__HIP_DEVICE_COMPILE__)
+__shared__ uint32_t g_ldsMatExt[VCM_LDS_MATERIALS * VCM_LDS_EXT_WORDS];
+#endif
+template <class S>
+VCM_HD void stage_scene_tables(const S &sc)
 {
 #if defined(__HIP_DEVICE_COMPILE__)
+    if constexpr (S::kGgx) {
+        static_assert(sizeof(vcm_material_ext) == VCM_LDS_EXT_WORDS * 4, "table entries are whole words");
+        if (sc.nMaterials <= VCM_LDS_MATERIALS) {
+            const uint32_t *src = (const uint32_t *)sc.materialExt();
+            for (int i = (int)threadIdx.x; i < sc.nMaterials * VCM_LDS_EXT_WORDS; i += (int)blockDim.x) g_ldsMatExt[i] = src[i];
+        }
+    }
     static_assert(sizeof(vcm_material) == VCM_LDS_MAT_WORDS * 4 && sizeof(vcm_prim) == VCM_LDS_PRIM_WORDS * 4 &&
                   sizeof(vcm_light) == VCM_LDS_LIGHT_WORDS * 4, "table entries are whole words");
     const int t = (int)threadIdx.x, nt = (int)blockDim.x;
@@ -607,6 +636,22 @@ VCM_HD vcm_material scene_material(const DScene &sc, int matID, bool lds = true)
     }
 #endif
     return sc.materials()[matID];
+}
+/* the GGX lobe of a material in a kind that has them (VCM_GGX_ON); as scene_material, global memory above 32 materials */
+template <class S>
+VCM_HD vcm_material_ext scene_material_ext(const S &sc, int matID, bool lds = true)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    if constexpr (S::kGgx) {
+        if (lds && sc.nMaterials <= VCM_LDS_MATERIALS) {   /* wave-uniform */
+            const __attribute__((address_space(3))) uint32_t *p = (const __attribute__((address_space(3))) uint32_t *)g_ldsMatExt + matID * VCM_LDS_EXT_WORDS;
+            vcm_material_ext x;
+            x.ggx[0] = u2f(p[0]); x.ggx[1] = u2f(p[1]); x.ggx[2] = u2f(p[2]); x.alpha = u2f(p[3]);
+            return x;
+        }
+    }
+#endif
+    return sc.materialExt()[matID];
 }
 VCM_HD vcm_prim scene_prim(const DScene &sc, int index)
 {
@@ -1774,7 +1819,7 @@ VCM_HD bool scene_occluded(const SC &sc, V3 point, V3 dir, float tmax)
 }
 
 /* ---- BSDF: bsdf.hxx:61-576 ---------------------------------------- */
-enum { kDiffuse = 1, kPhong = 2, kReflect = 4, kRefract = 8, kSpecular = 12 };
+enum { kDiffuse = 1, kPhong = 2, kReflect = 4, kRefract = 8, kSpecular = 12, kGgx = 16 };
 struct Bsdf {
     int   matID;          /* < 0: invalid (bsdf.hxx:260) */
     Frame frame;
@@ -1783,16 +1828,69 @@ struct Bsdf {
     float diffProb, phongProb, reflProb, refrProb;
     float contProb;
     float reflectCoeff;
+    float ggxProb;        /* the GGX lobe's share; written and read in the kinds with the lobe alone (VCM_GGX_ON) */
 };
 
-VCM_HD void bsdf_component_probabilities(Bsdf &b, const vcm_material &m)
+/* ---- the GGX lobe (vcm_material_ext; not in the reference).  o = mLocalDirFix, i = the generated direction, both in
+ * the local frame, h = normalize(o + i).  D = a2 / (pi d^2) with d = a2 h_z^2 + (h_x^2 + h_y^2) (no cancellation at
+ * small alpha), Lambda(w) = (-1 + sqrt(1 + a2 (w_x^2 + w_y^2) / w_z^2)) / 2, G2 = 1 / (1 + Lambda(o) + Lambda(i)),
+ * G1(w) = 1 / (1 + Lambda(w)), Schlick's F over F0; f = F D G2 / (4 o_z i_z), pdf = G1(o) D / (4 o_z), reverse pdf =
+ * G1(i) D / (4 i_z).  Only + - * / sqrt: the host emulation computes the same bits. */
+VCM_HD bool ggx_has_lobe(const vcm_material_ext &x) { return x.ggx[0] != 0.f || x.ggx[1] != 0.f || x.ggx[2] != 0.f; }
+VCM_HD float ggx_lambda(V3 w, float a2) { return (-1.f + sqrtf(1.f + a2 * (w.x * w.x + w.y * w.y) / (w.z * w.z))) * 0.5f; }
+VCM_HD V3 ggx_fresnel(V3 f0, float c)
+{
+    const float t = 1.f - smin(1.f, smax(0.f, c));
+    const float t2 = t * t;
+    return f0 + (sp3(1.f) - f0) * (t2 * t2 * t);
+}
+/* value and pdfs of the lobe for o.z, i.z >= EPS_COSINE, from what depends on o alone (a2, Lambda(o): the merge stages
+   them once per query) and i; `prob` is mGgxProb */
+VCM_HD V3 ggx_eval_core(V3 o, V3 i, V3 f0, float a2, float lambdaO, float prob, float *dirPdf, float *revPdf)
+{
+    const V3 h = normalize(o + i);
+    const float d = a2 * (h.z * h.z) + (h.x * h.x + h.y * h.y);
+    const float D = a2 / (VCM_PI_F * (d * d));
+    const float lambdaI = ggx_lambda(i, a2);
+    if (dirPdf) *dirPdf += prob * (D / ((1.f + lambdaO) * (4.f * o.z)));
+    if (revPdf) *revPdf += prob * (D / ((1.f + lambdaI) * (4.f * i.z)));
+    return ggx_fresnel(f0, dot(o, h)) * (D / ((1.f + lambdaO + lambdaI) * (4.f * o.z * i.z)));
+}
+VCM_HD V3 bsdf_eval_ggx(const Bsdf &b, const vcm_material_ext &x, V3 gen, float *dirPdf, float *revPdf)
+{
+    if (b.ggxProb == 0.f) return sp3(0.f);
+    if (b.localDirFix.z < VCM_EPS_COSINE || gen.z < VCM_EPS_COSINE) return sp3(0.f);
+    const float a2 = x.alpha * x.alpha;
+    return ggx_eval_core(b.localDirFix, gen, ld3(x.ggx), a2, ggx_lambda(b.localDirFix, a2), b.ggxProb, dirPdf, revPdf);
+}
+/* a visible normal by the spherical cap (Dupuy & Benyoub 2023), reflected: the direction, not yet checked against EPS_COSINE */
+VCM_HD V3 ggx_sample_dir(V3 o, float alpha, float sinPhi, float cosPhi, float r1)
+{
+    const V3 s = normalize(mk3(alpha * o.x, alpha * o.y, o.z));
+    const float z = (1.f - r1) * (1.f + s.z) - s.z;
+    const float sinTheta = sqrtf(smin(1.f, smax(0.f, 1.f - z * z)));
+    const V3 m = mk3(sinTheta * cosPhi, sinTheta * sinPhi, z) + s;
+    const V3 h = normalize(mk3(alpha * m.x, alpha * m.y, smax(m.z, 0.f)));
+    return (2.f * dot(o, h)) * h - o;
+}
+
+/* ggx: the kind has the lobes (VCM_GGX_ON) and x is the material's; otherwise x is not looked at */
+VCM_HD void bsdf_component_probabilities(Bsdf &b, const vcm_material &m, bool ggx, const vcm_material_ext &x)
 {   /* GetComponentProbabilities :528-566 */
     b.reflectCoeff = fresnel_dielectric(b.localDirFix.z, m.ior);
     const float albedoDiffuse = luminance(ld3(m.diffuse));
     const float albedoPhong   = luminance(ld3(m.phong));
     const float albedoReflect = b.reflectCoeff * luminance(ld3(m.mirror));
     const float albedoRefract = (1.f - b.reflectCoeff) * (m.ior > 0.f ? 1.f : 0.f);
-    const float totalAlbedo = albedoDiffuse + albedoPhong + albedoReflect + albedoRefract;
+    float totalAlbedo = albedoDiffuse + albedoPhong + albedoReflect + albedoRefract;
+    V3 fresnelGgx = sp3(0.f);
+    float albedoGgx = 0.f;
+    b.ggxProb = 0.f;
+    if (ggx && ggx_has_lobe(x)) {
+        fresnelGgx = ggx_fresnel(ld3(x.ggx), b.localDirFix.z);
+        albedoGgx = luminance(fresnelGgx);
+        totalAlbedo = totalAlbedo + albedoGgx;
+    }
     if (totalAlbedo < 1e-9f) {
         b.diffProb = b.phongProb = b.reflProb = b.refrProb = 0.f;
         b.contProb = 0.f;
@@ -1801,33 +1899,47 @@ VCM_HD void bsdf_component_probabilities(Bsdf &b, const vcm_material &m)
         b.phongProb = albedoPhong / totalAlbedo;
         b.reflProb  = albedoReflect / totalAlbedo;
         b.refrProb  = albedoRefract / totalAlbedo;
-        b.contProb = vmax3(ld3(m.diffuse) + ld3(m.phong) + b.reflectCoeff * ld3(m.mirror)) +
+        V3 survive = ld3(m.diffuse) + ld3(m.phong) + b.reflectCoeff * ld3(m.mirror);
+        if (ggx) { b.ggxProb = albedoGgx / totalAlbedo; survive = survive + fresnelGgx; }
+        b.contProb = vmax3(survive) +
                      (1.f - b.reflectCoeff);
         b.contProb = smin(1.f, smax(0.f, b.contProb));
     }
 }
+template <class S>
+VCM_HD void bsdf_component_probabilities(Bsdf &b, const S &sc, int matID, bool ldsMaterials)
+{
+    const vcm_material m = scene_material(sc, matID, ldsMaterials);
+    vcm_material_ext x = { { 0.f, 0.f, 0.f }, 0.f };
+    const bool ggx = VCM_GGX_ON(S, sc);
+    if (ggx) x = scene_material_ext(sc, matID, ldsMaterials);
+    bsdf_component_probabilities(b, m, ggx, x);
+}
 /* Setup :95-117.  rayDir = the incoming ray direction, normal = isect.normal, prim = isect.prim */
-VCM_HD void bsdf_setup(Bsdf &b, V3 rayDir, V3 normal, int matID, int prim, const DScene &sc)
+template <class S>
+VCM_HD void bsdf_setup(Bsdf &b, V3 rayDir, V3 normal, int matID, int prim, const S &sc)
 {
     (void)prim;
     b.matID = -1;
     frame_from_z(b.frame, normal);
     b.localDirFix = to_local(b.frame, -rayDir);
     if (fabsf(b.localDirFix.z) < VCM_EPS_COSINE) return;
-    bsdf_component_probabilities(b, scene_material(sc, matID));
+    bsdf_component_probabilities(b, sc, matID, true);
     b.isDelta = (b.diffProb == 0.f) && (b.phongProb == 0.f);
+    if (VCM_GGX_ON(S, sc)) b.isDelta = b.isDelta && (b.ggxProb == 0.f);
     b.matID = matID;
 }
 /* What a stored vertex keeps of its surface, in the upper 24 bits of the word that holds its path length: matID */
 VCM_HD uint32_t shade_code(int matID, int /*prim*/) { return (uint32_t)matID & 0xffffffu; }
 /* Rebuild the BSDF of a STORED vertex from (isect.normal, mLocalDirFix, matID): the same operations Setup ran,
  * hence the same bits. */
-VCM_HD void bsdf_restore(Bsdf &b, V3 normal, V3 localDirFix, uint32_t code, const DScene &sc, bool ldsMaterials = true)
+template <class S>
+VCM_HD void bsdf_restore(Bsdf &b, V3 normal, V3 localDirFix, uint32_t code, const S &sc, bool ldsMaterials = true)
 {
     const int matID = (int)(code & 0xffffffu);
     frame_from_z(b.frame, normal);
     b.localDirFix = localDirFix;
-    bsdf_component_probabilities(b, scene_material(sc, matID, ldsMaterials));
+    bsdf_component_probabilities(b, sc, matID, ldsMaterials);
     b.isDelta = false;
     b.matID = matID;
 }
@@ -1887,6 +1999,7 @@ VCM_HD V3 bsdf_evaluate(const Bsdf &b, const S &sc, V3 worldDirGen, float &cosTh
     const vcm_material m = scene_material(sc, b.matID);
     result = result + bsdf_eval_diffuse(b, m, gen, dirPdf, revPdf);
     result = result + bsdf_eval_phong(b, m, gen, dirPdf, revPdf, S::kIntPhong);
+    if (VCM_GGX_ON(S, sc)) result = result + bsdf_eval_ggx(b, scene_material_ext(sc, b.matID), gen, dirPdf, revPdf);
     return result;
 }
 template <class S>
@@ -1898,6 +2011,7 @@ VCM_HD float bsdf_pdf(const Bsdf &b, const S &sc, V3 worldDirGen, bool evalRev)
     float directPdfW = 0.f, reversePdfW = 0.f;
     bsdf_pdf_diffuse(b, gen, &directPdfW, &reversePdfW);
     bsdf_pdf_phong(b, m, gen, &directPdfW, &reversePdfW, S::kIntPhong);
+    if (VCM_GGX_ON(S, sc)) (void)bsdf_eval_ggx(b, scene_material_ext(sc, b.matID), gen, &directPdfW, &reversePdfW);
     return evalRev ? reversePdfW : directPdfW;
 }
 /* Sample :191-257 with SampleDiffuse :274, SamplePhong :290, SampleReflect :320,
@@ -1906,17 +2020,21 @@ template <class S>
 VCM_HD V3 bsdf_sample(const Bsdf &b, const S &sc, bool fixIsLight, float r0, float r1, float r2,
                       V3 &worldDirGen, float &pdfW, float &cosThetaGen, uint32_t &sampledEvent)
 {
+    const bool ggx = VCM_GGX_ON(S, sc);   /* the cumulative order: diffuse, phong, ggx, reflect, refract */
     if (r2 < b.diffProb) sampledEvent = kDiffuse;
     else if (r2 < b.diffProb + b.phongProb) sampledEvent = kPhong;
-    else if (r2 < b.diffProb + b.phongProb + b.reflProb) sampledEvent = kReflect;
+    else if (ggx && r2 < b.diffProb + b.phongProb + b.ggxProb) sampledEvent = kGgx;
+    else if (r2 < (ggx ? b.diffProb + b.phongProb + b.ggxProb + b.reflProb : b.diffProb + b.phongProb + b.reflProb)) sampledEvent = kReflect;
     else sampledEvent = kRefract;
 
     const vcm_material m = scene_material(sc, b.matID);
+    vcm_material_ext mx = { { 0.f, 0.f, 0.f }, 0.f };
+    if (ggx) mx = scene_material_ext(sc, b.matID);
     pdfW = 0.f;
     V3 result = sp3(0.f);
     V3 gen = sp3(0.f);
-    float sinPhi = 0.f, cosPhi = 0.f;   /* of term1 = 2 pi r0 (utils.hxx:91, :177), for the two branches that sample a lobe */
-    if (sampledEvent == kDiffuse || sampledEvent == kPhong) dm_sincosf(2.f * VCM_PI_F * r0, sinPhi, cosPhi);
+    float sinPhi = 0.f, cosPhi = 0.f;   /* of term1 = 2 pi r0 (utils.hxx:91, :177), for the branches that sample a lobe */
+    if (sampledEvent == kDiffuse || sampledEvent == kPhong || (ggx && sampledEvent == kGgx)) dm_sincosf(2.f * VCM_PI_F * r0, sinPhi, cosPhi);
     RC_MARK(32);
 
     if (sampledEvent == kDiffuse) {
@@ -1927,7 +2045,16 @@ VCM_HD V3 bsdf_sample(const Bsdf &b, const S &sc, bool fixIsLight, float r0, flo
         result = result + ld3(m.diffuse) * VCM_INV_PI_F;
         if (iszero(result)) return sp3(0.f);
         result = result + bsdf_eval_phong(b, m, gen, &pdfW, (float *)0, S::kIntPhong);
+        if (ggx) result = result + bsdf_eval_ggx(b, mx, gen, &pdfW, (float *)0);
         RC_MARK(33);
+    } else if (ggx && sampledEvent == kGgx) {
+        if (b.localDirFix.z < VCM_EPS_COSINE) return sp3(0.f);
+        gen = ggx_sample_dir(b.localDirFix, mx.alpha, sinPhi, cosPhi, r1);
+        if (gen.z < VCM_EPS_COSINE) return sp3(0.f);
+        result = result + bsdf_eval_ggx(b, mx, gen, &pdfW, (float *)0);
+        if (iszero(result)) return sp3(0.f);
+        result = result + bsdf_eval_diffuse(b, m, gen, &pdfW, (float *)0);
+        result = result + bsdf_eval_phong(b, m, gen, &pdfW, (float *)0, S::kIntPhong);
     } else if (sampledEvent == kPhong) {
         gen = sample_power_cos_hemisphere(sinPhi, cosPhi, r1, m.phongExp);
         const V3 refl = reflect_local(b.localDirFix);
@@ -1946,6 +2073,7 @@ VCM_HD V3 bsdf_sample(const Bsdf &b, const S &sc, bool fixIsLight, float r0, flo
         result = result + rho * pw;
         if (iszero(result)) return sp3(0.f);
         result = result + bsdf_eval_diffuse(b, m, gen, &pdfW, (float *)0);
+        if (ggx) result = result + bsdf_eval_ggx(b, mx, gen, &pdfW, (float *)0);
         RC_MARK(34);
     } else if (sampledEvent == kReflect) {
         gen = reflect_local(b.localDirFix);
@@ -2717,7 +2845,8 @@ VCM_HD bool light_path_step(const SC &sc, const IterParams &P, LightPath &lp, co
  * BSDF, vertexcm.hxx:140, :161), rebuilt from the record: Setup's frame from the stored normal, ToWorld of the stored
  * mLocalDirFix, GetComponentProbabilities of the stored material -- the operations the light pass ran, on the same values,
  * hence the same bits. */
-VCM_HD F4 light_vertex_wdir_contprob(const DScene &sc, F4 field0, F4 field2, F4 field3, bool ldsMaterials)
+template <class S>
+VCM_HD F4 light_vertex_wdir_contprob(const S &sc, F4 field0, F4 field2, F4 field3, bool ldsMaterials)
 {
     Bsdf b;
     bsdf_restore(b, mk3(field2.x, field2.y, field2.z), mk3(field3.x, field3.y, field3.z), f2u(field0.w) >> 8, sc, ldsMaterials);
@@ -2887,11 +3016,30 @@ struct MergeEval {
     float camdVM;
     uint32_t pathLength;
     bool cosOk;           /* !(mLocalDirFix.z < EPS_COSINE) */
+    /* the GGX lobe, in the forms with it alone: mLocalDirFix, F0, alpha^2, Lambda(mLocalDirFix), mGgxProb -- what
+       bsdf_eval_ggx derives from the query before it calls ggx_eval_core */
+    V3 ldf, ggxF0;
+    float ggxA2, ggxLambdaFix, ggxProb;
 };
-VCM_HD void merge_eval_setup(MergeEval &e, const DScene &sc, const IterParams &P, const Bsdf &b,
+/* the merge forms with the lobe: a template argument on the device, the query's own ggxProb on the host */
+#if defined(__HIP_DEVICE_COMPILE__)
+#define VCM_MERGE_GGX(GGX, e) (GGX)
+#else
+#define VCM_MERGE_GGX(GGX, e) true
+#endif
+template <class S>
+VCM_HD void merge_eval_setup(MergeEval &e, const S &sc, const IterParams &P, const Bsdf &b,
                              const SubPathState &st, bool ldsMaterials = true)
 {
     const vcm_material m = scene_material(sc, b.matID, ldsMaterials);
+    e.ggxProb = 0.f;
+    if (VCM_GGX_ON(S, sc)) {
+        const vcm_material_ext x = scene_material_ext(sc, b.matID, ldsMaterials);
+        e.ldf = b.localDirFix; e.ggxF0 = ld3(x.ggx);
+        e.ggxA2 = x.alpha * x.alpha;
+        e.ggxLambdaFix = ggx_lambda(b.localDirFix, e.ggxA2);
+        e.ggxProb = b.ggxProb;
+    }
     e.frame = b.frame;
     e.refl = reflect_local(b.localDirFix);
     e.diffuseVal = ld3(m.diffuse) * VCM_INV_PI_F;
@@ -2905,7 +3053,7 @@ VCM_HD void merge_eval_setup(MergeEval &e, const DScene &sc, const IterParams &P
     e.pathLength = st.pathLength;
     e.cosOk = !(b.localDirFix.z < VCM_EPS_COSINE);
 }
-template <bool IP /* the scene's Phong exponents are integers (DScene::kIntPhong) */>
+template <bool IP /* the scene's Phong exponents are integers (DScene::kIntPhong) */, bool GGX = false /* the kind has GGX lobes */>
 VCM_HD void merge_eval_photon(const MergeEval &e, const IterParams &P, uint32_t lvLen, V3 lightDirection,
                               float lvContProb, V3 lvThroughput, float lvdVCM, float lvdVM, V3 &contrib)
 {
@@ -2932,6 +3080,8 @@ VCM_HD void merge_eval_photon(const MergeEval &e, const IterParams &P, uint32_t 
         ph = e.rho * pw;
     }
     result = result + ph;
+    if (VCM_MERGE_GGX(GGX, e) && valid && ok && (e.ggxProb != 0.f))   /* bsdf_eval_ggx */
+        result = result + ggx_eval_core(e.ldf, gen, e.ggxF0, e.ggxA2, e.ggxLambdaFix, e.ggxProb, &dirPdf, &revPdf);
     if (valid && !iszero(result)) {                                                     /* :145-146 */
         dirPdf *= e.camContProb;                                                        /* :148 */
         revPdf *= lvContProb;                                                           /* :153 */
@@ -2953,7 +3103,7 @@ VCM_HD void merge_photon_load(const GridStore &g, const MergeScratch &ms, int k,
     p.c = g.g2[idx];
     p.dVM = t.x;
 }
-template <bool IP>
+template <bool IP, bool GGX = false>
 VCM_HD void merge_drain(const IterParams &P, const GridStore &g, const MergeEval &e, const MergeScratch &ms, int qn,
                         V3 &contrib)
 {
@@ -2967,13 +3117,13 @@ VCM_HD void merge_drain(const IterParams &P, const GridStore &g, const MergeEval
         const bool more1 = wave_any(k + 1 < qn);
         if (more1) merge_photon_load(g, ms, k + 1, qn, pb);
         if (k < qn)
-            merge_eval_photon<IP>(e, P, f2u(pa.lenBits), mk3(pa.b.x, pa.b.y, pa.b.z), pa.b.w,
+            merge_eval_photon<IP, GGX>(e, P, f2u(pa.lenBits), mk3(pa.b.x, pa.b.y, pa.b.z), pa.b.w,
                                   mk3(pa.c.x, pa.c.y, pa.c.z), pa.c.w, pa.dVM, contrib);
         if (!more1) break;
         const bool more2 = wave_any(k + 2 < qn);
         if (more2) merge_photon_load(g, ms, k + 2, qn, pa);
         if (k + 1 < qn)
-            merge_eval_photon<IP>(e, P, f2u(pb.lenBits), mk3(pb.b.x, pb.b.y, pb.b.z), pb.b.w,
+            merge_eval_photon<IP, GGX>(e, P, f2u(pb.lenBits), mk3(pb.b.x, pb.b.y, pb.b.z), pb.b.w,
                                   mk3(pb.c.x, pb.c.y, pb.c.z), pb.c.w, pb.dVM, contrib);
         if (!more2) break;
     }
@@ -2992,8 +3142,8 @@ VCM_HD void merge_drain(const IterParams &P, const GridStore &g, const MergeEval
  * lanes active instead of the ~18 % that accept at any one candidate.  Each
  * lane still processes ITS photons in the reference's order, so the sum
  * (:168) is bit-identical. */
-template <bool IP>
-VCM_HD V3 merge_query(const DScene &sc, const IterParams &P, const GridStore &g, const Bsdf &cameraBsdf,
+template <bool IP, class S>
+VCM_HD V3 merge_query(const S &sc, const IterParams &P, const GridStore &g, const Bsdf &cameraBsdf,
                       const SubPathState &st, V3 queryPos, LaneStats &ls, const MergeScratch &ms, bool ldsMaterials = true)
 {
     V3 contrib = sp3(0.f);
@@ -3071,13 +3221,13 @@ VCM_HD V3 merge_query(const DScene &sc, const IterParams &P, const GridStore &g,
             lo = nextLo;
             if (wave_any(qn > ms.cap - VCM_MERGE_UNROLL)) {
                 ls.mergeAccepted += (uint32_t)qn;
-                merge_drain<IP>(P, g, ev, ms, qn, contrib);
+                merge_drain<IP, S::kGgx>(P, g, ev, ms, qn, contrib);
                 qn = 0;
             }
         }
     }
     ls.mergeAccepted += (uint32_t)qn;
-    merge_drain<IP>(P, g, ev, ms, qn, contrib);
+    merge_drain<IP, S::kGgx>(P, g, ev, ms, qn, contrib);
     return contrib;
 }
 
@@ -3523,7 +3673,8 @@ struct CamVertex {
     uint32_t lp;
     uint32_t diK;         /* position of DirectIllumination's 3 floats in the path's random stream */
 };
-VCM_HD void load_cam_vertex(const DScene &sc, const VertexStore &vs, int vi, CamVertex &v)
+template <class S>
+VCM_HD void load_cam_vertex(const S &sc, const VertexStore &vs, int vi, CamVertex &v)
 {
     const F4 a = vq(vs, 0, vi), b = vq(vs, 1, vi), c = vq(vs, 2, vi), d = vq(vs, 3, vi), e = vq(vs, 4, vi);
     v.hit = mk3(a.x, a.y, a.z);
@@ -3564,8 +3715,8 @@ VCM_HD V3 eval_vc_task(const SC &sc, const IterParams &P, const VertexStore &vs,
            connect_vertices(sc, P, mk3(a.x, a.y, a.z), lvBsdf, b.w, c.w, v.bsdf, v.hit, v.st, ls);
 }
 /* the addend of :534  (color += throughput * mVmNormalization * query.GetContrib()) */
-template <bool IP>
-VCM_HD V3 eval_merge_task(const DScene &sc, const IterParams &P, const VertexStore &vs, const GridStore &g,
+template <bool IP, class S>
+VCM_HD V3 eval_merge_task(const S &sc, const IterParams &P, const VertexStore &vs, const GridStore &g,
                           int vi, LaneStats &ls, const MergeScratch &ms, size_t &pathSlot, bool ldsMaterials = true)
 {
     const F4 a = vq(vs, 0, vi), b = vq(vs, 1, vi), c = vq(vs, 2, vi), d = vq(vs, 3, vi);

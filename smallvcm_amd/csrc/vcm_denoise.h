@@ -46,7 +46,8 @@ VCM_HD void feature_pixel(const SC &sc, int resX, int pixel, F4 &guide, F4 &albe
     if (isect.lightID >= 0) return;   /* an emitter */
     const vcm_material m = scene_material(sc, isect.matID);
     if (m.ior > 0.f) return;          /* refracts: what is seen lies behind it */
-    const V3 a = ld3(m.diffuse) + ld3(m.phong) + ld3(m.mirror);
+    V3 a = ld3(m.diffuse) + ld3(m.phong) + ld3(m.mirror);
+    if (VCM_GGX_ON(SC, sc)) a = a + ld3(scene_material_ext(sc, isect.matID).ggx);   /* the lobe's F0 */
     albedo = mk4(dn_albedo_component(a.x), dn_albedo_component(a.y), dn_albedo_component(a.z), 1.f);
 }
 
@@ -306,7 +307,7 @@ VCM_HD F4 dn_filter_pixel2(const DnPass2 &P2, int x, int y, F4 albedoP, Load &&l
 /* ---------------- launches (vcm_denoise.hip; the C-ABI of vcm_api.hip calls them) ---------------- */
 #if defined(__HIPCC__)
 /* guide / albedo of the pixels [p0, p0 + nLocal), by the k_features of the context's kind */
-hipError_t dn_launch_features(const DScene *dScene, SceneKind kind, int resX, int p0, int nLocal, F4 *guide, F4 *albedo,
+hipError_t dn_launch_features(const DScene *dScene, SceneKind kind, bool ggx, int resX, int p0, int nLocal, F4 *guide, F4 *albedo,
                               hipStream_t stream);
 /* out = the filtered colour.  fb3 != NULL: the colour is a W*H*3 float image times `scale`, else the float4 image
    `color`.  tmpA, tmpB: two W*H float4 images of scratch (unused when passes == 0).  Parameters already checked. */

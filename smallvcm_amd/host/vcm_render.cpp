@@ -380,8 +380,25 @@ int main(int argc, char **argv)
         samplerDesc.sampler = sampler;
         samplerScene = &samplerDesc;
     }
+    // the GGX lobes of a scene file's `Pr` materials: the scene as a version-8 description over whatever the flags made of it
+    const vcm_material_ext *materialExt = loaded ? vcm_scene_file_desc8(loaded)->materialExt : NULL;
+    vcm_scene_desc8 ggxDesc;
+    const vcm_scene_desc8 *ggxScene = NULL;
+    if (materialExt && gpus <= 0) {
+        memset(&ggxDesc, 0, sizeof(ggxDesc));
+        if (samplerScene) ggxDesc.base = *samplerScene;
+        else if (filterScene) ggxDesc.base.base = *filterScene;
+        else if (pickScene) ggxDesc.base.base.base = *pickScene;
+        else if (lensScene) ggxDesc.base.base.base.base = *lensScene;
+        else if (envScene) ggxDesc.base.base.base.base.base = *envScene;
+        else ggxDesc.base.base.base.base.base = *vcm_scene_file_desc3(loaded);
+        ggxDesc.materialExt = materialExt;
+        ggxScene = &ggxDesc;
+    }
+    if (materialExt && gpus > 0) { fprintf(stderr, "vcm_render: a scene file with Pr materials cannot be rendered with --gpus yet\n"); return 1; }
     auto create = [&](int s) {
-        return samplerScene ? vcm_create_sharded7(samplerScene, algorithm, radiusFactor, radiusAlpha, s, device, 0, 1)
+        return ggxScene ? vcm_create_sharded8(ggxScene, algorithm, radiusFactor, radiusAlpha, s, device, 0, 1)
+             : samplerScene ? vcm_create_sharded7(samplerScene, algorithm, radiusFactor, radiusAlpha, s, device, 0, 1)
              : filterScene ? vcm_create_sharded6(filterScene, algorithm, radiusFactor, radiusAlpha, s, device, 0, 1)
              : pickScene ? vcm_create_sharded5(pickScene, algorithm, radiusFactor, radiusAlpha, s, device, 0, 1)
              : lensScene ? vcm_create_sharded4(lensScene, algorithm, radiusFactor, radiusAlpha, s, device, 0, 1)

@@ -16,7 +16,7 @@ import math
 import numpy as np
 
 from ._abi import (Camera, EnvMap, Light, LightPick, Material, Prim, SceneDesc2, SceneDesc3, SceneDesc4, SceneDesc5, SceneDesc6, ThinLens,
-                   PixelFilter, SAMPLERS, with_sampler, FILTER_BOX, FILTER_MAX_RADIUS, LIGHT_PICK_CUSTOM, LIGHT_PICK_MODES, PIXEL_FILTERS)
+                   PixelFilter, SAMPLERS, with_sampler, with_material_ext, FILTER_BOX, FILTER_MAX_RADIUS, LIGHT_PICK_CUSTOM, LIGHT_PICK_MODES, PIXEL_FILTERS)
 
 
 def _f3(v):
@@ -59,9 +59,13 @@ class SceneBuilder:
         self.pick = None
         self.filter = None
         self.sampler_kind = None
+        self.material_ext = []
 
     # ---- materials (materials.hxx:33-65) ----
-    def material(self, diffuse=(0, 0, 0), phong=(0, 0, 0), exponent=1.0, mirror=(0, 0, 0), ior=-1.0):
+    def material(self, diffuse=(0, 0, 0), phong=(0, 0, 0), exponent=1.0, mirror=(0, 0, 0), ior=-1.0, ggx=(0, 0, 0), alpha=1.0):
+        """ggx, alpha: the optional GGX lobe (include/smallvcm_amd.h vcm_material_ext) -- F0 per channel in [0, 1] and
+        the width in [0.01, 1].  build() returns a SceneDesc8 when any material has one."""
+        self.material_ext.append(tuple(float(x) for x in ggx) + (float(alpha),))
         m = Material()
         self.L.vcm_make_material(C.byref(m))
         m.diffuse[:] = [float(x) for x in diffuse]
@@ -206,7 +210,11 @@ class SceneBuilder:
     # ---- the description ----
     def build(self, position, forward, up, fov_deg, resx, resy):
         d = self._build6(position, forward, up, fov_deg, resx, resy)
-        return d if self.sampler_kind is None else with_sampler(d, self.sampler_kind)
+        if self.sampler_kind is not None:
+            d = with_sampler(d, self.sampler_kind)
+        if any(e[0] != 0.0 or e[1] != 0.0 or e[2] != 0.0 for e in self.material_ext):
+            d = with_material_ext(d, self.material_ext)
+        return d
 
     def _build6(self, position, forward, up, fov_deg, resx, resy):
         d = SceneDesc2()
