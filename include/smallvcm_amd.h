@@ -268,6 +268,36 @@ typedef struct vcm_scene_desc8 {
     const vcm_material_ext *materialExt;
 } vcm_scene_desc8;
 
+/* The camera's projection.  PERSPECTIVE (the default): the reference's pinhole behind a planar image, as described by
+ * vcm_camera's matrices.  The two angular projections read only camera.position, camera.forward, camera.resolution
+ * (W, H) and the raster axes the matrices imply: with f = forward, ex = the raster +x direction made orthogonal to f
+ * and ey = +-(f x ex), the sign that points along raster +y (all three derived in binary64), a raster point (x, y) in
+ * pixels looks along
+ *   FISHEYE (equidistant; fovDegrees in (0, 360), measured across the image WIDTH): k = W / fov[rad] pixels per radian,
+ *     q = (x - W/2, y - H/2), rho = |q|, theta = rho / k, dir = sin(theta) (q / rho . (ex, ey)) + cos(theta) f.  A
+ *     sample with theta > fov / 2 lies outside the image circle and contributes exactly 0.
+ *   PANORAMA (equirectangular, 360 x 180 degrees, no parameter, any W and H): lambda = 2 pi (x / W - 1/2), the azimuth
+ *     from f towards ex, theta = pi y / H, the polar angle from -ey (row 0 is up):
+ *     dir = sin(theta) (cos(lambda) f + sin(lambda) ex) - cos(theta) ey.
+ * Densities are per raster area, so non-square images are correct.  A thin lens combines with PERSPECTIVE only; a
+ * pixel filter combines with all three.  DESIGN.md "Camera projections". */
+enum {
+    VCM_PROJ_PERSPECTIVE = 0,
+    VCM_PROJ_FISHEYE = 1,
+    VCM_PROJ_PANORAMA = 2
+};
+typedef struct vcm_camera_model {
+    int   kind;
+    float fovDegrees;   /* FISHEYE only */
+} vcm_camera_model;
+
+/* Scene description, version 9: a version-8 scene and its camera model (copied).  `model` NULL, or kind PERSPECTIVE,
+ * renders exactly what vcm_create8 renders, with the kernels it launches. */
+typedef struct vcm_scene_desc9 {
+    vcm_scene_desc8         base;
+    const vcm_camera_model *model;
+} vcm_scene_desc9;
+
 /* VertexCM::AlgorithmType (src/vertexcm.hxx:182-204) -- same values */
 enum {
     VCM_ALGO_LIGHT_TRACE = 0,
@@ -394,6 +424,15 @@ vcm_ctx *vcm_create_sharded7(const vcm_scene_desc7 *scene, int algorithm,
 vcm_ctx *vcm_create8(const vcm_scene_desc8 *scene, int algorithm,
                      float radiusFactor, float radiusAlpha, int seed);
 vcm_ctx *vcm_create_sharded8(const vcm_scene_desc8 *scene, int algorithm,
+                             float radiusFactor, float radiusAlpha, int seed,
+                             int device, int rank, int worldSize);
+
+/* The same for a version-9 scene description (camera projection).  NULL with vcm_last_error() for an unknown kind, a
+ * FISHEYE fovDegrees that is not finite or not in (0, 360), a thin lens together with a projection other than
+ * PERSPECTIVE, or a bad version-8 scene; checked before a device is looked for. */
+vcm_ctx *vcm_create9(const vcm_scene_desc9 *scene, int algorithm,
+                     float radiusFactor, float radiusAlpha, int seed);
+vcm_ctx *vcm_create_sharded9(const vcm_scene_desc9 *scene, int algorithm,
                              float radiusFactor, float radiusAlpha, int seed,
                              int device, int rank, int worldSize);
 
@@ -644,6 +683,9 @@ const vcm_scene_desc7 *vcm_scene_file_desc7(const vcm_scene_file *scene);
  * use has a `Pr` line in its .mtl (Ks is then the F0 of a GGX lobe of alpha = max(Pr^2, 0.01)), NULL otherwise.  Points
  * into the handle, like vcm_scene_file_desc. */
 const vcm_scene_desc8 *vcm_scene_file_desc8(const vcm_scene_file *scene);
+/* The same scene as a version-9 description: its base is vcm_scene_file_desc8's, its model that of the file's
+ * `projection fisheye <fovDeg>|panorama` directive, NULL without one.  Points into the handle, like vcm_scene_file_desc. */
+const vcm_scene_desc9 *vcm_scene_file_desc9(const vcm_scene_file *scene);
 
 /* Environment maps from files: Radiance RGBE (.hdr: "#?RADIANCE" / "#?RGBE", FORMAT=32-bit_rle_rgbe, "-Y H +X W", flat
  * or new-style run-length scanlines) or PFM (.pfm: "PF", either byte order; its bottom-up rows are flipped), picked by

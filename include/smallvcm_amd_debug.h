@@ -76,7 +76,11 @@ enum {
                                      stream and index, out[1] = the bit pattern of its 32-bit word.  The op names the
                                      sampler's function (csrc/sobol.h sobol_word), not the context's mode: any context answers
                                                                                                   DESIGN.md "Sampler" */
-    VCM_KAT_OPS = 13
+    VCM_KAT_PROJECTION = 13,      /* in: raster x, y, world point -> ray dir, cameraPdfW, valid (0: outside the fisheye's image circle
+                                     or the panorama's rows), then the raster x, y of the world point, valid (1: inside the
+                                     field of view and the image) and the cameraPdfW of that direction; needs a context with a
+                                     fisheye or panorama projection (vcm_create9)              DESIGN.md "Camera projections" */
+    VCM_KAT_OPS = 14
 };
 int vcm_debug_kat(vcm_ctx *ctx, int op, int n, const float *in, float *out);
 
@@ -109,6 +113,14 @@ int vcm_debug_sampler(vcm_ctx *ctx, int *kind);
 /* Whether a context launches the WithGgx kinds (1: some material has a GGX lobe; 0: it launches exactly the kernels of
  * vcm_create7), and in *nLobes, if not NULL, how many materials have one. */
 int vcm_debug_ggx(vcm_ctx *ctx, int *nLobes);
+
+/* The projection of a context as its kernels see it (vcm_camera_model): *kind = VCM_PROJ_*, *fovDegrees = the fisheye's
+ * field of view (0 otherwise); either pointer may be NULL.  Returns 1 when the context launches the WithLens kinds
+ * because of its projection, 0 for PERSPECTIVE: it then launches exactly the kernels of vcm_create8.  (This is the
+ * VCM_INFO_PROJECTION read-back; it is a function of its own because callers size vcm_debug_context_info's array by the
+ * VCM_INFO_COUNT they were built with.) */
+#define VCM_INFO_PROJECTION(ctx, kind, fov) vcm_debug_projection((ctx), (kind), (fov))
+int vcm_debug_projection(vcm_ctx *ctx, int *kind, float *fovDegrees);
 
 /* The rule that picks a context's kind from the five facts about its scene (csrc/scene_kind.h, scene_kind_of), for a
  * test of the rule itself: 0 SceneList, 1 SceneQuads, 2 SceneRects, 3 SceneBvh, 4 SceneBvhG, 5 SceneRectsE, 6 SceneListE,

@@ -235,6 +235,47 @@ def with_material_ext(desc, ext):
     return d8
 
 
+PROJ_PERSPECTIVE, PROJ_FISHEYE, PROJ_PANORAMA = 0, 1, 2
+PROJECTIONS = {"perspective": PROJ_PERSPECTIVE, "fisheye": PROJ_FISHEYE, "panorama": PROJ_PANORAMA}
+PROJECTION_NAMES = {v: k for k, v in PROJECTIONS.items()}
+
+
+class CameraModel(C.Structure):
+    """vcm_camera_model: the camera's projection (PROJ_PERSPECTIVE: the pinhole, the default; PROJ_FISHEYE: equidistant,
+    fovDegrees in (0, 360) across the image width; PROJ_PANORAMA: equirectangular; include/smallvcm_amd.h)"""
+    _fields_ = [("kind", C.c_int), ("fovDegrees", C.c_float)]
+
+
+class SceneDesc9(C.Structure):
+    """vcm_scene_desc9: a version-8 scene and an optional camera model.  Like SceneDesc2 the arrays are owned by the
+    Python object that built it."""
+    _fields_ = [("base", SceneDesc8), ("model", C.POINTER(CameraModel))]
+
+    @property
+    def camera(self):
+        return self.base.camera
+
+
+def with_projection(desc, kind, fov_degrees=0.0):
+    """a SceneDesc2 .. SceneDesc8 as a SceneDesc9 with the projection `kind` ("perspective", "fisheye", "panorama" or a
+    PROJ_* value; None: model = NULL) and, for a fisheye, its field of view.  The result keeps `desc` alive."""
+    if isinstance(desc, SceneDesc9):
+        desc = desc.base
+    d8 = desc if isinstance(desc, SceneDesc8) else with_material_ext(desc, None)
+    d9 = SceneDesc9()
+    d9.base = d8
+    d9._keep = (getattr(d8, "_keep", None), d8)
+    if kind is not None:
+        if isinstance(kind, str):
+            if kind not in PROJECTIONS:
+                raise ValueError("projection: must be 'perspective', 'fisheye' or 'panorama'")
+            kind = PROJECTIONS[kind]
+        m = CameraModel(int(kind), float(fov_degrees))
+        d9.model = C.pointer(m)
+        d9._keep = d9._keep + (m,)
+    return d9
+
+
 class DenoiseParams(C.Structure):
     """vcm_denoise_params: a-trous passes (0 .. 12), the three edge-stopping sigmas, and whether the albedo is divided
     out before the first pass and multiplied back after the last (include/smallvcm_amd.h)"""

@@ -39,6 +39,12 @@
 //                                                        Owen-scrambled Sobol sequence or the default white noise,
 //                                                        nothing after it (vcm_sampler, vcm_scene_desc7,
 //                                                        vcm_scene_file_desc7)
+//       projection fisheye fovDeg | projection panorama  the camera's projection, at most once: an equidistant fisheye
+//                                                        with its field of view across the image width, finite and
+//                                                        in (0, 360) degrees, or a 360 x 180 degree equirectangular
+//                                                        panorama; nothing after it.  The camera line keeps giving the
+//                                                        position and the axes; its fov is not used (vcm_camera_model,
+//                                                        vcm_scene_desc9, vcm_scene_file_desc9)
 //   .obj        v, f (triangles; polygons are fanned around their first vertex; v, v/vt, v/vt/vn, v//vn; negative
 //               = relative indices), usemtl, mtllib; everything else is skipped
 //   .mtl        newmtl, Kd -> mDiffuseReflectance, Ks + Ns -> mPhongReflectance / mPhongExponent (materials.hxx:54-65),
@@ -92,6 +98,9 @@ struct vcm_scene_file {
     std::vector<vcm_material_ext> materialExt;   /* one per material once a `Pr` material is in use, else empty */
     bool haveGgx = false;
     vcm_scene_desc8 desc8;
+    bool haveModel = false;           /* `projection` */
+    vcm_camera_model model;
+    vcm_scene_desc9 desc9;
     ~vcm_scene_file() { vcm_envmap_free(envmap); }
 };
 
@@ -506,6 +515,17 @@ struct Loader {
                 if (out->haveSampler) { ok = fail(at + ": a second sampler"); break; }
                 out->sampler.kind = kind == "sobol" ? VCM_SAMPLER_SOBOL : VCM_SAMPLER_PHILOX;
                 out->haveSampler = true;
+            } else if (key == "projection") {
+                const std::string kind = word(p);
+                float x[1] = { 0.f };
+                const bool got = kind == "panorama" || (kind == "fisheye" && floats(p, x, 1));
+                const std::string rest = got ? word(p) : std::string();
+                if (!got || (!rest.empty() && rest[0] != '#')) { ok = fail(at + ": projection fisheye fovDeg | projection panorama"); break; }
+                if (out->haveModel) { ok = fail(at + ": a second projection"); break; }
+                if (kind == "fisheye" && (!std::isfinite(x[0]) || !(x[0] > 0.f) || !(x[0] < 360.f))) { ok = fail(at + ": projection fisheye fovDeg must be finite and in (0, 360)"); break; }
+                out->model.kind = kind == "fisheye" ? VCM_PROJ_FISHEYE : VCM_PROJ_PANORAMA;
+                out->model.fovDegrees = x[0];
+                out->haveModel = true;
             } else if (key == "light") {
                 const std::string kind = word(p);
                 vcm_light l;
@@ -578,6 +598,8 @@ struct Loader {
         if (out->haveGgx) { const vcm_material_ext none = { { 0.f, 0.f, 0.f }, 0.f }; out->materialExt.resize(out->materials.size(), none); }
         out->desc8.base = out->desc7;
         out->desc8.materialExt = out->haveGgx ? out->materialExt.data() : NULL;
+        out->desc9.base = out->desc8;
+        out->desc9.model = out->haveModel ? &out->model : NULL;
         return true;
     }
 };
@@ -621,6 +643,7 @@ const vcm_scene_desc5 *vcm_scene_file_desc5(const vcm_scene_file *s) { return s 
 const vcm_scene_desc6 *vcm_scene_file_desc6(const vcm_scene_file *s) { return s ? &s->desc6 : NULL; }
 const vcm_scene_desc7 *vcm_scene_file_desc7(const vcm_scene_file *s) { return s ? &s->desc7 : NULL; }
 const vcm_scene_desc8 *vcm_scene_file_desc8(const vcm_scene_file *s) { return s ? &s->desc8 : NULL; }
+const vcm_scene_desc9 *vcm_scene_file_desc9(const vcm_scene_file *s) { return s ? &s->desc9 : NULL; }
 
 vcm_envmap *vcm_envmap_load(const char *path)
 {

@@ -58,6 +58,10 @@ struct SceneHost {
     /* the GGX lobes (scene_host_set_material_ext): one entry per material when some material has a lobe, else empty,
        DScene::ggxOn */
     std::vector<vcm_material_ext> materialExt;
+    /* the camera's projection (scene_host_set_projection; projKind PERSPECTIVE: the reference's pinhole), DScene::projKind ... */
+    int projKind = VCM_PROJ_PERSPECTIVE;
+    float projFovDegrees = 0.f, projK = 0.f, projThetaMax = 0.f;
+    float projF[3] = { 0.f, 0.f, 0.f }, projEx[3] = { 0.f, 0.f, 0.f }, projEy[3] = { 0.f, 0.f, 0.f };
     /* how lights are chosen (scene_host_set_pick; pickMode UNIFORM: no tables), DScene::pickMode ...; pickWeights are
        the weights before the mix and pickQuanta the m_i of pmf[i] = m_i 2^-23 (for reports and tests) */
     int pickMode = VCM_LIGHT_PICK_UNIFORM, pickGuide = 0;
@@ -109,6 +113,8 @@ struct SceneHost {
         d.filterKind = filterKind; d.filterRadius = filterRadius;
         d.samplerKind = sampler;
         d.ggxOn = materialExt.empty() ? 0 : 1; d.offMaterialExt = 0;
+        d.projKind = projKind; d.projK = projK; d.projThetaMax = projThetaMax;
+        for (int k = 0; k < 3; k++) { d.projF[k] = projF[k]; d.projEx[k] = projEx[k]; d.projEy[k] = projEy[k]; }
         { const char *e = getenv("SMALLVCM_AMD_NO_RECTS"); if (e && e[0] == '1') d.nFastRects[0] = d.nFastRects[1] = d.nFastRects[2] = 0; }   /* measurement switch */
     }
 };
@@ -555,6 +561,59 @@ inline bool scene_host_set_material_ext(SceneHost &s, const vcm_material_ext *ex
 inline bool scene_host_from_desc8(const vcm_scene_desc8 &sc, SceneHost &s, std::string &err)
 {
     return scene_host_from_desc7(sc.base, s, err) && scene_host_set_material_ext(s, sc.materialExt, err);
+}
+
+/* ---- the camera's projection (vcm_core.h proj_raster_to_dir / proj_dir_to_raster) ----
+ * The camera frame in binary64 from the camera as stored: f = forward, ex = the world direction of raster +x (the
+ * difference of rasterToWorld at raster (1, 0) and (0, 0)) made orthogonal to f -- what lensRight is --, ey = +-(f x ex),
+ * the sign that points along raster +y (rasterToWorld at (0, 1) minus at (0, 0)).  The fisheye's k = W / fov[rad] pixels
+ * per radian and theta_max = fov / 2.  A thin lens is refused with either angular projection: its focus plane has no
+ * meaning there. */
+inline bool scene_host_set_projection(SceneHost &s, const vcm_camera_model *model, std::string &err)
+{
+    s.projKind = VCM_PROJ_PERSPECTIVE; s.projFovDegrees = 0.f; s.projK = 0.f; s.projThetaMax = 0.f;
+    if (!model || model->kind == VCM_PROJ_PERSPECTIVE) return true;
+    if (model->kind != VCM_PROJ_FISHEYE && model->kind != VCM_PROJ_PANORAMA) { err = "camera model: unknown projection kind"; return false; }
+    const double PI = 3.14159265358979323846;
+    const float fov = model->fovDegrees;
+    if (model->kind == VCM_PROJ_FISHEYE && (!std::isfinite(fov) || !(fov > 0.f) || !(fov < 360.f))) {
+        err = "camera model: a fisheye's fovDegrees must be finite and in (0, 360)"; return false;
+    }
+    if (s.lensRadius > 0.f) { err = "camera model: a thin lens combines with the perspective projection only"; return false; }
+    const float *m = s.camera.rasterToWorld;
+    double o[3], f[3], x[3], y[3], u[3];
+    for (int k = 0; k < 3; k++) {   /* transform_point at (0, 0, 0), (1, 0, 0) and (0, 1, 0) */
+        o[k] = (double)m[12 + k] / (double)m[15];
+        x[k] = ((double)m[12 + k] + m[k]) / ((double)m[15] + m[3]) - o[k];
+        y[k] = ((double)m[12 + k] + m[4 + k]) / ((double)m[15] + m[7]) - o[k];
+        f[k] = s.camera.forward[k];
+    }
+    const double fl = std::sqrt(f[0] * f[0] + f[1] * f[1] + f[2] * f[2]);
+    if (!(fl > 0.0) || !std::isfinite(fl)) { err = "camera model: the camera has no forward direction"; return false; }
+    for (int k = 0; k < 3; k++) f[k] /= fl;
+    const double xf = x[0] * f[0] + x[1] * f[1] + x[2] * f[2];
+    for (int k = 0; k < 3; k++) x[k] -= xf * f[k];
+    const double xl = std::sqrt(x[0] * x[0] + x[1] * x[1] + x[2] * x[2]);
+    if (!(xl > 0.0) || !std::isfinite(xl)) { err = "camera model: the camera's raster axes are degenerate"; return false; }
+    for (int k = 0; k < 3; k++) x[k] /= xl;
+    u[0] = f[1] * x[2] - f[2] * x[1]; u[1] = f[2] * x[0] - f[0] * x[2]; u[2] = f[0] * x[1] - f[1] * x[0];
+    const double uy = u[0] * y[0] + u[1] * y[1] + u[2] * y[2];
+    if (!std::isfinite(uy) || uy == 0.0) { err = "camera model: the camera's raster axes are degenerate"; return false; }
+    const double sign = uy < 0.0 ? -1.0 : 1.0;
+    for (int k = 0; k < 3; k++) { s.projF[k] = (float)f[k]; s.projEx[k] = (float)x[k]; s.projEy[k] = (float)(sign * u[k]); }
+    s.projKind = model->kind;
+    if (model->kind == VCM_PROJ_FISHEYE) {
+        const double rad = (double)fov * PI / 180.0;
+        s.projFovDegrees = fov;
+        s.projK = (float)((double)s.camera.resolution[0] / rad);
+        s.projThetaMax = (float)(0.5 * rad);
+    }
+    return true;
+}
+
+inline bool scene_host_from_desc9(const vcm_scene_desc9 &sc, SceneHost &s, std::string &err)
+{
+    return scene_host_from_desc8(sc.base, s, err) && scene_host_set_projection(s, sc.model, err);
 }
 
 /* ---- brute-force list: consecutive triangles in pairs, fields interleaved (vcm_core.h TriPair) ---- */

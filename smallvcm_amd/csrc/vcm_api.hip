@@ -182,6 +182,7 @@ struct vcm_ctx : Scratch {
     bool envMap;                      /* the scene's background is an environment map: the SceneRectsE / SceneListE / SceneBvhE kernels */
     bool lens;                        /* the camera is a thin lens: the WithLens kernels for the camera vertex */
     bool filter;                      /* the scene has a pixel filter: the WithLens kernels too (vcm_core.h kLens) */
+    bool proj;                        /* the scene has a fisheye or panorama projection: the WithLens kernels too */
     bool pick;                        /* lights are chosen from a table: the WithPick kernels */
     bool lights;                      /* the scene holds a spot or a sphere light: WithLights over WithPick (then pick is set) */
     bool sobol;                       /* the scene asks for the Sobol sampler: the WithSobol kind of every kernel that draws */
@@ -226,7 +227,7 @@ static hipEvent_t vcm_ctx::*const kOrderEvents[] = {
 
 /* A ray-casting kernel is launched in the instantiation of the context's kind, under the wrappers it exists for (Wrap:
    scene_kind.h): f(tag) launches it with S = typename decltype(tag)::type.  What f evaluates, it evaluates once. */
-template <unsigned Wrap, class F> static void launch_kind(const vcm_ctx *c, F &&f) { with_scene_kind<Wrap>(c->kind, SceneWrappers{ c->lens || c->filter, c->pick, c->lights, c->sobol, c->ggx }, f); }
+template <unsigned Wrap, class F> static void launch_kind(const vcm_ctx *c, F &&f) { with_scene_kind<Wrap>(c->kind, SceneWrappers{ c->lens || c->filter || c->proj, c->pick, c->lights, c->sobol, c->ggx }, f); }
 
 /* K4 of a context: k_merge_pairs or k_merge_walk (VCM_MERGE_*), with the pow its exponents allow */
 typedef void (*MergeKernel)(const DScene *, IterParams, GridStore, VertexStore, const int *, const int *, unsigned long long *, int, StampArgs);
@@ -816,6 +817,7 @@ static vcm_ctx *create_from_host(SceneHost *h, int algorithm, float radiusFactor
     c->envMap = h->envW > 0;
     c->lens = h->lensRadius > 0.f;
     c->filter = h->filterKind != VCM_FILTER_BOX;
+    c->proj = h->projKind != VCM_PROJ_PERSPECTIVE;
     c->pick = h->pickMode != VCM_LIGHT_PICK_UNIFORM;
     c->lights = c->pick && scene_host_has_new_lights(*h);   /* such a scene always has a table (scene_host_lights_need_table) */
     c->sobol = h->sampler == VCM_SAMPLER_SOBOL;
@@ -938,6 +940,12 @@ vcm_ctx *vcm_create_sharded8(const vcm_scene_desc8 *scene, int algorithm, float 
     return create_from_desc("vcm_create8", scene_host_from_desc8, scene, algorithm, radiusFactor, radiusAlpha, seed, device, rank, worldSize);
 }
 
+vcm_ctx *vcm_create_sharded9(const vcm_scene_desc9 *scene, int algorithm, float radiusFactor, float radiusAlpha,
+                             int seed, int device, int rank, int worldSize)
+{
+    return create_from_desc("vcm_create9", scene_host_from_desc9, scene, algorithm, radiusFactor, radiusAlpha, seed, device, rank, worldSize);
+}
+
 /* Which device a renderer-per-host-core host puts its next renderer on (vcm_next_device).  The reference's driver
  * builds one renderer per host core and runs them concurrently (smallvcm.cxx:61-72, :99-108): on a multi-GPU node the
  * drop-in deals them round-robin over the visible devices -- every GPU renders whole iterations of its renderers
@@ -1011,6 +1019,11 @@ vcm_ctx *vcm_create7(const vcm_scene_desc7 *scene, int algorithm, float radiusFa
 vcm_ctx *vcm_create8(const vcm_scene_desc8 *scene, int algorithm, float radiusFactor, float radiusAlpha, int seed)
 {
     return vcm_create_sharded8(scene, algorithm, radiusFactor, radiusAlpha, seed, next_device(true), 0, 1);
+}
+
+vcm_ctx *vcm_create9(const vcm_scene_desc9 *scene, int algorithm, float radiusFactor, float radiusAlpha, int seed)
+{
+    return vcm_create_sharded9(scene, algorithm, radiusFactor, radiusAlpha, seed, next_device(true), 0, 1);
 }
 
 void vcm_destroy(vcm_ctx *c)
@@ -2379,7 +2392,7 @@ int vcm_render_features(vcm_ctx *c)
     if (!c) return fail("vcm_render_features", "ctx is NULL");
     if (ensure_device(c)) return -1;
     if (ensure_feature_buffers(c)) return -1;
-    HIPCHK(dn_launch_features(c->dScene, c->kind, c->ggx, c->resX, c->p0, c->nLocal, c->dGuide, c->dAlbedo, c->stream));
+    HIPCHK(dn_launch_features(c->dScene, c->kind, c->ggx, c->proj, c->resX, c->p0, c->nLocal, c->dGuide, c->dAlbedo, c->stream));
     c->featuresValid = true;
     return 0;
 }
@@ -3213,6 +3226,7 @@ int vcm_debug_kat(vcm_ctx *c, int op, int n, const float *in, float *out)
     if (!c || !in || !out || n < 0 || op < 0 || op >= VCM_KAT_OPS) return fail("vcm_debug_kat", "bad argument");
     if (op == VCM_KAT_FILTER && !c->filter) return fail("vcm_debug_kat", "VCM_KAT_FILTER needs a context with a pixel filter (vcm_create6)");
     if (op == VCM_KAT_LIGHT_RADIANCE_AT && !c->lights) return fail("vcm_debug_kat", "VCM_KAT_LIGHT_RADIANCE_AT needs a context with a spot or a sphere light");
+    if (op == VCM_KAT_PROJECTION && !c->proj) return fail("vcm_debug_kat", "VCM_KAT_PROJECTION needs a context with a fisheye or panorama projection (vcm_create9)");
     if (op == VCM_KAT_LENS && !c->lens) return fail("vcm_debug_kat", "VCM_KAT_LENS needs a context with a thin lens (vcm_create4)");
     if (ensure_device(c)) return -1;
     if (n == 0) return 0;
@@ -3277,6 +3291,14 @@ int vcm_debug_ggx(vcm_ctx *c, int *nLobes)
         for (const vcm_material_ext &x : c->scene->materialExt) *nLobes += ggx_has_lobe(x) ? 1 : 0;
     }
     return c->ggx ? 1 : 0;
+}
+
+int vcm_debug_projection(vcm_ctx *c, int *kind, float *fovDegrees)
+{
+    if (!c) return fail("vcm_debug_projection", "bad argument");
+    if (kind) *kind = c->scene->projKind;
+    if (fovDegrees) *fovDegrees = c->scene->projFovDegrees;
+    return c->proj ? 1 : 0;
 }
 
 int vcm_debug_lights_kind(vcm_ctx *c)

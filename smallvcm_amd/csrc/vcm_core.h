@@ -407,6 +407,11 @@ struct DScene {
     /* the GGX lobes (vcm_material_ext, one per material; ggxOn == 0: no material has one and the table is absent) */
     int ggxOn;
     long long offMaterialExt;
+    /* the camera's projection (vcm_camera_model; projKind == VCM_PROJ_PERSPECTIVE: the reference's pinhole, nothing below
+       is read), built by scene_host.h in binary64: the fisheye's pixels per radian k = W / fov and half field of view,
+       and the camera frame f = forward, ex = raster +x made orthogonal to f, ey = +-(f x ex) along raster +y */
+    int projKind;
+    float projK, projThetaMax, projF[3], projEx[3], projEy[3];
     template <class T> VCM_HD const T *at(long long off) const { return reinterpret_cast<const T *>(reinterpret_cast<const char *>(this) + off); }
     VCM_HD const vcm_material_ext *materialExt() const { return at<vcm_material_ext>(offMaterialExt); }
     VCM_HD const vcm_prim *prims() const { return at<vcm_prim>(offPrims); }
@@ -475,11 +480,15 @@ template <class S> struct WithLens : S { static constexpr bool kLens = true; };
 #define VCM_LENS_KIND(S) (S::kLens)
 #define VCM_LENS_ON(S, sc) (S::kLens && (sc).lensRadius > 0.f)
 #define VCM_FILTER_ON(S, sc) (S::kLens && (sc).filterKind != VCM_FILTER_BOX)
+#define VCM_PROJ_ON(S, sc) (S::kLens && (sc).projKind != VCM_PROJ_PERSPECTIVE)
 #else
 #define VCM_LENS_KIND(S) true
 #define VCM_LENS_ON(S, sc) ((sc).lensRadius > 0.f)
 #define VCM_FILTER_ON(S, sc) ((sc).filterKind != VCM_FILTER_BOX)
+#define VCM_PROJ_ON(S, sc) ((sc).projKind != VCM_PROJ_PERSPECTIVE)
 #endif
+/* (a fisheye or panorama projection, DScene::projKind, is the third such branch: a context with one launches the same
+   WithLens kinds, and the kinds without the wrapper hold none of its code) */
 
 /* kPick: lights are chosen from a table (DScene::pickMode != UNIFORM).  Only the kernels that choose a light or weigh
    an emitter hit (K1, K3, k_connect_di, the path tracer) and the known-answer kernel exist in these kinds, over each
@@ -2693,6 +2702,99 @@ VCM_HD int filter_splat_pixel(const DScene &sc, float x, float y, const FilterDr
     return int(x) + int(y) * (int)cam.resolution[0];
 }
 
+/* ---- camera projections (DESIGN.md "Camera projections") ----
+ * FISHEYE (equidistant) and PANORAMA (equirectangular), stated once: the forward map, a raster point to its direction,
+ * and the inverse, a direction to its raster point, each with cameraPdfW = d(raster area) / d(solid angle) of that
+ * direction.  Every camera site calls one of the two from its VCM_PROJ_ON branch; the perspective statements stay where
+ * they were.  Only + - x / sqrt and detmath.h, so the host and the device agree bit for bit.  The max(., 1e-4) under the
+ * densities is the same expression on both sides of the camera vertex: a connection at a panorama's pole (or towards
+ * theta = pi of a wide fisheye) is finite instead of a division by zero, and the clamp touches a solid angle of order
+ * 1e-8.  The sine is taken from the direction's components on the inverse side (|d - (d . axis) axis|), from
+ * dm_sincosf on the forward side. */
+VCM_HD float proj_fisheye_pdf(const DScene &sc, float theta, float sinTheta)
+{
+    const float g = (theta < 1e-3f) ? 1.f : theta / smax(sinTheta, 1e-4f);
+    return (sc.projK * sc.projK) * g;
+}
+VCM_HD float proj_panorama_pdf(const DScene &sc, float sinTheta)
+{
+    const float W = sc.camera.resolution[0], H = sc.camera.resolution[1];
+    return (W * H) / ((2.f * VCM_PI_F * VCM_PI_F) * smax(fabsf(sinTheta), 1e-4f));
+}
+/* forward: the direction through raster point (x, y) and its cameraPdfW; false when the point is outside the fisheye's
+   image circle or above / below the panorama's rows (x is periodic there): such a sample contributes nothing */
+VCM_HD bool proj_raster_to_dir(const DScene &sc, float x, float y, V3 &dir, float &pdfW)
+{
+    const float W = sc.camera.resolution[0], H = sc.camera.resolution[1];
+    const V3 f = ld3(sc.projF), ex = ld3(sc.projEx), ey = ld3(sc.projEy);
+    float s, c;
+    if (sc.projKind == VCM_PROJ_FISHEYE) {
+        const float qx = x - 0.5f * W, qy = y - 0.5f * H;
+        const float rho = sqrtf(qx * qx + qy * qy);
+        const float theta = rho / sc.projK;
+        dir = f; pdfW = 1.f;
+        if (theta > sc.projThetaMax) return false;
+        dm_sincosf_cold(theta, s, c);
+        if (rho > 0.f) {
+            const float a = s / rho;
+            dir = normalize((a * qx) * ex + (a * qy) * ey + c * f);
+        }
+        pdfW = proj_fisheye_pdf(sc, theta, s);
+        return true;
+    }
+    dir = f; pdfW = 1.f;
+    if (!(y >= 0.f && y < H)) return false;
+    const float lambda = (2.f * VCM_PI_F) * (x / W - 0.5f);
+    const float theta = VCM_PI_F * (y / H);
+    float sl, cl;
+    dm_sincosf_cold(lambda, sl, cl);
+    dm_sincosf_cold(theta, s, c);
+    dir = normalize(s * (cl * f + sl * ex) - c * ey);
+    pdfW = proj_panorama_pdf(sc, s);
+    return true;
+}
+/* inverse: the raster point of the unit direction d (camera -> world point) and the cameraPdfW of that direction; false
+   outside the fisheye's field of view.  The panorama's x is wrapped into [0, W) and y == H goes to the last row; the
+   caller's bounds check follows. */
+VCM_HD bool proj_dir_to_raster(const DScene &sc, V3 d, float &rx, float &ry, float &pdfW)
+{
+    const float W = sc.camera.resolution[0], H = sc.camera.resolution[1];
+    const float df = dot(d, ld3(sc.projF)), a = dot(d, ld3(sc.projEx)), b = dot(d, ld3(sc.projEy));
+    if (sc.projKind == VCM_PROJ_FISHEYE) {
+        const float theta = dm_acosf(df);
+        if (theta > sc.projThetaMax) return false;
+        const float s = sqrtf(a * a + b * b);
+        rx = 0.5f * W; ry = 0.5f * H;
+        if (s > 0.f) {
+            const float t = (sc.projK * theta) / s;
+            rx = rx + t * a; ry = ry + t * b;
+        }
+        pdfW = proj_fisheye_pdf(sc, theta, s);
+        return true;
+    }
+    const float theta = dm_acosf(-b);
+    const float lambda = dm_atan2f(a, df);
+    rx = W * (lambda / (2.f * VCM_PI_F) + 0.5f);
+    ry = H * (theta / VCM_PI_F);
+    if (rx >= W) rx = rx - W;
+    if (rx < 0.f) rx = 0.f;
+    if (ry >= H) ry = H * 0.99999994f;
+    pdfW = proj_panorama_pdf(sc, sqrtf(df * df + a * a));
+    return true;
+}
+/* filter_splat_pixel for the panorama: x + o wraps modulo W, a y outside [0, H) is dropped (as the camera side drops a
+   moved sample there: the pole rows come out slightly darker under a filter, by the share of the kernel that leaves) */
+VCM_HD int proj_panorama_splat_pixel(const DScene &sc, float x, float y, const FilterDraw &d, float &ox, float &oy)
+{
+    const float W = sc.camera.resolution[0], H = sc.camera.resolution[1];
+    filter_offset(sc.filterKind, sc.filterRadius, d, ox, oy);
+    x = x + ox; y = y + oy;
+    if (x < 0.f) x = x + W;
+    if (x >= W) x = x - W;
+    if (!(x >= 0 && y >= 0 && x < W && y < H)) return -1;
+    return int(x) + int(y) * (int)W;
+}
+
 /* ConnectToCamera :862-933; the splat is an atomic add (Framebuffer::AddColor
  * framebuffer.hxx:43-57 on an arbitrary pixel) */
 /* splatOut == NULL: the splat is an fp32 atomic add on fb (strict mode);
@@ -2702,7 +2804,9 @@ VCM_HD int filter_splat_pixel(const DScene &sc, float x, float y, const FilterDr
  * without either).  With a filter the splat goes to the pixel that holds the projection moved by a kind-5 offset, and
  * nothing else changes: same contribution, same MIS weight; lightSplats counts what is splatted.  With a lens the
  * camera vertex is a lens point drawn per light vertex, and the rest is evaluated from it: the lens-area pdf of that
- * vertex is common to every strategy that holds it, so it enters no MIS weight, and it cancels the importance's. */
+ * vertex is common to every strategy that holds it, so it enters no MIS weight, and it cancels the importance's.
+ * With a fisheye or a panorama the raster point and cameraPdfW come from proj_dir_to_raster; cameraPdfA, the weight and
+ * the contribution are evaluated from that cameraPdfW exactly as for the pinhole. */
 template <class SC>
 VCM_HD void connect_to_camera(const SC &sc, const IterParams &P, const SubPathState &st, V3 hitpoint,
                               const Bsdf &bsdf, float *fb, LaneStats &ls, F4 *splatOut, int lensPath)
@@ -2719,16 +2823,23 @@ VCM_HD void connect_to_camera(const SC &sc, const IterParams &P, const SubPathSt
         if (!lens_project(sc, camPos, hitpoint, ip)) return;
     }
     V3 directionToCamera = camPos - hitpoint;
-    if (dot(ld3(cam.forward), -directionToCamera) <= 0.f) return;
-    if (!VCM_LENS_ON(SC, sc)) ip = transform_point(cam.worldToRaster, hitpoint);
+    float projPdfW = 0.f;   /* a fisheye or a panorama: the inverse map gives the raster point and cameraPdfW; no half-space test */
+    if (VCM_PROJ_ON(SC, sc)) {
+        ip = sp3(0.f);
+        if (!proj_dir_to_raster(sc, normalize(hitpoint - camPos), ip.x, ip.y, projPdfW)) return;
+    } else {
+        if (dot(ld3(cam.forward), -directionToCamera) <= 0.f) return;
+        if (!VCM_LENS_ON(SC, sc)) ip = transform_point(cam.worldToRaster, hitpoint);
+    }
     int filterPixel = 0;
     if (VCM_FILTER_ON(SC, sc)) {
         const float fr = sc.filterRadius;   /* no offset reaches the image from outside the image grown by the support */
-        if (!(ip.x >= -fr && ip.y >= -fr && ip.x < cam.resolution[0] + fr && ip.y < cam.resolution[1] + fr)) return;
+        const bool wraps = VCM_PROJ_ON(SC, sc) && sc.projKind == VCM_PROJ_PANORAMA;   /* x + o wraps modulo W */
+        if (!wraps && !(ip.x >= -fr && ip.y >= -fr && ip.x < cam.resolution[0] + fr && ip.y < cam.resolution[1] + fr)) return;
         FilterDraw d;
         float ox, oy;
         filter_rnd(sc, P, 5u, (uint32_t)lensPath, st.pathLength, sc.filterKind, d);
-        filterPixel = filter_splat_pixel(sc, ip.x, ip.y, d, ox, oy);
+        filterPixel = wraps ? proj_panorama_splat_pixel(sc, ip.x, ip.y, d, ox, oy) : filter_splat_pixel(sc, ip.x, ip.y, d, ox, oy);
         if (filterPixel < 0) return;
     } else if (!(ip.x >= 0 && ip.y >= 0 && ip.x < cam.resolution[0] && ip.y < cam.resolution[1])) return;
     const float distEye2 = lensqr(directionToCamera);
@@ -2740,7 +2851,7 @@ VCM_HD void connect_to_camera(const SC &sc, const IterParams &P, const SubPathSt
     bsdfRevPdfW *= bsdf.contProb;
     const float cosAtCamera = dot(ld3(cam.forward), -directionToCamera);
     const float imagePointToCameraDist = cam.imagePlaneDist / cosAtCamera;
-    const float imageToSolidAngleFactor = sqr(imagePointToCameraDist) / cosAtCamera;
+    const float imageToSolidAngleFactor = VCM_PROJ_ON(SC, sc) ? projPdfW : sqr(imagePointToCameraDist) / cosAtCamera;
     const float imageToSurfaceFactor = imageToSolidAngleFactor * fabsf(cosToCamera) / sqr(distance);
     const float cameraPdfA = imageToSurfaceFactor;
     const float wLight = mis(cameraPdfA / P.lightSubPathCount) *
@@ -3467,12 +3578,17 @@ VCM_HD void camera_path_begin(const S &sc, const IterParams &P, CameraPath &cp, 
     const float cosAtCamera = dot(ld3(cam.forward), dir);
     const float imagePointToCameraDist = cam.imagePlaneDist / cosAtCamera;
     const float imageToSolidAngleFactor = sqr(imagePointToCameraDist) / cosAtCamera;
-    const float cameraPdfW = imageToSolidAngleFactor;
+    float cameraPdfW = imageToSolidAngleFactor;
+    /* a fisheye or a panorama replaces the direction and the density (the pinhole's are computed and dropped: as a branch
+       of its own with an early return this cost every K3 of these kinds 32 bytes of scratch); pathLength 0 marks a sample
+       outside the image: camera_path_step ends such a path before it casts or counts a ray, and its colour stays 0 */
+    bool inside = true;
+    if (VCM_PROJ_ON(S, sc)) inside = proj_raster_to_dir(sc, rx, ry, dir, cameraPdfW);
     SubPathState &st = cp.st;
     st.origin = org;
     st.direction = dir;
     st.throughput = sp3(1.f);
-    st.pathLength = 1;
+    st.pathLength = inside ? 1u : 0u;
     st.specularPath = 1;
     st.isFiniteLight = 0;
     st.dVCM = mis(P.lightSubPathCount / cameraPdfW);
@@ -3500,6 +3616,7 @@ VCM_HD bool camera_path_step(const SC &sc, const IterParams &P, CameraPath &cp, 
                              CameraWaveQueues &wqs, const QueryKey &qk /* wavefront mode with the query sort: query_key_load, once per kernel */)
 {
     SubPathState &st = cp.st;
+    if (VCM_PROJ_ON(SC, sc) && st.pathLength == 0u) return false;   /* a sample outside the projection's image (camera_path_begin) */
     Ray ray; ray.org = st.origin + st.direction * VCM_EPS_RAY; ray.dir = st.direction; ray.tmin = 0;
     Isect isect; isect.dist = 1e36f; isect.matID = 0; isect.lightID = -1; isect.normal = sp3(0.f); isect.prim = -1;
     ls.cameraRays++;
@@ -3800,6 +3917,10 @@ VCM_HD void pt_path_begin(const S &sc, const IterParams &P, PtPath &pp, int loca
     pp.weight = sp3(1.f);
     pp.color = sp3(0.f);
     pp.pathLength = 1;
+    if (VCM_PROJ_ON(S, sc)) {   /* a fisheye or a panorama; pathLength 0: outside its image, pt_path_step ends the path at once */
+        float cameraPdfW;
+        if (!proj_raster_to_dir(sc, rx, ry, pp.dir, cameraPdfW)) pp.pathLength = 0;
+    }
     pp.lastSpecular = 1;
     pp.lastPdfW = 1.f;
 }
@@ -3809,6 +3930,7 @@ VCM_HD bool pt_path_step(const SC &sc, const IterParams &P, PtPath &pp, LaneStat
 {
     const int lightCount = sc.nLights;
     const float uniformPickProb = 1.f / lightCount;   /* :48-49 */
+    if (VCM_PROJ_ON(SC, sc) && pp.pathLength == 0u) return false;   /* a sample outside the projection's image (pt_path_begin) */
     Ray ray; ray.org = pp.org; ray.dir = pp.dir; ray.tmin = 0;
     Isect isect; isect.dist = 1e36f; isect.matID = 0; isect.lightID = -1; isect.normal = sp3(0.f); isect.prim = -1;
     ls.cameraRays++;
@@ -3928,6 +4050,10 @@ VCM_HD bool eyelight_path(const SC &sc, const IterParams &P, int localPath, V3 &
         float r[2];
         lens_rnd(sc, P, 2u, (uint32_t)pathIdx, 0u, r);
         lens_ray(sc, ray.dir, r[0], r[1], ray.org, ray.dir);
+    }
+    if (VCM_PROJ_ON(SC, sc)) {   /* a fisheye or a panorama: outside its image nothing is cast, counted or added */
+        float cameraPdfW;
+        if (!proj_raster_to_dir(sc, rx, ry, ray.dir, cameraPdfW)) return false;
     }
     ray.tmin = 0;
     Isect isect; isect.dist = 1e36f; isect.matID = 0; isect.lightID = -1; isect.normal = sp3(0.f); isect.prim = -1;

@@ -27,7 +27,7 @@ VCM_HD float dn_albedo_component(float a)
 }
 
 /* One ray through the CENTRE of pixel `pixel` from the pinhole (a thin lens is ignored: guides stay sharp), the scene
- * kind's own closest-hit routine. */
+ * kind's own closest-hit routine.  A fisheye or panorama context sends the ray through its projection instead. */
 template <class SC>
 VCM_HD void feature_pixel(const SC &sc, int resX, int pixel, F4 &guide, F4 &albedo)
 {
@@ -41,6 +41,11 @@ VCM_HD void feature_pixel(const SC &sc, int resX, int pixel, F4 &guide, F4 &albe
     Isect isect; isect.dist = 1e36f; isect.matID = 0; isect.lightID = -1; isect.normal = sp3(0.f); isect.prim = -1;
     guide = mk4(0.f, 0.f, 0.f, 0.f);
     albedo = mk4(1.f, 1.f, 1.f, 1.f);
+    if (VCM_PROJ_ON(SC, sc)) {   /* a fisheye or a panorama (the WithLens forms): the guides line up with the image; a pixel
+                                   centre outside the fisheye's circle reads as a miss */
+        float cameraPdfW;
+        if (!proj_raster_to_dir(sc, sx, sy, ray.dir, cameraPdfW)) return;
+    }
     if (!scene_intersect(sc, ray, isect)) return;
     guide = mk4(isect.normal.x, isect.normal.y, isect.normal.z, isect.dist);
     if (isect.lightID >= 0) return;   /* an emitter */
@@ -306,8 +311,8 @@ VCM_HD F4 dn_filter_pixel2(const DnPass2 &P2, int x, int y, F4 albedoP, Load &&l
 
 /* ---------------- launches (vcm_denoise.hip; the C-ABI of vcm_api.hip calls them) ---------------- */
 #if defined(__HIPCC__)
-/* guide / albedo of the pixels [p0, p0 + nLocal), by the k_features of the context's kind */
-hipError_t dn_launch_features(const DScene *dScene, SceneKind kind, bool ggx, int resX, int p0, int nLocal, F4 *guide, F4 *albedo,
+/* guide / albedo of the pixels [p0, p0 + nLocal), by the k_features of the context's kind (proj: its WithLens form) */
+hipError_t dn_launch_features(const DScene *dScene, SceneKind kind, bool ggx, bool proj, int resX, int p0, int nLocal, F4 *guide, F4 *albedo,
                               hipStream_t stream);
 /* out = the filtered colour.  fb3 != NULL: the colour is a W*H*3 float image times `scale`, else the float4 image
    `color`.  tmpA, tmpB: two W*H float4 images of scratch (unused when passes == 0).  Parameters already checked. */

@@ -158,11 +158,18 @@ k_atrous_var(DnPass2 P2, const F4 *__restrict__ color, const F4 *__restrict__ gu
 
 namespace vcm {
 
-hipError_t dn_launch_features(const DScene *dScene, SceneKind kind, bool ggx, int resX, int p0, int nLocal, F4 *guide, F4 *albedo,
+hipError_t dn_launch_features(const DScene *dScene, SceneKind kind, bool ggx, bool proj, int resX, int p0, int nLocal, F4 *guide, F4 *albedo,
                               hipStream_t stream)
 {
     int blocks = (nLocal + 255) / 256;
     blocks = blocks < 1 ? 1 : (blocks > 4096 ? 4096 : blocks);
+    if (proj) {   /* a fisheye or a panorama: the WithLens forms, WithLens<S> and WithGgx<WithLens<S>>, which hold the projection */
+        with_scene_kind<kWrapLens | kWrapGgx>(kind, SceneWrappers{ true, false, false, false, ggx }, [&](auto tag) {
+            using S = typename decltype(tag)::type;
+            hipLaunchKernelGGL((k_features<S>), dim3(blocks), dim3(256), 0, stream, dScene, resX, p0, nLocal, guide, albedo);
+        });
+        return hipGetLastError();
+    }
     with_scene_kind<kWrapGgx>(kind, SceneWrappers{ false, false, false, false, ggx }, [&](auto tag) {   /* one more form per kind: WithGgx<S> */
         using S = typename decltype(tag)::type;
         hipLaunchKernelGGL((k_features<S>), dim3(blocks), dim3(256), 0, stream, dScene, resX, p0, nLocal, guide, albedo);

@@ -128,6 +128,19 @@ VCM_HD void kat_eval(const SC &sc, int op, const float *in, float *out)
         out[0] = r.x; out[1] = r.y; out[2] = r.z;
         if (!iszero(r)) { out[3] = directPdfA; out[4] = emissionPdfW; }
     } break;
+    case VCM_KAT_PROJECTION:   /* a fisheye or a panorama: the forward and the inverse map of the camera sites (vcm_core.h) */
+        if constexpr (VCM_LENS_KIND(SC)) {
+            if (sc.projKind == VCM_PROJ_PERSPECTIVE) break;
+            V3 dir = sp3(0.f);
+            float pdfW = 0.f, rx = 0.f, ry = 0.f, pdfBack = 0.f;
+            if (proj_raster_to_dir(sc, in[0], in[1], dir, pdfW)) { out[0] = dir.x; out[1] = dir.y; out[2] = dir.z; out[3] = pdfW; out[4] = 1.f; }
+            const vcm_camera &cam = sc.camera;
+            if (proj_dir_to_raster(sc, normalize(ld3(in + 2) - ld3(cam.position)), rx, ry, pdfBack)) {
+                out[5] = rx; out[6] = ry; out[8] = pdfBack;
+                out[7] = (rx >= 0 && ry >= 0 && rx < cam.resolution[0] && ry < cam.resolution[1]) ? 1.f : 0.f;
+            }
+        }
+        break;
     default: break;
     }
 }

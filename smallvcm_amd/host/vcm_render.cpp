@@ -13,6 +13,7 @@
 //              [--envmap f.hdr|f.pfm [--envmap-scale S]] [--aperture R --focus D]
 //              [--light-pick uniform|power [--light-pick-mix A] [--light-pick-report]]
 //              [--filter tent|bspline R]
+//              [--projection fisheye DEG|panorama]
 //              [--denoise [passes]] [--denoise-sigma c,n,z] [--no-demodulate] [--features-out prefix]
 //              [--noise-target E [--check-every N] [--max-iterations M]] [--track-variance] [--robust [M]]
 //              [--tonemap clamp|reinhard|aces|hable] [--exposure EV] [--auto-exposure [key]] [--bloom S [levels]]
@@ -45,6 +46,11 @@
 // --sampler sobol|philox: where the paths' random floats come from (vcm_sampler, vcm_scene_desc7): the Owen-scrambled
 // Sobol sequence or the default white noise; it overrides a scene file's `sampler` directive, and with --gpus every
 // renderer of the farm takes it.
+//
+// --projection fisheye DEG|panorama: the camera's projection (vcm_camera_model, vcm_scene_desc9) in place of the pinhole:
+// an equidistant fisheye of DEG degrees (finite, in (0, 360)) across the image width, or a 360 x 180 degree
+// equirectangular panorama (written as .pfm or .hdr it loads back as an environment map; DESIGN.md "Camera projections"
+// has the recipe); it overrides a scene file's `projection` directive.  Not with --gpus, and not with a lens.
 //
 // --denoise [passes]: the image goes through the edge-avoiding a-trous filter (vcm_denoise: vcm_denoise_defaults with
 // `passes`, --denoise-sigma's sigmaColor,sigmaNormal,sigmaDepth and --no-demodulate applied) before it is written to
@@ -139,6 +145,8 @@ int main(int argc, char **argv)
     bool havePickMix = false, pickReport = false;
     std::string filterName;
     std::string samplerName;
+    std::string projName;
+    float projFov = 0.f;
     float filterRadius = 0.f;
     bool denoise = false;
     vcm_denoise_params dn;
@@ -208,6 +216,17 @@ int main(int argc, char **argv)
             need(1);
             samplerName = argv[++i];
             if (samplerName != "sobol" && samplerName != "philox") { fprintf(stderr, "vcm_render: --sampler sobol|philox\n"); return 2; }
+        }
+        else if (a == "--projection") {
+            need(1);
+            projName = argv[++i];
+            if (projName != "fisheye" && projName != "panorama") { fprintf(stderr, "vcm_render: --projection fisheye DEG|panorama\n"); return 2; }
+            if (projName == "fisheye") {
+                need(1);
+                char *e = NULL;
+                projFov = strtof(argv[++i], &e);
+                if (e == argv[i] || *e) { fprintf(stderr, "vcm_render: --projection fisheye DEG|panorama\n"); return 2; }
+            }
         }
         else if (a == "--denoise") {
             denoise = true;
@@ -396,8 +415,30 @@ int main(int argc, char **argv)
         ggxScene = &ggxDesc;
     }
     if (materialExt && gpus > 0) { fprintf(stderr, "vcm_render: a scene file with Pr materials cannot be rendered with --gpus yet\n"); return 1; }
+    // the projection (--projection, else a scene file's `projection`): the scene as a version-9 description over whatever the flags made of it
+    vcm_camera_model flagModel;
+    flagModel.kind = projName == "fisheye" ? VCM_PROJ_FISHEYE : VCM_PROJ_PANORAMA;
+    flagModel.fovDegrees = projFov;
+    const vcm_camera_model *model = !projName.empty() ? &flagModel : loaded ? vcm_scene_file_desc9(loaded)->model : NULL;
+    vcm_scene_desc9 projDesc;
+    const vcm_scene_desc9 *projScene = NULL;
+    if (model && model->kind != VCM_PROJ_PERSPECTIVE) {
+        if (gpus > 0) { fprintf(stderr, "vcm_render: a projection with --gpus is not supported (the farm takes version-1 scenes)\n"); return 2; }
+        memset(&projDesc, 0, sizeof(projDesc));
+        if (ggxScene) projDesc.base = *ggxScene;
+        else if (samplerScene) projDesc.base.base = *samplerScene;
+        else if (filterScene) projDesc.base.base.base = *filterScene;
+        else if (pickScene) projDesc.base.base.base.base = *pickScene;
+        else if (lensScene) projDesc.base.base.base.base.base = *lensScene;
+        else if (envScene) projDesc.base.base.base.base.base.base = *envScene;
+        else if (loaded) projDesc.base.base.base.base.base.base = *vcm_scene_file_desc3(loaded);
+        else scene_as_desc2(scene, projDesc.base.base.base.base.base.base.base);   // the built-in scene (the arrays stay in `scene`)
+        projDesc.model = model;
+        projScene = &projDesc;
+    }
     auto create = [&](int s) {
-        return ggxScene ? vcm_create_sharded8(ggxScene, algorithm, radiusFactor, radiusAlpha, s, device, 0, 1)
+        return projScene ? vcm_create_sharded9(projScene, algorithm, radiusFactor, radiusAlpha, s, device, 0, 1)
+             : ggxScene ? vcm_create_sharded8(ggxScene, algorithm, radiusFactor, radiusAlpha, s, device, 0, 1)
              : samplerScene ? vcm_create_sharded7(samplerScene, algorithm, radiusFactor, radiusAlpha, s, device, 0, 1)
              : filterScene ? vcm_create_sharded6(filterScene, algorithm, radiusFactor, radiusAlpha, s, device, 0, 1)
              : pickScene ? vcm_create_sharded5(pickScene, algorithm, radiusFactor, radiusAlpha, s, device, 0, 1)

@@ -21,7 +21,7 @@ import os
 
 import numpy as np
 
-from ._abi import (CURVES, DISPLAY_SOURCES, DenoiseParams, DenoiseParams2, DisplayParams, DisplayStats, FEATURES, IMAGE_BGR8, TRANSFERS, NoiseStats, PART_NAMES, PARTS, PartsStats, ROBUST_DEFAULT_BUCKETS, RobustStats, SceneDesc, SceneDesc2, SceneDesc3, SceneDesc4, SceneDesc5, SceneDesc6, SceneDesc7, SceneDesc8, Stats, SCENE_CONFIGS, VCM_MERGE_RECORD_FLOATS, ALGO_LIGHT_TRACE, ALGO_PPM, ALGO_BPM,
+from ._abi import (CURVES, DISPLAY_SOURCES, DenoiseParams, DenoiseParams2, DisplayParams, DisplayStats, FEATURES, IMAGE_BGR8, TRANSFERS, NoiseStats, PART_NAMES, PARTS, PartsStats, ROBUST_DEFAULT_BUCKETS, RobustStats, SceneDesc, SceneDesc2, SceneDesc3, SceneDesc4, SceneDesc5, SceneDesc6, SceneDesc7, SceneDesc8, SceneDesc9, Stats, SCENE_CONFIGS, VCM_MERGE_RECORD_FLOATS, ALGO_LIGHT_TRACE, ALGO_PPM, ALGO_BPM,
                    ALGO_BPT, ALGO_VCM)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -77,6 +77,10 @@ def load_library(require_gpu=True):
         if hasattr(L, "vcm_create_sharded8"):   # likewise: a SceneDesc8 then raises
             L.vcm_create_sharded8.restype = vp
             L.vcm_create_sharded8.argtypes = [C.POINTER(SceneDesc8), C.c_int, C.c_float, C.c_float, C.c_int, C.c_int,
+                                              C.c_int, C.c_int]
+        if hasattr(L, "vcm_create_sharded9"):   # likewise: a SceneDesc9 then raises
+            L.vcm_create_sharded9.restype = vp
+            L.vcm_create_sharded9.argtypes = [C.POINTER(SceneDesc9), C.c_int, C.c_float, C.c_float, C.c_int, C.c_int,
                                               C.c_int, C.c_int]
         L.vcm_destroy.argtypes = [vp]
         L.vcm_destroy.restype = None
@@ -409,7 +413,8 @@ class HipBackend:
         self.resx = int(scene.camera.resolution[0])
         self.resy = int(scene.camera.resolution[1])
         self.N = self.resx * self.resy
-        create = (self.L.vcm_create_sharded8 if isinstance(scene, SceneDesc8) else
+        create = (self.L.vcm_create_sharded9 if isinstance(scene, SceneDesc9) else
+                  self.L.vcm_create_sharded8 if isinstance(scene, SceneDesc8) else
                   self.L.vcm_create_sharded7 if isinstance(scene, SceneDesc7) else
                   self.L.vcm_create_sharded6 if isinstance(scene, SceneDesc6) else
                   self.L.vcm_create_sharded5 if isinstance(scene, SceneDesc5) else

@@ -16,7 +16,7 @@ import math
 import numpy as np
 
 from ._abi import (Camera, EnvMap, Light, LightPick, Material, Prim, SceneDesc2, SceneDesc3, SceneDesc4, SceneDesc5, SceneDesc6, ThinLens,
-                   PixelFilter, SAMPLERS, with_sampler, with_material_ext, FILTER_BOX, FILTER_MAX_RADIUS, LIGHT_PICK_CUSTOM, LIGHT_PICK_MODES, PIXEL_FILTERS)
+                   PixelFilter, SAMPLERS, with_sampler, with_material_ext, with_projection, PROJECTIONS, PROJ_FISHEYE, FILTER_BOX, FILTER_MAX_RADIUS, LIGHT_PICK_CUSTOM, LIGHT_PICK_MODES, PIXEL_FILTERS)
 
 
 def _f3(v):
@@ -60,6 +60,7 @@ class SceneBuilder:
         self.filter = None
         self.sampler_kind = None
         self.material_ext = []
+        self.camera_model = None
 
     # ---- materials (materials.hxx:33-65) ----
     def material(self, diffuse=(0, 0, 0), phong=(0, 0, 0), exponent=1.0, mirror=(0, 0, 0), ior=-1.0, ggx=(0, 0, 0), alpha=1.0):
@@ -207,6 +208,20 @@ class SceneBuilder:
             raise ValueError("sampler: kind must be 'sobol' or 'philox'")
         self.sampler_kind = kind
 
+    # ---- the camera's projection ----
+    def projection(self, kind, fov_degrees=0.0):
+        """the camera's projection (include/smallvcm_amd.h vcm_camera_model): "perspective" (the pinhole, the default),
+        "fisheye" (equidistant; fov_degrees finite and in (0, 360), measured across the image width) or "panorama"
+        (equirectangular, 360 x 180 degrees).  The two angular projections keep the camera's position, forward axis and
+        raster axes and ignore build()'s fov_deg; a thin lens goes with "perspective" only.  build() then returns a
+        SceneDesc9."""
+        if kind not in PROJECTIONS:
+            raise ValueError("projection: kind must be 'perspective', 'fisheye' or 'panorama'")
+        f = float(fov_degrees)
+        if PROJECTIONS[kind] == PROJ_FISHEYE and not (math.isfinite(f) and 0.0 < f < 360.0):
+            raise ValueError("projection: a fisheye's fov_degrees must be finite and in (0, 360)")
+        self.camera_model = (kind, f if PROJECTIONS[kind] == PROJ_FISHEYE else 0.0)
+
     # ---- the description ----
     def build(self, position, forward, up, fov_deg, resx, resy):
         d = self._build6(position, forward, up, fov_deg, resx, resy)
@@ -214,6 +229,8 @@ class SceneBuilder:
             d = with_sampler(d, self.sampler_kind)
         if any(e[0] != 0.0 or e[1] != 0.0 or e[2] != 0.0 for e in self.material_ext):
             d = with_material_ext(d, self.material_ext)
+        if self.camera_model is not None:
+            d = with_projection(d, *self.camera_model)
         return d
 
     def _build6(self, position, forward, up, fov_deg, resx, resy):

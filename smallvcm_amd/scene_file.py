@@ -2,8 +2,8 @@
 SceneDesc3 when the file names an environment map (`light envmap <file> <scale>`), SceneDesc4 when it names a thin
 lens (`lens <apertureRadius> <focusDistance>`), SceneDesc5 when it says how lights are chosen (`lightpick
 uniform|power [uniformMix]`), SceneDesc6 when it names a pixel filter (`filter tent|bspline <radius>`), SceneDesc7
-when it names a sampler (`sampler sobol|philox`), or SceneDesc8 when a material in use has a `Pr` line in its `.mtl`
-(a GGX lobe).
+when it names a sampler (`sampler sobol|philox`), SceneDesc8 when a material in use has a `Pr` line in its `.mtl`
+(a GGX lobe), or SceneDesc9 when it names a projection (`projection fisheye <fovDeg>|panorama`).
 The parsing happens in the library (smallvcm_amd/csrc/scene_file.cpp documents the format); this is the ctypes binding.
 
     scene = load_scene("tests/scenes/bumpy_room.vcmscene", 1024, 1024)
@@ -11,7 +11,7 @@ The parsing happens in the library (smallvcm_amd/csrc/scene_file.cpp documents t
 """
 import ctypes as C
 
-from ._abi import SceneDesc2, SceneDesc3, SceneDesc4, SceneDesc5, SceneDesc6, SceneDesc7, SceneDesc8
+from ._abi import SceneDesc2, SceneDesc3, SceneDesc4, SceneDesc5, SceneDesc6, SceneDesc7, SceneDesc8, SceneDesc9
 
 
 class _Handle:
@@ -26,7 +26,8 @@ class _Handle:
 
 def load_scene(path, resx, resy):
     """-> SceneDesc2, SceneDesc3 with an env map, SceneDesc4 with a lens, SceneDesc5 with a `lightpick` directive,
-    SceneDesc6 with a `filter` directive, SceneDesc7 with a `sampler` directive, or SceneDesc8 with a `Pr` material (the
+    SceneDesc6 with a `filter` directive, SceneDesc7 with a `sampler` directive, SceneDesc8 with a `Pr` material, or
+    SceneDesc9 with a `projection` directive (the
     arrays it points to live as long as the returned object)"""
     from .renderer import load_library
     L = load_library(require_gpu=False)
@@ -46,6 +47,8 @@ def load_scene(path, resx, resy):
     L.vcm_scene_file_desc7.argtypes = [C.c_void_p]
     L.vcm_scene_file_desc8.restype = C.POINTER(SceneDesc8)
     L.vcm_scene_file_desc8.argtypes = [C.c_void_p]
+    L.vcm_scene_file_desc9.restype = C.POINTER(SceneDesc9)
+    L.vcm_scene_file_desc9.argtypes = [C.c_void_p]
     L.vcm_scene_file_free.argtypes = [C.c_void_p]
     L.vcm_scene_file_free.restype = None
     L.vcm_scene_load_error.restype = C.c_char_p
@@ -58,7 +61,10 @@ def load_scene(path, resx, resy):
     d6 = L.vcm_scene_file_desc6(h).contents
     d7 = L.vcm_scene_file_desc7(h).contents
     d8 = L.vcm_scene_file_desc8(h).contents
-    if d8.materialExt:
+    d9 = L.vcm_scene_file_desc9(h).contents
+    if d9.model:
+        d = SceneDesc9.from_buffer_copy(d9)   # the struct (pointers into the handle's arrays and settings, the camera model among them)
+    elif d8.materialExt:
         d = SceneDesc8.from_buffer_copy(d8)   # the struct (pointers into the handle's arrays and settings, the ext table among them)
     elif d7.sampler:
         d = SceneDesc7.from_buffer_copy(d7)   # the struct (pointers into the handle's arrays, map, lens, pick, filter and sampler)
