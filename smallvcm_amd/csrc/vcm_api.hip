@@ -186,8 +186,8 @@ struct vcm_ctx : Scratch {
     bool pick;                        /* lights are chosen from a table: the WithPick kernels */
     bool lights;                      /* the scene holds a spot or a sphere light: WithLights over WithPick (then pick is set) */
     bool sobol;                       /* the scene asks for the Sobol sampler: the WithSobol kind of every kernel that draws */
-    bool ggx;                         /* some material has a GGX lobe: the WithGgx kind of every kernel that handles a BSDF, the _ggx twins of
-                                         the grid kernels, and k_merge_pairs_ggx / k_merge_walk_ggx as K4 */
+    bool ggx;                         /* some material has a GGX lobe: the WithGgx kind of every kernel that handles a BSDF, WithGgx<DScene> in
+                                         the grid kernels that take a scene type, and the GGX forms of k_merge_pairs / k_merge_walk as K4 */
     bool intPhong;                    /* every Phong exponent in use is an integer in [1, 65536]: the kernels whose pow is the binary
                                          exponentiation alone (detmath.h); otherwise the SceneList / SceneBvhG kernels and the general merge */
     /* feature buffers and denoiser (vcm_denoise.h): allocated by the first vcm_render_features / vcm_denoise */
@@ -233,12 +233,10 @@ template <unsigned Wrap, class F> static void launch_kind(const vcm_ctx *c, F &&
 typedef void (*MergeKernel)(const DScene *, IterParams, GridStore, VertexStore, const int *, const int *, unsigned long long *, int, StampArgs);
 static MergeKernel merge_kernel(int mergeKind, bool intPhong, bool ggx)
 {
-    if (ggx) {
-        if (mergeKind == VCM_MERGE_PAIRS) return intPhong ? k_merge_pairs_ggx<true> : k_merge_pairs_ggx<false>;
-        return intPhong ? k_merge_walk_ggx<true> : k_merge_walk_ggx<false>;
-    }
-    if (mergeKind == VCM_MERGE_PAIRS) return intPhong ? k_merge_pairs<true> : k_merge_pairs<false>;
-    return intPhong ? k_merge_walk<true> : k_merge_walk<false>;
+    static const MergeKernel table[2][2][2] = {   /* [pairs][intPhong][ggx] */
+        { { k_merge_walk<false, false>, k_merge_walk<false, true> }, { k_merge_walk<true, false>, k_merge_walk<true, true> } },
+        { { k_merge_pairs<false, false>, k_merge_pairs<false, true> }, { k_merge_pairs<true, false>, k_merge_pairs<true, true> } } };
+    return table[mergeKind == VCM_MERGE_PAIRS][intPhong][ggx];
 }
 
 static int use_device(vcm_ctx *c) { HIPCHK(hipSetDevice(c->device)); return 0; }
@@ -1412,7 +1410,7 @@ static int vcm_trace_light_impl(vcm_ctx *c)
            also publishes the counts and the box K1 kept (k_set_counts / k_bbox_finalize folded in). */
         c->recordsValid = c->useVM && c->world > 1 && !c->sortedExchange;   /* (vcm_export_light_records still materialises them on demand) */
         const bool fold = c->world == 1;
-        hipLaunchKernelGGL((c->ggx ? k_compact_records_ggx : k_compact_records), dim3(aux_blocks(c->nLocal)), dim3(256), 0, c->stream, (const DScene *)c->dScene, c->P, c->store, c->dPathStart,
+        hipLaunchKernelGGL((c->ggx ? k_compact_records<WithGgx<DScene>> : k_compact_records<DScene>), dim3(aux_blocks(c->nLocal)), dim3(256), 0, c->stream, (const DScene *)c->dScene, c->P, c->store, c->dPathStart,
                            c->dRecordsLocal, c->dSlotOfVertex, c->recordsValid ? 1 : 0, fold ? c->dHdr : (GridHeader *)NULL,
                            (const int *)c->dLocalTotal, (fold && c->bboxFromLight) ? 1 : 0);
         HIPCHK(hipGetLastError());
@@ -1435,7 +1433,7 @@ static int vcm_trace_light_impl(vcm_ctx *c)
 static int ensure_records(vcm_ctx *c)
 {
     if (c->recordsValid || !c->useVM) return 0;
-    hipLaunchKernelGGL((c->ggx ? k_compact_records_ggx : k_compact_records), dim3(aux_blocks(c->nLocal)), dim3(256), 0, c->stream, (const DScene *)c->dScene, c->P, c->store, c->dPathStart,
+    hipLaunchKernelGGL((c->ggx ? k_compact_records<WithGgx<DScene>> : k_compact_records<DScene>), dim3(aux_blocks(c->nLocal)), dim3(256), 0, c->stream, (const DScene *)c->dScene, c->P, c->store, c->dPathStart,
                        c->dRecordsLocal, c->dSlotOfVertex, 1, (GridHeader *)NULL, (const int *)c->dLocalTotal, 0);
     HIPCHK(hipGetLastError());
     c->recordsValid = true;
@@ -1635,7 +1633,7 @@ static int vcm_sort_light_records_impl(vcm_ctx *c, void *dstDev, long long strid
                            (const int *)c->dCellStart, recs.records ? (const int *)NULL : (const int *)c->dSlotOfVertex, c->dUnsorted);
     }
     uint32_t *slab = (uint32_t *)dstDev;
-    hipLaunchKernelGGL((c->ggx ? k_cell_rank_pack_ggx : k_cell_rank_pack), g, b, 0, c->stream, (const DScene *)c->dScene, (const GridHeader *)c->dHdr, recs, (const int *)c->dCellStart,
+    hipLaunchKernelGGL((c->ggx ? k_cell_rank_pack<WithGgx<DScene>> : k_cell_rank_pack<DScene>), g, b, 0, c->stream, (const DScene *)c->dScene, (const GridHeader *)c->dHdr, recs, (const int *)c->dCellStart,
                        (const I4 *)c->dUnsorted, sorted, slab, (int *)(slab + (size_t)strideRecords * VCM_SORTED_WORDS), nCells, K, nBlocks);
     HIPCHK(hipGetLastError());
     return 0;
@@ -1746,7 +1744,7 @@ static int vcm_build_grid_impl(vcm_ctx *c)
                                (const int *)c->dSortedIndex, (const int *)c->dCellStart,
                                recs.records ? (const int *)NULL : (const int *)c->dSlotOfVertex, c->dUnsorted);
         }
-        hipLaunchKernelGGL((c->ggx ? k_cell_rank_gather_ggx : k_cell_rank_gather), g, b, 0, q, (const DScene *)c->dScene, (const GridHeader *)c->dHdr, recs,
+        hipLaunchKernelGGL((c->ggx ? k_cell_rank_gather<WithGgx<DScene>> : k_cell_rank_gather<DScene>), g, b, 0, q, (const DScene *)c->dScene, (const GridHeader *)c->dHdr, recs,
                            (const int *)c->dCellStart, (const I4 *)c->dUnsorted, sorted, c->dGx,
                            c->dGy, c->dGz, c->dGb, c->dG1, c->dG2, c->dG3, c->dSortedIndex);
         if (mark_on(c, EV_GRID, q)) return -1;

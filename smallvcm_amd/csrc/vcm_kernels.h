@@ -563,7 +563,7 @@ __device__ __forceinline__ V3 merge_query_walk(const S &sc, const IterParams &P,
  * sorted queries per XCD drawn from eight counters with stealing -- SMALLVCM_AMD_MERGE_DEAL=slab, rounds 3-5 -- moved 19 % less HBM
  * traffic and was 1.5 % faster on the Cornell scenes and 40 % slower on a mesh with a caustic: retired in round 6,
  * profiles/archive/r05e_ab_summary.txt, r05f_ab_summary.txt.) */
-/* (the body of k_merge_walk and of its twin for scenes with GGX lobes, k_merge_walk_ggx: S = DScene or WithGgx<DScene>) */
+/* (the body of k_merge_walk: S = DScene, or WithGgx<DScene> for a scene with GGX lobes) */
 template <bool IP, class S>
 __device__ __forceinline__ void merge_walk_body(const DScene *__restrict__ scp, const IterParams &P, const GridStore &g, const VertexStore &vs,
                                                 const int *__restrict__ sortedVertex, const int *__restrict__ nSorted, unsigned long long *gstats, int chunk)
@@ -601,22 +601,14 @@ __device__ __forceinline__ void merge_walk_body(const DScene *__restrict__ scp, 
     flush_stats(ls, gstats);
 #endif
 }
-template <bool IP>
+/* GGX: K4 of a scene with GGX lobes (vcm_core.h WithGgx): MergeEval carries the lobe's per-query part */
+template <bool IP, bool GGX>
 __global__ void __launch_bounds__(VCM_MERGE_BLOCK) VCM_K4_ATTR
 k_merge_walk(const DScene *__restrict__ scp, IterParams P, GridStore g, VertexStore vs,
              const int *__restrict__ sortedVertex, const int *__restrict__ nSorted, unsigned long long *gstats, int chunk, StampArgs st)
 {
     stamp_entry(st);
-    merge_walk_body<IP, DScene>(scp, P, g, vs, sortedVertex, nSorted, gstats, chunk);
-}
-/* K4 of a scene with GGX lobes (vcm_core.h WithGgx): MergeEval carries the lobe's per-query part */
-template <bool IP>
-__global__ void __launch_bounds__(VCM_MERGE_BLOCK) VCM_K4_ATTR
-k_merge_walk_ggx(const DScene *__restrict__ scp, IterParams P, GridStore g, VertexStore vs,
-                 const int *__restrict__ sortedVertex, const int *__restrict__ nSorted, unsigned long long *gstats, int chunk, StampArgs st)
-{
-    stamp_entry(st);
-    merge_walk_body<IP, WithGgx<DScene>>(scp, P, g, vs, sortedVertex, nSorted, gstats, chunk);
+    merge_walk_body<IP, std::conditional_t<GGX, WithGgx<DScene>, DScene>>(scp, P, g, vs, sortedVertex, nSorted, gstats, chunk);
 }
 
 #if defined(VCM_K4_TIMES)
@@ -781,7 +773,7 @@ __device__ __forceinline__ void merge_pairs_issue(const GridStore &g, const Pair
 }
 /* RangeQuery::Process (vertexcm.hxx:130-169) for the pair of every lane: merge_eval_setup + merge_eval_photon (vcm_core.h)
    statement by statement, the query's side out of its LDS row; then the terms to the accumulators, round by round */
-/* GGX (k_merge_pairs_ggx, a scene with GGX lobes): the query's row holds mGgxProb where the other form keeps the reverse
+/* GGX (k_merge_pairs<IP, true>, a scene with GGX lobes): the query's row holds mGgxProb where the other form keeps the reverse
    pdf of the diffuse lobe (recomputed here from diffProb and ldf.z: the same two operations on the same values), rows 3 and
    4 are written for a lobe as for Phong, and F0 and alpha come from `ext`, the scene's table in global memory (the LDS
    of this kernel is full: four workgroups per CU); then bsdf_eval_ggx's operations through ggx_eval_core.  ext is not
@@ -923,9 +915,10 @@ __device__ __forceinline__ void merge_pairs_push(const IterParams &P, const Grid
 #undef VCM_PAIR_COLUMN
 #endif
 
-/* (TWIN: k_merge_pairs_ggx below repeats this kernel for scenes with GGX lobes -- a change here belongs there too.  The two
-   are separate texts so that this one's code stays what it was: the resource report is the gate.) */
-template <bool IP>
+/* GGX: K4 of a scene with GGX lobes, over WithGgx<DScene>: mGgxProb in the query's row, rows 3 and 4 for a lobe as for Phong,
+   and the lobe evaluated by merge_pairs_eval<IP, true> (its comment has the layout).  The text stands in the kernel itself,
+   not in a body function that the forms call: so every form's code is what its own text gave (DESIGN.md "Microfacet materials", Kinds). */
+template <bool IP, bool GGX>
 __global__ void __launch_bounds__(VCM_MERGE_BLOCK) VCM_K4_ATTR
 k_merge_pairs(const DScene *__restrict__ scp, IterParams P, GridStore g, VertexStore vs,
               const int *__restrict__ sortedVertex, const int *__restrict__ nSorted, unsigned long long *gstats, int chunk, StampArgs st)
@@ -935,7 +928,10 @@ k_merge_pairs(const DScene *__restrict__ scp, IterParams P, GridStore g, VertexS
 #if defined(VCM_K4_TIMES)   /* measurement variant: when every workgroup of the launch started and ended (profiles/tools/k4_tail.py) */
     if (threadIdx.x == 0 && blockIdx.x < 32768) g_k4Times[2 * blockIdx.x] = wall_clock64();
 #endif
-    const DScene &sc = *scp;
+    using S = std::conditional_t<GGX, WithGgx<DScene>, DScene>;
+    const S &sc = *static_cast<const S *>(scp);
+    const vcm_material_ext *ext = 0;
+    if constexpr (GGX) ext = sc.materialExt();
     const int nQ = *nSorted;
     __shared__ __attribute__((aligned(16))) PairLds L;
     const int tid = (int)threadIdx.x, lane = tid & 63, waveBase = tid & ~63;
@@ -980,9 +976,10 @@ k_merge_pairs(const DScene *__restrict__ scp, IterParams P, GridStore g, VertexS
             r.x = bsdf.diffProb; r.y = bsdf.phongProb; r.z = bsdf.contProb; r.w = bq.w; row[1] = r;   /* bq.w: pathLength | matID << 8 */
             r.x = c.w * P.misVcWeightFactor;                                              /* vertexcm.hxx:160 */
             r.y = d.w;
-            r.z = bsdf.diffProb * smax(0.f, bsdf.localDirFix.z * VCM_INV_PI_F);           /* bsdf.hxx:408 */
+            r.z = GGX ? bsdf.ggxProb   /* (merge_pairs_eval<IP, true> recomputes bsdf.hxx:408) */
+                      : bsdf.diffProb * smax(0.f, bsdf.localDirFix.z * VCM_INV_PI_F);     /* bsdf.hxx:408 */
             r.w = u2f(0xffffffffu); row[2] = r;   /* seqMin (merge_pairs_eval) */
-            if (bsdf.phongProb != 0.f) {
+            if (bsdf.phongProb != 0.f || (GGX && bsdf.ggxProb != 0.f)) {
                 r.x = bsdf.frame.mX.x; r.y = bsdf.frame.mX.y; r.z = bsdf.frame.mX.z; r.w = bsdf.localDirFix.x; row[3] = r;
                 r.x = bsdf.frame.mY.x; r.y = bsdf.frame.mY.y; r.z = bsdf.frame.mY.z; r.w = bsdf.localDirFix.y; row[4] = r;
             }
@@ -1034,7 +1031,7 @@ k_merge_pairs(const DScene *__restrict__ scp, IterParams P, GridStore g, VertexS
             }                                                                                                                  \
             VCM_PAIR_LOAD(SX, SY, SZ, VCM_PAIR_AHEAD.lo)                                                                       \
             K4R_DIST(d0, d1, d2, d3)                                                                                           \
-            merge_pairs_push<IP, false>(P, g, L, ring, lane, waveBase, it0.lo, it0.hi, d0, d1, d2, d3, head, cnt, metaCur, inflight, pb, waveAccepted, (const vcm_material_ext *)0 K4R_ARG); \
+            merge_pairs_push<IP, GGX>(P, g, L, ring, lane, waveBase, it0.lo, it0.hi, d0, d1, d2, d3, head, cnt, metaCur, inflight, pb, waveAccepted, ext K4R_ARG); \
             VCM_PAIR_SHIFT                                                                                                     \
             K4R(6)                                                                                                             \
         }
@@ -1048,160 +1045,10 @@ k_merge_pairs(const DScene *__restrict__ scp, IterParams P, GridStore g, VertexS
 #undef VCM_PAIR_LOAD
 #undef VCM_PAIR_AHEAD
 #undef VCM_PAIR_SHIFT
-        if (inflight) merge_pairs_eval<IP, false>(P, L, waveBase, pb, (const vcm_material_ext *)0 K4R_ARG);
+        if (inflight) merge_pairs_eval<IP, GGX>(P, L, waveBase, pb, ext K4R_ARG);
         while (cnt > 0) {
             merge_pairs_issue(g, ring, lane, head, cnt, pb K4R_ARG);
-            merge_pairs_eval<IP, false>(P, L, waveBase, pb, (const vcm_material_ext *)0 K4R_ARG);
-        }
-        if (q < nQ) {
-            const V3 contrib = mk3(L.acc[tid], L.acc[VCM_MERGE_BLOCK + tid], L.acc[2 * VCM_MERGE_BLOCK + tid]);
-            const V3 v = thr * P.vmNormalization * contrib;
-            vs.mergeOut[ps] = mk4(v.x, v.y, v.z, 0.f);
-        }
-        K4R(7)
-    }
-#if defined(VCM_K4_REGIONS)
-    if (lane == 0) for (int i = 0; i < 8; i++) atomicAdd(&g_k4Regions[i], k4r.c[i]);
-#endif
-    if (lane == 0) ls.mergeAccepted = waveAccepted;
-    flush_stats(ls, gstats);
-#if defined(VCM_K4_TIMES)
-    __syncthreads();
-    if (threadIdx.x == 0 && blockIdx.x < 32768) g_k4Times[2 * blockIdx.x + 1] = wall_clock64();
-#endif
-#endif
-}
-
-/* K4 of a scene with GGX lobes: k_merge_pairs (TWIN: a change there belongs here too) over WithGgx<DScene>, with mGgxProb in
-   the query's row and the lobe evaluated by merge_pairs_eval<IP, true> */
-template <bool IP>
-__global__ void __launch_bounds__(VCM_MERGE_BLOCK) VCM_K4_ATTR
-k_merge_pairs_ggx(const DScene *__restrict__ scp, IterParams P, GridStore g, VertexStore vs,
-              const int *__restrict__ sortedVertex, const int *__restrict__ nSorted, unsigned long long *gstats, int chunk, StampArgs st)
-{
-    stamp_entry(st);
-#if defined(__HIP_DEVICE_COMPILE__)
-#if defined(VCM_K4_TIMES)   /* measurement variant: when every workgroup of the launch started and ended (profiles/tools/k4_tail.py) */
-    if (threadIdx.x == 0 && blockIdx.x < 32768) g_k4Times[2 * blockIdx.x] = wall_clock64();
-#endif
-    const WithGgx<DScene> &sc = *static_cast<const WithGgx<DScene> *>(scp);
-    const vcm_material_ext *ext = sc.materialExt();
-    const int nQ = *nSorted;
-    __shared__ __attribute__((aligned(16))) PairLds L;
-    const int tid = (int)threadIdx.x, lane = tid & 63, waveBase = tid & ~63;
-    PairEntry *ring = L.ring + (tid >> 6) * VCM_PAIR_RING;
-    for (int m = tid; m < sc.nMaterials && m < VCM_PAIR_MATERIALS; m += VCM_MERGE_BLOCK) {
-        const vcm_material mm = scene_material(sc, m, false);
-        const V3 dv = ld3(mm.diffuse) * VCM_INV_PI_F;                                    /* bsdf.hxx:411 */
-        const V3 rho = ld3(mm.phong) * (mm.phongExp + 2.f) * 0.5f * VCM_INV_PI_F;       /* :442-443 */
-        vcm_f4 a, b;
-        a.x = dv.x; a.y = dv.y; a.z = dv.z; a.w = mm.phongExp;
-        b.x = rho.x; b.y = rho.y; b.z = rho.z; b.w = 0.f;
-        L.mat[m * 2] = a; L.mat[m * 2 + 1] = b;
-    }
-    __syncthreads();   /* the only barrier: from here on a wave touches its own quarter of the LDS */
-    LaneStats ls; lane_stats_zero(ls);
-    uint32_t waveAccepted = 0;   /* wave-uniform */
-#if defined(VCM_K4_REGIONS)
-    K4Regions k4r;
-    for (int i = 0; i < 8; i++) k4r.c[i] = 0ull;
-    k4r.t = clock64();
-#endif
-    const int nBatches = (nQ + VCM_MERGE_BLOCK - 1) / VCM_MERGE_BLOCK;
-    const int xcd = blockIdx.x & 7, wgOfXcd = blockIdx.x >> 3, wgPerXcd = gridDim.x >> 3;
-    for (int t = wgOfXcd;; t += wgPerXcd) {   /* k_merge_walk's static dealing: chunks of batches round-robin over the XCDs */
-        const int bt = ((t / chunk) * 8 + xcd) * chunk + (t % chunk);
-        if ((t / chunk) * 8 * chunk >= nBatches) break;
-        if (bt >= nBatches) continue;
-        const int q = bt * VCM_MERGE_BLOCK + tid;
-        V3 qp = sp3(0.f), thr = sp3(0.f);
-        size_t ps = 0;
-        int n = 0;
-        uint32_t probes = 0u;
-        if (q < nQ) {
-            const int vi = sortedVertex[q];
-            const F4 a = vq(vs, 0, vi), bq = vq(vs, 1, vi), c = vq(vs, 2, vi), d = vq(vs, 3, vi);
-            ps = merge_out_slot(P, f2u(bq.w) & 0xffu, f2u(a.w), vi);
-            Bsdf bsdf;
-            bsdf_restore(bsdf, mk3(bq.x, bq.y, bq.z), mk3(c.x, c.y, c.z), f2u(bq.w) >> 8, sc, false);
-            vcm_f4 r;
-            vcm_f4 *row = L.row + tid * VCM_PAIR_ROW;
-            r.x = bsdf.frame.mZ.x; r.y = bsdf.frame.mZ.y; r.z = bsdf.frame.mZ.z; r.w = bsdf.localDirFix.z; row[0] = r;
-            r.x = bsdf.diffProb; r.y = bsdf.phongProb; r.z = bsdf.contProb; r.w = bq.w; row[1] = r;   /* bq.w: pathLength | matID << 8 */
-            r.x = c.w * P.misVcWeightFactor;                                              /* vertexcm.hxx:160 */
-            r.y = d.w;
-            r.z = bsdf.ggxProb;                                                           /* (merge_pairs_eval<IP, true> recomputes bsdf.hxx:408) */
-            r.w = u2f(0xffffffffu); row[2] = r;   /* seqMin (merge_pairs_eval) */
-            if (bsdf.phongProb != 0.f || bsdf.ggxProb != 0.f) {
-                r.x = bsdf.frame.mX.x; r.y = bsdf.frame.mX.y; r.z = bsdf.frame.mX.z; r.w = bsdf.localDirFix.x; row[3] = r;
-                r.x = bsdf.frame.mY.x; r.y = bsdf.frame.mY.y; r.z = bsdf.frame.mY.z; r.w = bsdf.localDirFix.y; row[4] = r;
-            }
-            qp = mk3(a.x, a.y, a.z); thr = mk3(d.x, d.y, d.z);
-            int total;
-            n = merge_pairs_runs(P, g, qp, L, tid, total, probes);
-            ls.mergeCandidates += (uint32_t)total;
-#if defined(VCM_K4_STEPS)
-            if (q < (1 << 24)) {
-                int steps = 0;
-                for (int k = 0; k < n; k++) steps += ((L.runLo[k * VCM_MERGE_BLOCK + tid] & 3) + (int)L.runLen[k * VCM_MERGE_BLOCK + tid] + 3) >> 2;
-                g_k4Steps[q] = (unsigned short)(steps < 65535 ? steps : 65535);
-            }
-#endif
-        }
-        L.acc[tid] = 0.f; L.acc[VCM_MERGE_BLOCK + tid] = 0.f; L.acc[2 * VCM_MERGE_BLOCK + tid] = 0.f;
-        /* ---- scan (merge_query_walk's) with the accepted pairs to the wave's ring.  The candidates of a step are loaded TWO
-           steps ahead (k_merge_walk: one): the kernel waits for memory, not for issue slots -- three workgroups per CU instead
-           of four cost it 16 % (profiles/r13i) -- and the two register sets that hold a step's candidates serve: a set is
-           free the moment its distances are formed, and takes the candidates of the step after next. */
-        const f2 qx = f2_sp(qp.x), qy = f2_sp(qp.y), qz = f2_sp(qp.z);
-        int head = 0, cnt = 0;
-        uint32_t metaCur = (uint32_t)lane;   /* the next entry's meta: lane | the pairs this lane has pushed << 6 */
-        bool inflight = false;
-        PairBatch pb;
-        pb.valid = false; pb.meta = 0u;
-        PairPos it0 = merge_pairs_first(L, tid, n), it1 = merge_pairs_next(P, g, L, tid, n, qp, probes, it0), it2 = merge_pairs_next(P, g, L, tid, n, qp, probes, it1);
-#define VCM_PAIR_LOAD(SX, SY, SZ, at) { const vcm_f4 *blk = (const vcm_f4 *)(g.gb + (size_t)((at) >> 2) * 12u); SX = blk[0]; SY = blk[1]; SZ = blk[2]; }
-        vcm_f4 AX, AY, AZ, BX, BY, BZ;
-        VCM_PAIR_LOAD(AX, AY, AZ, it0.lo)
-        VCM_PAIR_LOAD(BX, BY, BZ, it1.lo)
-        K4R(0)
-#define VCM_PAIR_AHEAD it2
-#define VCM_PAIR_SHIFT it0 = it1; it1 = it2; it2 = merge_pairs_next(P, g, L, tid, n, qp, probes, it2);
-#if defined(VCM_K4_REGIONS)   /* (the distances must exist before the mark: they wait for the step's loads) */
-#define K4R_DIST(a, b, c, d) { asm volatile("" :: "v"(a), "v"(b), "v"(c), "v"(d)); K4R(1) }
-#else
-#define K4R_DIST(a, b, c, d)
-#endif
-#define VCM_PAIR_STEP(SX, SY, SZ)                                                                                              \
-        {                                                                                                                      \
-            float d0, d1, d2, d3;                                                                                              \
-            {   /* LenSqr(query - position), hashgrid.hxx:162, math.hxx:107: two candidates per packed operation */          \
-                const f2 dxa = qx - SX.xy, dya = qy - SY.xy, dza = qz - SZ.xy;                                                 \
-                const f2 dxb = qx - SX.zw, dyb = qy - SY.zw, dzb = qz - SZ.zw;                                                 \
-                const f2 da = dxa * dxa + dya * dya + dza * dza;                                                               \
-                const f2 db = dxb * dxb + dyb * dyb + dzb * dzb;                                                               \
-                d0 = da.x; d1 = da.y; d2 = db.x; d3 = db.y;                                                                    \
-            }                                                                                                                  \
-            VCM_PAIR_LOAD(SX, SY, SZ, VCM_PAIR_AHEAD.lo)                                                                       \
-            K4R_DIST(d0, d1, d2, d3)                                                                                           \
-            merge_pairs_push<IP, true>(P, g, L, ring, lane, waveBase, it0.lo, it0.hi, d0, d1, d2, d3, head, cnt, metaCur, inflight, pb, waveAccepted, ext K4R_ARG); \
-            VCM_PAIR_SHIFT                                                                                                     \
-            K4R(6)                                                                                                             \
-        }
-        for (;;) {
-            if (!wave_any(it0.lo < it0.hi)) break;
-            VCM_PAIR_STEP(AX, AY, AZ)
-            if (!wave_any(it0.lo < it0.hi)) break;
-            VCM_PAIR_STEP(BX, BY, BZ)
-        }
-#undef VCM_PAIR_STEP
-#undef VCM_PAIR_LOAD
-#undef VCM_PAIR_AHEAD
-#undef VCM_PAIR_SHIFT
-        if (inflight) merge_pairs_eval<IP, true>(P, L, waveBase, pb, ext K4R_ARG);
-        while (cnt > 0) {
-            merge_pairs_issue(g, ring, lane, head, cnt, pb K4R_ARG);
-            merge_pairs_eval<IP, true>(P, L, waveBase, pb, ext K4R_ARG);
+            merge_pairs_eval<IP, GGX>(P, L, waveBase, pb, ext K4R_ARG);
         }
         if (q < nQ) {
             const V3 contrib = mk3(L.acc[tid], L.acc[VCM_MERGE_BLOCK + tid], L.acc[2 * VCM_MERGE_BLOCK + tid]);
@@ -1480,12 +1327,12 @@ __device__ __forceinline__ void bbox_finalize_component(GridHeader *hdr, int c, 
 }
 /* hdr != NULL (single rank): the first block also publishes the vertex counts (what k_set_counts does) and, with
    finalizeBox, turns the box K1 accumulated into floats -- two one-lane launches less per iteration */
-/* (k_compact_records below, once more as a function of the scene's type: the body of k_compact_records_ggx, the twin for
-   scenes with GGX lobes -- the continuation probability of a stored vertex depends on the lobe.  The kernel itself keeps
-   its own text, so that its code stays what it was.) */
+/* S = DScene, or WithGgx<DScene> for a scene with GGX lobes: the continuation probability of a stored vertex depends on the
+   lobe.  (As in k_merge_pairs the text stands in the kernel, not in an inlined body: there the workgroup's size is loaded by
+   the longer sequence for partial workgroups, which cost each of these kernels a VGPR -- DESIGN.md "Microfacet materials", Kinds.) */
 template <class S>
-__device__ __forceinline__ void compact_records_body(const DScene *__restrict__ scp, const IterParams &P, const LightStore &store, const int *__restrict__ pathStart,
-                                                     float *records, int *slotOfVertex, int writeRecords, GridHeader *hdr, const int *localTotal, int finalizeBox)
+__global__ void __launch_bounds__(256) k_compact_records(const DScene *__restrict__ scp, IterParams P, LightStore store, const int *__restrict__ pathStart,
+                                  float *records, int *slotOfVertex, int writeRecords, GridHeader *hdr, const int *localTotal, int finalizeBox)
 {
     if (hdr && blockIdx.x == 0 && threadIdx.x < 3) {
         const int n = *localTotal;
@@ -1511,40 +1358,6 @@ __device__ __forceinline__ void compact_records_body(const DScene *__restrict__ 
             r[12] = u2f(f2u(a.w) & 0xffu);
         }
     }
-}
-/* (TWIN: compact_records_body repeats this body for k_compact_records_ggx -- a change here belongs there too) */
-__global__ void __launch_bounds__(256) k_compact_records(const DScene *__restrict__ scp, IterParams P, LightStore store, const int *__restrict__ pathStart,
-                                  float *records, int *slotOfVertex, int writeRecords, GridHeader *hdr, const int *localTotal, int finalizeBox)
-{
-    if (hdr && blockIdx.x == 0 && threadIdx.x < 3) {
-        const int n = *localTotal;
-        if (threadIdx.x == 0) { hdr->nLocalRecords = n; hdr->nRecords = n; }
-        if (finalizeBox) bbox_finalize_component(hdr, (int)threadIdx.x, n, 1);
-    }
-    /* one lane per light path: slot reads are coalesced across the wave for every j (slot-major store) */
-    for (int lp = blockIdx.x * blockDim.x + threadIdx.x; lp < P.nLocal; lp += gridDim.x * blockDim.x) {
-        const int n = (int)store.count[lp];
-        const int base = pathStart[lp];
-        for (int j = 0; j < n; j++) {
-            const size_t slot = (size_t)j * (size_t)P.nLocal + (size_t)lp;
-            const int vtx = base + j;
-            slotOfVertex[vtx] = (int)slot;   /* dense vertex list for k_connect_camera */
-            if (!writeRecords) continue;
-            const F4 a = lv(store, slot, 0), b = lv(store, slot, 1), d = lv(store, slot, 3);
-            const F4 e = light_vertex_wdir_contprob(*scp, a, lv(store, slot, 2), d, false);
-            float *r = records + (size_t)vtx * VCM_MERGE_RECORD_FLOATS;
-            r[0] = a.x; r[1] = a.y; r[2] = a.z;
-            r[3] = e.x; r[4] = e.y; r[5] = e.z;
-            r[6] = b.x; r[7] = b.y; r[8] = b.z;
-            r[9] = b.w; r[10] = d.w; r[11] = e.w;
-            r[12] = u2f(f2u(a.w) & 0xffu);
-        }
-    }
-}
-__global__ void __launch_bounds__(256) k_compact_records_ggx(const DScene *__restrict__ scp, IterParams P, LightStore store, const int *__restrict__ pathStart,
-                                      float *records, int *slotOfVertex, int writeRecords, GridHeader *hdr, const int *localTotal, int finalizeBox)
-{
-    compact_records_body<WithGgx<DScene>>(scp, P, store, pathStart, records, slotOfVertex, writeRecords, hdr, localTotal, finalizeBox);
 }
 
 /* ---------------- K1c: connect every stored light vertex to the camera ---- */
@@ -1988,27 +1801,34 @@ __global__ void __launch_bounds__(256) k_cell_starts(const uint32_t *__restrict_
  * cell with a smaller index; the vertex data is then written to its final
  * position, so the query reads contiguous, cell-sorted memory and needs no
  * mIndices indirection. */
-/* (the body of k_cell_rank_gather_ggx, as compact_records_body is that of k_compact_records_ggx) */
+/* the entry at `pos` of the list ({vertex, slot, ...}) and, in dst, its place in the cell-sorted order */
+__device__ __forceinline__ I4 cell_rank_entry(const int *__restrict__ cellStart, const I4 *__restrict__ unsorted, const I2 *__restrict__ sorted, int pos, int &dst)
+{
+    I4 me;
+    dst = pos;
+    if (sorted) {   /* the radix sort's list: {vertex, slot} in the grid's final order -- position = destination */
+        const I2 e = sorted[pos];
+        me.x = e.x; me.y = e.y; me.z = 0; me.w = 0;
+    } else {
+        me = unsorted[pos];
+        const int cell = me.z;
+        const int lo = cellStart[cell], hi = cellStart[cell + 1];
+        int rank = 0;
+        for (int q = lo; q < hi; q++) rank += (unsorted[q].x < me.x) ? 1 : 0;
+        dst = lo + rank;
+    }
+    return me;
+}
+/* (S, and why the text is the kernel's own: k_compact_records) */
 template <class S>
-__device__ __forceinline__ void cell_rank_gather_body(const DScene *__restrict__ scp, const GridHeader *__restrict__ hdr, const VertexSource &src,
-                                                      const int *__restrict__ cellStart, const I4 *__restrict__ unsorted, const I2 *__restrict__ sorted,
-                                                      float *gx, float *gy, float *gz, float *gb, F4 *g1, F4 *g2, F2 *g3, int *sortedIndex)
+__global__ void __launch_bounds__(256) k_cell_rank_gather(const DScene *__restrict__ scp, const GridHeader *__restrict__ hdr, VertexSource src,
+                                   const int *__restrict__ cellStart, const I4 *__restrict__ unsorted, const I2 *__restrict__ sorted,
+                                   float *gx, float *gy, float *gz, float *gb, F4 *g1, F4 *g2, F2 *g3, int *sortedIndex)
 {
     const int n = hdr->nRecords;
     for (int pos = blockIdx.x * blockDim.x + threadIdx.x; pos < n; pos += gridDim.x * blockDim.x) {
-        I4 me;
-        int dst = pos;
-        if (sorted) {   /* the radix sort's list: {vertex, slot} in the grid's final order -- position = destination */
-            const I2 e = sorted[pos];
-            me.x = e.x; me.y = e.y; me.z = 0; me.w = 0;
-        } else {
-            me = unsorted[pos];
-            const int cell = me.z;
-            const int lo = cellStart[cell], hi = cellStart[cell + 1];
-            int rank = 0;
-            for (int q = lo; q < hi; q++) rank += (unsorted[q].x < me.x) ? 1 : 0;
-            dst = lo + rank;
-        }
+        int dst;
+        const I4 me = cell_rank_entry(cellStart, unsorted, sorted, pos, dst);
         const int i = me.x;
         F2 t;
         if (src.records) {
@@ -2031,55 +1851,6 @@ __device__ __forceinline__ void cell_rank_gather_body(const DScene *__restrict__
         g3[dst] = t;
         if (sortedIndex) sortedIndex[dst] = i;
     }
-}
-/* (TWIN: cell_rank_gather_body repeats this body for k_cell_rank_gather_ggx -- a change here belongs there too) */
-__global__ void __launch_bounds__(256) k_cell_rank_gather(const DScene *__restrict__ scp, const GridHeader *__restrict__ hdr, VertexSource src,
-                                   const int *__restrict__ cellStart, const I4 *__restrict__ unsorted, const I2 *__restrict__ sorted,
-                                   float *gx, float *gy, float *gz, float *gb, F4 *g1, F4 *g2, F2 *g3, int *sortedIndex)
-{
-    const int n = hdr->nRecords;
-    for (int pos = blockIdx.x * blockDim.x + threadIdx.x; pos < n; pos += gridDim.x * blockDim.x) {
-        I4 me;
-        int dst = pos;
-        if (sorted) {   /* the radix sort's list: {vertex, slot} in the grid's final order -- position = destination */
-            const I2 e = sorted[pos];
-            me.x = e.x; me.y = e.y; me.z = 0; me.w = 0;
-        } else {
-            me = unsorted[pos];
-            const int cell = me.z;
-            const int lo = cellStart[cell], hi = cellStart[cell + 1];
-            int rank = 0;
-            for (int q = lo; q < hi; q++) rank += (unsorted[q].x < me.x) ? 1 : 0;
-            dst = lo + rank;
-        }
-        const int i = me.x;
-        F2 t;
-        if (src.records) {
-            const float *r = src.records + (size_t)i * VCM_MERGE_RECORD_FLOATS;
-            gx[dst] = r[0]; gy[dst] = r[1]; gz[dst] = r[2];
-            gb[grid_blocked_index(dst, 0)] = r[0]; gb[grid_blocked_index(dst, 1)] = r[1]; gb[grid_blocked_index(dst, 2)] = r[2];
-            g1[dst] = mk4(r[3], r[4], r[5], r[11]);
-            g2[dst] = mk4(r[6], r[7], r[8], r[9]);
-            t.x = r[10]; t.y = r[12];
-        } else {   /* the same 13 values k_compact_records would have written */
-            const size_t slot = (size_t)me.y;
-            const F4 a = lv(src.store, slot, 0), b = lv(src.store, slot, 1), d = lv(src.store, slot, 3);
-            const F4 e = light_vertex_wdir_contprob(*scp, a, lv(src.store, slot, 2), d, false);   /* (one 64-byte record: one line) */
-            gx[dst] = a.x; gy[dst] = a.y; gz[dst] = a.z;
-            gb[grid_blocked_index(dst, 0)] = a.x; gb[grid_blocked_index(dst, 1)] = a.y; gb[grid_blocked_index(dst, 2)] = a.z;
-            g1[dst] = e;
-            g2[dst] = b;
-            t.x = d.w; t.y = u2f(f2u(a.w) & 0xffu);
-        }
-        g3[dst] = t;
-        if (sortedIndex) sortedIndex[dst] = i;
-    }
-}
-__global__ void __launch_bounds__(256) k_cell_rank_gather_ggx(const DScene *__restrict__ scp, const GridHeader *__restrict__ hdr, VertexSource src,
-                                       const int *__restrict__ cellStart, const I4 *__restrict__ unsorted, const I2 *__restrict__ sorted,
-                                       float *gx, float *gy, float *gz, float *gb, F4 *g1, F4 *g2, F2 *g3, int *sortedIndex)
-{
-    cell_rank_gather_body<WithGgx<DScene>>(scp, hdr, src, cellStart, unsorted, sorted, gx, gy, gz, gb, g1, g2, g3, sortedIndex);
 }
 
 
@@ -2113,9 +1884,9 @@ inline __host__ __device__ int sorted_block_cells(int S)
 /* k_cell_rank_gather for the exchange: the vertex's 13 words go to its place in the cell-sorted SLAB (array of records),
  * and the table of block starts behind it */
 template <class S>
-__device__ __forceinline__ void cell_rank_pack_body(const DScene *__restrict__ scp, const GridHeader *__restrict__ hdr, const VertexSource &src,
-                                                    const int *__restrict__ cellStart, const I4 *__restrict__ unsorted, const I2 *__restrict__ sorted,
-                                                    uint32_t *slab, int *blockStart, int nCells, int K, int nBlocks)
+__global__ void __launch_bounds__(256) k_cell_rank_pack(const DScene *__restrict__ scp, const GridHeader *__restrict__ hdr, VertexSource src,
+                                 const int *__restrict__ cellStart, const I4 *__restrict__ unsorted, const I2 *__restrict__ sorted,
+                                 uint32_t *slab, int *blockStart, int nCells, int K, int nBlocks)
 {
     const int n = hdr->nRecords;
     for (int b = blockIdx.x * blockDim.x + threadIdx.x; b <= nBlocks; b += gridDim.x * blockDim.x) {
@@ -2123,19 +1894,8 @@ __device__ __forceinline__ void cell_rank_pack_body(const DScene *__restrict__ s
         blockStart[b] = cellStart[c < nCells ? (int)c : nCells];
     }
     for (int pos = blockIdx.x * blockDim.x + threadIdx.x; pos < n; pos += gridDim.x * blockDim.x) {
-        I4 me;
-        int dst = pos;
-        if (sorted) {
-            const I2 e = sorted[pos];
-            me.x = e.x; me.y = e.y; me.z = 0; me.w = 0;
-        } else {
-            me = unsorted[pos];
-            const int cell = me.z;
-            const int lo = cellStart[cell], hi = cellStart[cell + 1];
-            int rank = 0;
-            for (int q = lo; q < hi; q++) rank += (unsorted[q].x < me.x) ? 1 : 0;
-            dst = lo + rank;
-        }
+        int dst;
+        const I4 me = cell_rank_entry(cellStart, unsorted, sorted, pos, dst);
         const int i = me.x;
         uint32_t *r = slab + (size_t)dst * VCM_SORTED_WORDS;
         float w[13];
@@ -2154,55 +1914,6 @@ __device__ __forceinline__ void cell_rank_pack_body(const DScene *__restrict__ s
         for (int k = 0; k < 12; k++) r[k] = f2u(w[k]);
         r[12] = (f2u(w[12]) & 0xffu) | ((uint32_t)i << 8);
     }
-}
-/* (TWIN: cell_rank_pack_body repeats this body for k_cell_rank_pack_ggx -- a change here belongs there too) */
-__global__ void __launch_bounds__(256) k_cell_rank_pack(const DScene *__restrict__ scp, const GridHeader *__restrict__ hdr, VertexSource src,
-                                 const int *__restrict__ cellStart, const I4 *__restrict__ unsorted, const I2 *__restrict__ sorted,
-                                 uint32_t *slab, int *blockStart, int nCells, int K, int nBlocks)
-{
-    const int n = hdr->nRecords;
-    for (int b = blockIdx.x * blockDim.x + threadIdx.x; b <= nBlocks; b += gridDim.x * blockDim.x) {
-        const long long c = (long long)b * K;
-        blockStart[b] = cellStart[c < nCells ? (int)c : nCells];
-    }
-    for (int pos = blockIdx.x * blockDim.x + threadIdx.x; pos < n; pos += gridDim.x * blockDim.x) {
-        I4 me;
-        int dst = pos;
-        if (sorted) {
-            const I2 e = sorted[pos];
-            me.x = e.x; me.y = e.y; me.z = 0; me.w = 0;
-        } else {
-            me = unsorted[pos];
-            const int cell = me.z;
-            const int lo = cellStart[cell], hi = cellStart[cell + 1];
-            int rank = 0;
-            for (int q = lo; q < hi; q++) rank += (unsorted[q].x < me.x) ? 1 : 0;
-            dst = lo + rank;
-        }
-        const int i = me.x;
-        uint32_t *r = slab + (size_t)dst * VCM_SORTED_WORDS;
-        float w[13];
-        if (src.records) {
-            const float *q = src.records + (size_t)i * VCM_MERGE_RECORD_FLOATS;
-#pragma unroll
-            for (int k = 0; k < 13; k++) w[k] = q[k];
-        } else {
-            const size_t slot = (size_t)me.y;
-            const F4 a = lv(src.store, slot, 0), b = lv(src.store, slot, 1), d = lv(src.store, slot, 3);
-            const F4 e = light_vertex_wdir_contprob(*scp, a, lv(src.store, slot, 2), d, false);
-            w[0] = a.x; w[1] = a.y; w[2] = a.z; w[3] = e.x; w[4] = e.y; w[5] = e.z; w[6] = b.x; w[7] = b.y; w[8] = b.z;
-            w[9] = b.w; w[10] = d.w; w[11] = e.w; w[12] = u2f(f2u(a.w) & 0xffu);
-        }
-#pragma unroll
-        for (int k = 0; k < 12; k++) r[k] = f2u(w[k]);
-        r[12] = (f2u(w[12]) & 0xffu) | ((uint32_t)i << 8);
-    }
-}
-__global__ void __launch_bounds__(256) k_cell_rank_pack_ggx(const DScene *__restrict__ scp, const GridHeader *__restrict__ hdr, VertexSource src,
-                                     const int *__restrict__ cellStart, const I4 *__restrict__ unsorted, const I2 *__restrict__ sorted,
-                                     uint32_t *slab, int *blockStart, int nCells, int K, int nBlocks)
-{
-    cell_rank_pack_body<WithGgx<DScene>>(scp, hdr, src, cellStart, unsorted, sorted, slab, blockStart, nCells, K, nBlocks);
 }
 
 struct SortedSlabs {

@@ -2,7 +2,7 @@
 same device functions (tests/host_emul_ggx), bit for bit -- framebuffer, random-number tapes and workload counters --
 for every algorithm, scene kind, execution order and two image sizes; the lobe beside lens, filters, env map, spot and
 sphere lights, a pick table and the Sobol sampler; more materials than the LDS table holds; the two known-answer ops;
-the default unchanged; two shards against one context; the tracked images; the feature kernel's albedo; vcm_render on a
+the default unchanged; two shards against one context, under both exchanges; the tracked images; the feature kernel's albedo; vcm_render on a
 scene file with a `Pr` material."""
 import ctypes as C
 import os
@@ -86,8 +86,8 @@ def test_gpu_equals_host_emulation(monkeypatch, algo, kind, strict, res):
 @pytest.mark.parametrize("kind", ["rects", "list", "bvh"])
 @pytest.mark.parametrize("algo", [1, 2, 4])
 def test_both_merge_kernels_equal_the_host_emulation(monkeypatch, algo, kind, res, merge):
-    """the three merging algorithms with k_merge_walk_ggx and with k_merge_pairs_ggx (the default), integer and general
-    Phong exponents (rects / list), the kernel that ran read back; then beside Sobol, lights and a lens"""
+    """the three merging algorithms with k_merge_walk<IP, true> and with k_merge_pairs<IP, true> (the default), integer
+    and general Phong exponents (rects / list), the kernel that ran read back; then beside Sobol, lights and a lens"""
     _set_kind(kind, monkeypatch)
     _compare(gl.room(res[0], res[1]), algo, False, merge=merge, iters=3, rf=0.05)   # (a wide radius: hundreds of merges even at 20 x 14)
     if kind == "rects" and res == (20, 14):
@@ -162,14 +162,11 @@ def test_default_is_unchanged(algo):
         assert not np.array_equal(out[3][0], out[0][0])
 
 
-@pytest.mark.parametrize("algo", [5, 0, 4, 2])
-def test_two_thread_rank_shards_equal_one_context(algo):
-    """vcm_create_sharded8, world 2: two rank threads on one device exchanging light records against one context -- the
-    path tracer bit for bit, the others within rounding of the summation order"""
+def _two_rank_frames(d, algo, iters=3):
+    """the frames of two rank threads on one device exchanging light records (vcm_create_sharded8, world 2)"""
     from smallvcm_amd.renderer import ShardedVertexCM
     from test_gpu_dropin_sharded import _ThreadCollectives
-    d = gl.room()
-    world, iters = 2, 3
+    world = 2
     coll = _ThreadCollectives(world)
     results, errors = [None] * world, []
 
@@ -197,6 +194,10 @@ def test_two_thread_rank_shards_equal_one_context(algo):
     for t in ts:
         t.join(timeout=300)
     assert not errors, errors
+    return results
+
+
+def _check_shards_against_one_context(d, algo, results, iters=3):
     one = VertexCM(d, algo, 0.003, 0.75, 3)
     one.mMaxPathLength, one.mMinPathLength = 10, 0
     for it in range(iters):
@@ -209,6 +210,29 @@ def test_two_thread_rank_shards_equal_one_context(algo):
             assert np.array_equal(fb, want)
         else:
             assert np.allclose(fb, want, rtol=2e-6, atol=2e-7)
+
+
+@pytest.mark.parametrize("algo", [5, 0, 4, 2])
+def test_two_thread_rank_shards_equal_one_context(algo):
+    """vcm_create_sharded8, world 2: two rank threads on one device exchanging light records against one context -- the
+    path tracer bit for bit, the others within rounding of the summation order"""
+    d = gl.room()
+    _check_shards_against_one_context(d, algo, _two_rank_frames(d, algo))
+
+
+@pytest.mark.parametrize("algo", [4, 2])
+def test_two_thread_rank_shards_unsorted_exchange(monkeypatch, algo):
+    """the same with SMALLVCM_AMD_SORTED_EXCHANGE=0 (read in vcm_create*: set before the contexts are made):
+    k_compact_records<WithGgx<DScene>> writes the records and k_cell_rank_gather reads them.  What the sorted run
+    asserts, and both ranks' frames equal to the sorted run's bit for bit: both exchanges build the same grid
+    (test_gpu_dropin_sharded.py test_sorted_and_unsorted_exchange_render_the_same_bits, there without a lobe)"""
+    d = gl.room()
+    sorted_frames = _two_rank_frames(d, algo)
+    monkeypatch.setenv("SMALLVCM_AMD_SORTED_EXCHANGE", "0")
+    frames = _two_rank_frames(d, algo)
+    _check_shards_against_one_context(d, algo, frames)
+    for fb, want in zip(frames, sorted_frames):
+        assert np.array_equal(fb.view(np.uint32), want.view(np.uint32))
 
 
 @pytest.mark.parametrize("algo", [4, 3])
