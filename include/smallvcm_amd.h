@@ -926,6 +926,56 @@ int vcm_get_display_stats(vcm_ctx *ctx, vcm_display_stats *out);  /* synchronise
 int vcm_display_buffers(int device, int width, int height, const void *colorDev, int channels, float scale,
                         const vcm_display_params *p, void *outDev, vcm_display_stats *statsOut, void *hipStream);
 
+/* ---- image comparison: relMSE, PSNR, SSIM against a reference image ----
+ * "How far is this image from that one", on the device: nothing is read back but 72 bytes of sums.  img = source * scale and
+ * ref are linear RGB; d_c = img_c - ref_c in binary32, per pixel and channel:
+ *   mse      the mean of d^2
+ *   relMse   the mean of d^2 / (ref^2 + relEpsilon): the relative squared error the noise statistic estimates
+ *   mae      the mean of |d|
+ *   maxAbs   the largest |d|; maxPixel the index y * W + x of the pixel that holds it, the lowest on ties (-1 without one)
+ *   psnr     10 log10(peak^2 / mse), computed on the host in binary64; +Inf for mse == 0
+ *   above    the pixels whose largest per-channel d^2 / (ref^2 + relEpsilon) exceeds `threshold` (+Inf counts none)
+ *   ssim     the mean SSIM (Wang et al. 2004) of the luminance Y = 0.212671 r + 0.715160 g + 0.072169 b of both images,
+ *            clamped to [0, peak] and divided by peak: the 11 x 11 Gaussian window of sigma 1.5, C1 = 0.01^2, C2 = 0.03^2,
+ *            moments in binary32.  Only the windows that lie wholly inside the image count, (W - 10) x (H - 10) at most:
+ *            ssimWindows says how many, and ssim is NaN with none (every image narrower or lower than 11 pixels).  Identical
+ *            images give exactly 1.  ssim == 0 in the parameters launches no window kernel: ssim NaN, ssimWindows 0.
+ * A pixel with a non-finite channel in either image is counted in nonFinite and left out of every sum, of the maximum and
+ * of every window that holds it (121 windows for a pixel well inside); without a counted pixel the means are NaN.  `pixels`
+ * is W * H, `iterations` what the framebuffer held (0 from vcm_compare_buffers).  The sums are binary64 sums of binary32
+ * terms over a fixed grid and a fixed combination tree, without floating-point atomics: the same bits on every run.
+ * With writeMap == 1 the same kernels write the error map, W * H float4 { d^2 / (ref^2 + relEpsilon) of r, g, b; the SSIM
+ * of the window centred on the pixel, or 0 where it has none or ssim is off }; a non-finite pixel's entry is all zero.
+ * vcm_set_reference copies W*H*3 floats, row 0 = top, into the context (a non-finite texel is refused);
+ * vcm_set_reference_device copies a W*H float4 device image on the context's stream (non-finite texels are allowed and
+ * counted); NULL drops the reference.  vcm_envmap_load reads .pfm and .hdr files with rows top first: it is the loader for
+ * reference images too (its limits: at most 8192 x 4096, finite, >= 0, not all black).  CAUTION: it takes a PFM's rows
+ * bottom-up, as the format has them, while vcm_render -o x.pfm (like the reference's SavePFM) writes them top to bottom: such
+ * a file comes out of vcm_envmap_load upside down, without an error, and a host turns its rows round before it hands them
+ * to vcm_set_reference (vcm_render --reference does, for a name that ends in .pfm or .PFM).  With ssim == 1 a frame of more
+ * than 524290 rows is refused (the SSIM kernel's grid): compare it with ssim 0.  vcm_compare(ctx, source, scale, p,
+ * out): source as vcm_display's, with its refusals; it synchronises, because it returns numbers, and leaves the framebuffer
+ * and every tracked image alone.  Refused with -1 (vcm_last_error says which): a NULL argument, no reference, a scale or a
+ * parameter that is not finite (threshold may be +Inf), relEpsilon <= 0, peak <= 0, ssim or writeMap other than 0 / 1, and a
+ * sharded context: reduce the frame and call vcm_compare_buffers.  Memory: nothing before the first vcm_set_reference, which
+ * allocates 16 bytes per pixel; the first vcm_compare adds the partial sums (about 0.1 MB + 16 bytes per 256 windows), the
+ * first with writeMap 16 bytes per pixel; until vcm_destroy.  vcm_compare_map_device / vcm_read_compare_map give the map of
+ * the last vcm_compare with writeMap.  vcm_compare_buffers needs no context: images of 3 or 4 floats per pixel on `device`
+ * (a float4 image 16-byte aligned), mapOutDev W*H float4 or NULL (it must be given with writeMap == 1, and be neither
+ * input); scratch comes from hipMallocAsync / hipFreeAsync on the stream, which it synchronises. */
+typedef struct vcm_compare_params { float relEpsilon, peak, threshold; int ssim; int writeMap; } vcm_compare_params;
+typedef struct vcm_compare_stats  { int iterations; long long pixels, nonFinite, above, ssimWindows, maxPixel;
+                                    double mse, relMse, mae, maxAbs, psnr, ssim; } vcm_compare_stats;
+void vcm_compare_defaults(vcm_compare_params *out);              /* 0.01, 1, +Inf, ssim 1, writeMap 0 */
+int  vcm_set_reference(vcm_ctx *ctx, const float *rgbHost);      /* W*H*3, row 0 = top, copied; NULL drops it */
+int  vcm_set_reference_device(vcm_ctx *ctx, const void *float4Dev);
+int  vcm_compare(vcm_ctx *ctx, int source, float scale, const vcm_compare_params *p, vcm_compare_stats *out);
+int  vcm_compare_map_device(vcm_ctx *ctx, void **devPtr);        /* W*H float4, after a compare with writeMap */
+int  vcm_read_compare_map(vcm_ctx *ctx, float *host4);           /* W*H*4 floats */
+int  vcm_compare_buffers(int device, int width, int height, const void *imgDev, int imgChannels, float scale,
+                         const void *refDev, int refChannels, const vcm_compare_params *p, void *mapOutDev /* or NULL */,
+                         vcm_compare_stats *out, void *hipStream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -155,6 +155,11 @@ void vcm_debug_display_max_blocks(int blocks);
  * where there has been none. */
 int vcm_debug_read_display_histogram(unsigned long long *out256);
 
+/* The cap of the grid of the comparison's pixel kernel (0 restores the default, 2048 workgroups of 256 lanes), so that a
+ * test reaches the grid-stride path with a few hundred pixels.  Process-wide; the combination tree, and so the last bits
+ * of the sums of vcm_compare_stats, depend on it: not for production hosts. */
+void vcm_debug_compare_max_blocks(int blocks);
+
 /* sizeof the PODs of smallvcm_amd.h as the library was compiled */
 unsigned vcm_sizeof_scene_desc(void);
 unsigned vcm_sizeof_stats(void);

@@ -364,6 +364,24 @@ class DisplayStats(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+class CompareParams(C.Structure):
+    """vcm_compare_params: the epsilon of the relative error, the peak of PSNR and SSIM, the threshold `above` counts
+    beyond, SSIM and the error map on or off (include/smallvcm_amd.h)"""
+    _fields_ = [("relEpsilon", C.c_float), ("peak", C.c_float), ("threshold", C.c_float), ("ssim", C.c_int), ("writeMap", C.c_int)]
+
+
+class CompareStats(C.Structure):
+    """vcm_compare_stats: an image against a reference image -- the counts, mse, relMse, mae, maxAbs and where, psnr, ssim
+    (include/smallvcm_amd.h)"""
+    _fields_ = [("iterations", C.c_int), ("pixels", C.c_longlong), ("nonFinite", C.c_longlong), ("above", C.c_longlong),
+                ("ssimWindows", C.c_longlong), ("maxPixel", C.c_longlong),
+                ("mse", C.c_double), ("relMse", C.c_double), ("mae", C.c_double), ("maxAbs", C.c_double), ("psnr", C.c_double),
+                ("ssim", C.c_double)]
+
+    def asdict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
 class Stats(C.Structure):
     _fields_ = [("lightVertices", C.c_longlong), ("gridVertices", C.c_longlong),
                 ("lightRays", C.c_longlong), ("cameraRays", C.c_longlong),

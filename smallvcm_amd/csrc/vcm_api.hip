@@ -25,6 +25,7 @@
 #include "vcm_robust.h"
 #include "vcm_parts.h"
 #include "vcm_display.h"
+#include "vcm_compare.h"
 
 using namespace vcm;
 
@@ -211,6 +212,11 @@ struct vcm_ctx : Scratch {
     bool displayValid;
     vcm_display_params dispParams;    /* of the last vcm_display (dither and ditherSeed: vcm_read_display_image) */
     vcm_display_stats dispStats;      /* of the last vcm_display, but `clipped`: vcm_get_display_stats reads it */
+    /* the comparison with a reference image (vcm_compare.h): nothing until the first vcm_set_reference */
+    F4 *dCmpRef;                      /* N: the reference { rgb, - }; NULL while none is set */
+    F4 *dCmpMap;                      /* N: the last error map (allocated by the first vcm_compare with writeMap) */
+    char *dCmpScratch; size_t cmpScratchBytes;   /* the kernels' partials and the result (allocated by the first vcm_compare) */
+    bool cmpMapValid;
     int fbIterations;                 /* iterations the framebuffer holds: those since the last vcm_clear_framebuffer; while
                                          tracking is on (it starts at 0 only) also the k of the two images */
     IterParams P;
@@ -1067,6 +1073,7 @@ void vcm_destroy(vcm_ctx *c)
         DFREE(c->dRobPrev); DFREE(c->dRobBuckets); DFREE(c->dRobOut);
         DFREE(c->dParts); DFREE(c->dPartOut);
         DFREE(c->dDisplay); DFREE(c->dDispCounters); DFREE(c->dDispScratch);
+        DFREE(c->dCmpRef); DFREE(c->dCmpMap); DFREE(c->dCmpScratch);
         c->dScene = NULL; DFREE(c->dSceneBlob); DFREE(c->dFb); DFREE(c->dRngLight); DFREE(c->dRngCam); DFREE(c->dHdr); DFREE(c->dStatsRing); DFREE(c->dStamps);
         for (int i = 0; i < EV_COUNT; i++) (void)hipEventDestroy(c->ev[i]);
         (void)hipStreamSynchronize(c->side);
@@ -2973,6 +2980,164 @@ int vcm_debug_read_display_histogram(unsigned long long *out256)
     memcpy(out256, g_dispHistogram, sizeof(g_dispHistogram));
     return 0;
 }
+
+/* ---- the comparison with a reference image (kernels: vcm_compare.hip) ---- */
+void vcm_compare_defaults(vcm_compare_params *out)
+{
+    if (out) cmp_defaults(out);
+}
+
+static int compare_refuse_sharded(vcm_ctx *c, const char *who)
+{
+    if (c->world > 1) return fail(who, "sharded context: its framebuffer is a shard of the image; reduce the frame and call vcm_compare_buffers");
+    return 0;
+}
+
+/* NULL: the context forgets its reference and gives the memory back */
+static int compare_drop_reference(vcm_ctx *c)
+{
+    if (!c->dCmpRef) return 0;
+    if (use_device(c)) return -1;
+    HIPCHK(hipStreamSynchronize(c->stream));
+    DFREE(c->dCmpRef);
+    return 0;
+}
+
+int vcm_set_reference(vcm_ctx *c, const float *rgbHost)
+{
+    if (!c) return fail("vcm_set_reference", "ctx is NULL");
+    if (compare_refuse_sharded(c, "vcm_set_reference")) return -1;
+    if (!rgbHost) return compare_drop_reference(c);
+    std::vector<F4> texels((size_t)c->N);
+    for (size_t i = 0; i < (size_t)c->N; i++) {
+        const V3 t = ld3(rgbHost + i * 3);
+        if (!cmp_finite3(t)) return fail("vcm_set_reference", "the reference holds a non-finite texel");
+        texels[i] = mk4(t.x, t.y, t.z, 0.f);
+    }
+    if (ensure_device(c)) return -1;
+    if (!c->dCmpRef && dalloc(&c->dCmpRef, (size_t)c->N)) return -1;
+    HIPCHK(hipMemcpyAsync(c->dCmpRef, texels.data(), (size_t)c->N * sizeof(F4), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));   /* `texels` goes away */
+    return 0;
+}
+
+int vcm_set_reference_device(vcm_ctx *c, const void *float4Dev)
+{
+    if (!c) return fail("vcm_set_reference_device", "ctx is NULL");
+    if (compare_refuse_sharded(c, "vcm_set_reference_device")) return -1;
+    if (!float4Dev) return compare_drop_reference(c);
+    if ((uintptr_t)float4Dev & 15) return fail("vcm_set_reference_device", "float4Dev must be 16-byte aligned (a float4 image)");
+    if (ensure_device(c)) return -1;
+    if (!c->dCmpRef && dalloc(&c->dCmpRef, (size_t)c->N)) return -1;
+    HIPCHK(hipMemcpyAsync(c->dCmpRef, float4Dev, (size_t)c->N * sizeof(F4), hipMemcpyDeviceToDevice, c->stream));
+    return 0;
+}
+
+/* what vcm_compare and vcm_compare_buffers refuse of their numbers */
+static const char *compare_check(float scale, const vcm_compare_params *p)
+{
+    if (const char *why = cmp_check_params(p)) return why;
+    if (!cmp_finite(scale)) return "scale is not finite";
+    return NULL;
+}
+
+/* the comparison on stream s of the current device, behind every refusal; scratch: cmp_scratch_bytes(.., cap); synchronises s */
+static int compare_run(const char *who, int width, int height, const float *img, int imgChannels, float scale, const float *ref, int refChannels,
+                       const vcm_compare_params &p, int cap, F4 *map, char *scratch, int iterations, vcm_compare_stats *out, hipStream_t s)
+{
+    CmpResult r;
+    hipError_t e = cmp_launch(width, height, img, imgChannels, scale, ref, refChannels, p, cap, map, scratch, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(&r, cmp_result_of(scratch, width, height, cap), sizeof(r), hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (e != hipSuccess) return fail(who, hipGetErrorString(e));
+    cmp_finish_stats(r, iterations, (long long)width * height, p.peak, out);
+    return 0;
+}
+
+int vcm_compare(vcm_ctx *c, int source, float scale, const vcm_compare_params *p, vcm_compare_stats *out)
+{
+    if (!c || !p || !out) return fail("vcm_compare", "NULL argument");
+    if (compare_refuse_sharded(c, "vcm_compare")) return -1;
+    if (source != VCM_DISPLAY_FRAMEBUFFER && source != VCM_DISPLAY_DENOISED && source != VCM_DISPLAY_ROBUST) return fail("vcm_compare", "unknown source");
+    if (const char *why = compare_check(scale, p)) return fail("vcm_compare", why);
+    if (const char *why = cmp_check_size(c->resY, p)) return fail("vcm_compare", why);
+    if (!c->dCmpRef) return fail("vcm_compare", "no reference image: vcm_set_reference has not run");
+    const float *src = NULL;
+    int channels = 4;
+    if (source == VCM_DISPLAY_DENOISED) {
+        if (need_denoised(c, "vcm_compare")) return -1;
+        src = (const float *)c->dDenoised;
+    } else if (source == VCM_DISPLAY_ROBUST) {
+        if (vcm_robust_resolve(c)) return -1;
+        src = (const float *)c->dRobOut;
+    } else {
+        if (ensure_device(c)) return -1;
+        if (join_splats(c)) return -1;   /* the light splats / K5 of the last iteration add to the framebuffer on a stream of their own */
+        src = c->dFb; channels = 3;
+    }
+    const int cap = cmp_max_blocks();
+    const size_t need = cmp_scratch_bytes(c->resX, c->resY, cap);
+    if (need > c->cmpScratchBytes) {   /* once, but where vcm_debug_compare_max_blocks has raised the cap since */
+        if (c->dCmpScratch) { HIPCHK(hipStreamSynchronize(c->stream)); DFREE(c->dCmpScratch); c->cmpScratchBytes = 0; }
+        if (dalloc(&c->dCmpScratch, need)) return -1;
+        c->cmpScratchBytes = need;
+    }
+    if (p->writeMap && !c->dCmpMap && dalloc(&c->dCmpMap, (size_t)c->N)) return -1;
+    if (p->writeMap) c->cmpMapValid = false;
+    if (compare_run("vcm_compare", c->resX, c->resY, src, channels, scale, (const float *)c->dCmpRef, 4, *p, cap, c->dCmpMap, c->dCmpScratch,
+                    c->fbIterations, out, c->stream)) return -1;
+    if (p->writeMap) c->cmpMapValid = true;
+    return 0;
+}
+
+static int need_compare_map(vcm_ctx *c, const char *who)
+{
+    if (compare_refuse_sharded(c, who)) return -1;
+    if (!c->cmpMapValid) return fail(who, "no vcm_compare with writeMap has run");
+    return use_device(c);
+}
+
+int vcm_compare_map_device(vcm_ctx *c, void **devPtr)
+{
+    if (!c || !devPtr) return fail("vcm_compare_map_device", "NULL argument");
+    if (need_compare_map(c, "vcm_compare_map_device")) return -1;
+    *devPtr = c->dCmpMap;
+    return 0;
+}
+
+int vcm_read_compare_map(vcm_ctx *c, float *host4)
+{
+    if (!c || !host4) return fail("vcm_read_compare_map", "NULL argument");
+    if (need_compare_map(c, "vcm_read_compare_map")) return -1;
+    HIPCHK(hipMemcpyAsync(host4, c->dCmpMap, (size_t)c->N * sizeof(F4), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+int vcm_compare_buffers(int device, int width, int height, const void *imgDev, int imgChannels, float scale, const void *refDev, int refChannels,
+                        const vcm_compare_params *p, void *mapOutDev, vcm_compare_stats *out, void *hipStream)
+{
+    if (!imgDev || !refDev || !p || !out) return fail("vcm_compare_buffers", "NULL argument");
+    if (buffers_size_ok("vcm_compare_buffers", width, height)) return -1;
+    if ((imgChannels != 3 && imgChannels != 4) || (refChannels != 3 && refChannels != 4)) return fail("vcm_compare_buffers", "channels must be 3 or 4");
+    if (const char *why = compare_check(scale, p)) return fail("vcm_compare_buffers", why);
+    if (const char *why = cmp_check_size(height, p)) return fail("vcm_compare_buffers", why);
+    if (p->writeMap && !mapOutDev) return fail("vcm_compare_buffers", "writeMap without mapOutDev");
+    if (mapOutDev && (mapOutDev == imgDev || mapOutDev == refDev)) return fail("vcm_compare_buffers", "mapOutDev is one of the inputs");
+    if (((uintptr_t)mapOutDev & 15) || ((uintptr_t)imgDev & (imgChannels == 4 ? 15 : 3)) || ((uintptr_t)refDev & (refChannels == 4 ? 15 : 3)))
+        return fail("vcm_compare_buffers", "a float4 image must be 16-byte aligned, a 3-float image 4-byte aligned");
+    if (buffers_device("vcm_compare_buffers", device)) return -1;
+    hipStream_t s = (hipStream_t)hipStream;
+    const int cap = cmp_max_blocks();
+    char *scratch = NULL;   /* stream-ordered: given back behind the copy of the result */
+    HIPCHK(hipMallocAsync((void **)&scratch, cmp_scratch_bytes(width, height, cap), s));
+    const int rc = compare_run("vcm_compare_buffers", width, height, (const float *)imgDev, imgChannels, scale, (const float *)refDev, refChannels, *p, cap,
+                               (F4 *)mapOutDev, scratch, 0, out, s);
+    (void)hipFreeAsync(scratch, s);
+    return rc;
+}
+
+void vcm_debug_compare_max_blocks(int blocks) { cmp_set_max_blocks(blocks); }
 
 /* ---- the technique breakdown (kernels: vcm_parts.hip; the LIGHT_TRACE plane: flush_light_splats) ---- */
 int vcm_track_parts(vcm_ctx *c, int on)

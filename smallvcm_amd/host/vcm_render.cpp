@@ -16,6 +16,7 @@
 //              [--projection fisheye DEG|panorama]
 //              [--denoise [passes]] [--denoise-sigma c,n,z] [--no-demodulate] [--features-out prefix]
 //              [--noise-target E [--check-every N] [--max-iterations M]] [--track-variance] [--robust [M]]
+//              [--reference FILE [--compare-every N] [--compare-log FILE.csv] [--error-target relMSE [--max-iterations M]] [--error-map FILE.pfm]]
 //              [--tonemap clamp|reinhard|aces|hable] [--exposure EV] [--auto-exposure [key]] [--bloom S [levels]]
 //              [--srgb] [--dither]
 //              [--parts prefix]
@@ -82,6 +83,22 @@
 // the robust image with --robust, else the framebuffer / iterations.  What the transform saw (vcm_get_display_stats: the
 // exposure picked, the channels clipped) is printed, and is "display" in --json; .hdr and .pfm stay linear, and without
 // these flags every file is what it was.  They want one renderer on one GPU.
+//
+// --reference FILE [--compare-every N] [--compare-log FILE.csv] [--error-target relMSE [--max-iterations M]]
+// [--error-map FILE.pfm]: the image is compared with a reference image on the device (vcm_set_reference, vcm_compare).  FILE is
+// a .pfm or .hdr of the frame's resolution (vcm_envmap_load reads it; a .pfm is taken with its rows top to bottom, as -o and
+// the reference's SavePFM write them, not bottom-up as the format has them; another resolution is refused).  Every
+// N iterations (--compare-every) and after the last, a line "compare after K iteration(s): relMSE .. MSE .. PSNR .. SSIM ..
+// maxAbs .. nonFinite .." is printed, and written to --compare-log as a CSV row (iteration, relMSE, MSE, PSNR, SSIM, maxAbs,
+// nonFinite, under a header row).  With --error-target rendering runs iterations 0, 1, ... and stops at the first check at
+// or below the target, or at --max-iterations (default 1024; without --compare-every every 4 iterations are checked).  The
+// compared image is the one written to -o: the denoised image with --denoise (filtered for every check), the robust estimate
+// with --robust (checked once it has as many iterations as buckets; fewer iterations than buckets in all are refused), else
+// framebuffer / iterations.  With --noise-target the run stops by the noise statistic as before and the error is looked at
+// every --compare-every iterations (default: --check-every) and at the iteration the run stops, so that the last line is
+// the true error of the image written.  --error-map writes the
+// last check's relative squared error of r, g, b as a PFM.  The last check is "compare" in --json.  One renderer on one GPU;
+// without --reference every file is what it was.
 //
 // -s / -a / -i keep the meaning they have in the reference's CLI
 // (src/config.hxx:246-395; scenes = g_SceneConfigs[0..3], :146-151).
@@ -163,6 +180,12 @@ int main(int argc, char **argv)
     vcm_display_defaults(&disp.p);
     vcm_display_stats ds = {};
     bool displayed = false;
+    std::string refFile, compareLog, errorMap;
+    int compareEvery = 0;
+    bool haveErrorTarget = false, haveCompareOption = false, haveMaxIterations = false;
+    float errorTarget = 0.f;
+    vcm_compare_stats cs = {};
+    int compareChecks = 0;
     for (int i = 1; i < argc; i++) {
         const std::string a(argv[i]);
         if (const int taken = display_parse_flag(argc, argv, i, disp)) { if (taken < 0) return 2; continue; }
@@ -246,7 +269,18 @@ int main(int argc, char **argv)
             haveTarget = trackVariance = true;
         }
         else if (a == "--check-every") { need(1); checkEvery = atoi(argv[++i]); haveTargetOption = true; }
-        else if (a == "--max-iterations") { need(1); maxIterations = atoi(argv[++i]); haveTargetOption = true; }
+        else if (a == "--max-iterations") { need(1); maxIterations = atoi(argv[++i]); haveMaxIterations = true; }
+        else if (a == "--reference") { need(1); refFile = argv[++i]; }
+        else if (a == "--compare-every") { need(1); compareEvery = atoi(argv[++i]); haveCompareOption = true; if (compareEvery < 1) { fprintf(stderr, "vcm_render: --compare-every >= 1\n"); return 2; } }
+        else if (a == "--compare-log") { need(1); compareLog = argv[++i]; haveCompareOption = true; }
+        else if (a == "--error-map") { need(1); errorMap = argv[++i]; haveCompareOption = true; }
+        else if (a == "--error-target") {
+            need(1);
+            char *e = NULL;
+            errorTarget = strtof(argv[++i], &e);
+            if (e == argv[i] || *e || !(errorTarget >= 0.f)) { fprintf(stderr, "vcm_render: --error-target needs a number >= 0\n"); return 2; }
+            haveErrorTarget = haveCompareOption = true;
+        }
         else if (a == "--track-variance") trackVariance = true;
         else if (a == "--robust") {
             robust = VCM_ROBUST_DEFAULT_BUCKETS;
@@ -294,7 +328,18 @@ int main(int argc, char **argv)
         fprintf(stderr, "vcm_render: --parts reads what wavefront mode keeps apart: no --strict, --maxlen <= 31\n");
         return 2;
     }
-    if (haveTargetOption && !haveTarget) { fprintf(stderr, "vcm_render: --check-every and --max-iterations go with --noise-target\n"); return 2; }
+    if (haveCompareOption && refFile.empty()) { fprintf(stderr, "vcm_render: --compare-every, --compare-log, --error-target and --error-map go with --reference\n"); return 2; }
+    if (!refFile.empty() && (renderers != 1 || gpus > 0)) {
+        fprintf(stderr, "vcm_render: --reference wants one renderer on one GPU (a farm host reduces the frames and calls vcm_compare_buffers)\n");
+        return 2;
+    }
+    if (!refFile.empty() && robust && ((haveTarget || haveErrorTarget) ? maxIterations : iterations) < robust) {
+        fprintf(stderr, "vcm_render: --reference with --robust %d wants at least %d iterations: the estimate cannot be resolved, and so not compared, before\n", robust, robust);
+        return 2;
+    }
+    if (haveErrorTarget && haveTarget) { fprintf(stderr, "vcm_render: --error-target and --noise-target do not combine\n"); return 2; }
+    if (haveErrorTarget && maxIterations < 1) { fprintf(stderr, "vcm_render: --max-iterations >= 1\n"); return 2; }
+    if ((haveTargetOption || (haveMaxIterations && !haveErrorTarget)) && !haveTarget) { fprintf(stderr, "vcm_render: --check-every and --max-iterations go with --noise-target\n"); return 2; }
     if (haveTarget && (checkEvery < 1 || maxIterations < 2)) { fprintf(stderr, "vcm_render: --check-every >= 1, --max-iterations >= 2\n"); return 2; }
     if (haveAperture != haveFocus) { fprintf(stderr, "vcm_render: --aperture and --focus go together\n"); return 2; }
     if (!pickName.empty() && pickName != "uniform" && pickName != "power") { fprintf(stderr, "vcm_render: --light-pick uniform|power\n"); return 2; }
@@ -488,6 +533,24 @@ int main(int argc, char **argv)
         if (robust && vcm_track_robust(r[g], robust)) return die("vcm_track_robust");
         if (!partsOut.empty() && vcm_track_parts(r[g], 1)) return die("vcm_track_parts");
     }
+    if (!refFile.empty()) {   // the reference image: a .pfm or .hdr of the frame's resolution
+        vcm_envmap *ref = vcm_envmap_load(refFile.c_str());
+        if (!ref) { fprintf(stderr, "vcm_render: --reference: %s\n", vcm_scene_load_error()); return 2; }
+        if (ref->width != resX || ref->height != resY) {
+            fprintf(stderr, "vcm_render: --reference %s is %d x %d, the frame %d x %d\n", refFile.c_str(), ref->width, ref->height, resX, resY);
+            vcm_envmap_free(ref);
+            return 2;
+        }
+        // a .pfm is read as this program (and the reference's SavePFM) writes it, rows top to bottom; vcm_envmap_load takes a
+        // PFM's rows bottom-up, as the format has them, so its rows are turned back
+        std::vector<float> rows(ref->rgb, ref->rgb + (size_t)resX * resY * 3);
+        const std::string ext = refFile.size() >= 4 ? refFile.substr(refFile.size() - 4) : "";
+        if (ext == ".pfm" || ext == ".PFM")
+            for (int y = 0; y < resY; y++) memcpy(&rows[(size_t)y * resX * 3], ref->rgb + (size_t)(resY - 1 - y) * resX * 3, (size_t)resX * 3 * sizeof(float));
+        const int rc = vcm_set_reference(r[0], rows.data());
+        vcm_envmap_free(ref);
+        if (rc) return die("vcm_set_reference");
+    }
     if (pick && (pick->mode != VCM_LIGHT_PICK_UNIFORM || pickReport) && !json) {
         const int nLights = pickScene->base.base.base.nLights;
         printf("light pick: %s, uniform mix %g, %d light(s)\n", pick->mode == VCM_LIGHT_PICK_POWER ? "power" : "uniform", pick->uniformMix, nLights);
@@ -518,21 +581,66 @@ int main(int argc, char **argv)
     const auto t0 = std::chrono::steady_clock::now();
     // static schedule of `#pragma omp parallel for` (smallvcm.cxx:98-108): contiguous blocks, the first
     // iterations % renderers threads get one more
-    if (haveTarget) {   // one renderer, iterations 0, 1, ... until the statistic is at or below the target
+    if (haveTarget || !refFile.empty()) {   // one renderer, iterations 0, 1, ...: looks at the noise statistic, at the error against the reference, or both
+        FILE *log = NULL;
+        if (!compareLog.empty()) {
+            log = fopen(compareLog.c_str(), "w");
+            if (!log) { fprintf(stderr, "vcm_render: cannot write %s\n", compareLog.c_str()); return 2; }
+            fprintf(log, "iteration,relMSE,MSE,PSNR,SSIM,maxAbs,nonFinite\n");
+        }
+        // with a stop rule (--noise-target, --error-target) up to --max-iterations; the error is looked at every --compare-every
+        // iterations (default: 4 with --error-target, --check-every with --noise-target, else never), after the last iteration and
+        // where the noise target stops the run
+        const int last = (haveTarget || haveErrorTarget) ? maxIterations : iterations;
+        const int every = compareEvery > 0 ? compareEvery : (haveErrorTarget ? 4 : (haveTarget ? checkEvery : 0));
+        vcm_compare_params cp;
+        vcm_compare_defaults(&cp);
+        if (haveErrorTarget) cp.threshold = errorTarget;
         vcm_noise_stats ns;
-        for (iterations = 0; iterations < maxIterations;) {
+        for (iterations = 0; iterations < last;) {
             if (vcm_run_iteration(r[0], iterations, minLen, maxLen)) return die("vcm_run_iteration");
             iterations++;
-            if (iterations < 2 || (iterations % checkEvery != 0 && iterations != maxIterations)) continue;
-            if (vcm_get_noise_stats(r[0], noiseTarget, &ns)) return die("vcm_get_noise_stats");
-            if (!json) printf("noise after %d iteration(s): mean %.9g, max %.9g, %lld of %lld above the target, %lld non-finite\n",
-                              ns.iterations, ns.mean, ns.max, ns.above, ns.elements, ns.nonFinite);
-            if (ns.mean <= (double)noiseTarget) break;
+            bool stop = iterations == last;
+            if (haveTarget && iterations >= 2 && (iterations % checkEvery == 0 || iterations == last)) {
+                if (vcm_get_noise_stats(r[0], noiseTarget, &ns)) return die("vcm_get_noise_stats");
+                if (!json) printf("noise after %d iteration(s): mean %.9g, max %.9g, %lld of %lld above the target, %lld non-finite\n",
+                                  ns.iterations, ns.mean, ns.max, ns.above, ns.elements, ns.nonFinite);
+                if (ns.mean <= (double)noiseTarget) stop = true;
+            }
+            if (!refFile.empty() && (stop || (every > 0 && iterations % every == 0)) && !(robust && iterations < robust)) {   // (a robust estimate
+                // of fewer iterations than buckets is not resolvable: refused before rendering for the last iteration, skipped before it)
+                if (denoise && vcm_denoise(r[0], 1.f / iterations, &dn)) return die("vcm_denoise");
+                const int source = denoise ? VCM_DISPLAY_DENOISED : (robust ? VCM_DISPLAY_ROBUST : VCM_DISPLAY_FRAMEBUFFER);
+                cp.writeMap = (!errorMap.empty() && (stop || haveErrorTarget)) ? 1 : 0;
+                if (vcm_compare(r[0], source, source == VCM_DISPLAY_FRAMEBUFFER ? 1.f / iterations : 1.f, &cp, &cs)) return die("vcm_compare");
+                compareChecks++;
+                if (!json) printf("compare after %d iteration(s): relMSE %.9g MSE %.9g PSNR %.6g SSIM %.9g maxAbs %.9g nonFinite %lld\n", iterations,
+                                  cs.relMse, cs.mse, cs.psnr, cs.ssim, cs.maxAbs, cs.nonFinite);
+                if (log) fprintf(log, "%d,%.17g,%.17g,%.17g,%.17g,%.17g,%lld\n", iterations, cs.relMse, cs.mse, cs.psnr, cs.ssim, cs.maxAbs, cs.nonFinite);
+                if (haveErrorTarget && cs.relMse <= (double)errorTarget) stop = true;
+            }
+            if (stop) break;
         }
-        if (!json) printf("noise target %g: %d iteration(s) used\n", noiseTarget, iterations);
+        if (haveTarget && !json) printf("noise target %g: %d iteration(s) used\n", noiseTarget, iterations);
+        if (log) fclose(log);
+        if (haveErrorTarget && !json) printf("error target %g: %d iteration(s) used\n", errorTarget, iterations);
+        if (!refFile.empty() && compareChecks == 0) {   // the noise target stopped a --robust run before it had an iteration per bucket
+            fprintf(stderr, "vcm_render: --reference: no check was possible, the robust estimate needs %d iterations and the run ended after %d\n", robust, iterations);
+            return 2;
+        }
+        if (!errorMap.empty()) {   // the last check's relative squared error, rows top to bottom like SavePFM
+            std::vector<float> m4((size_t)resX * resY * 4), m3((size_t)resX * resY * 3);
+            if (vcm_read_compare_map(r[0], m4.data())) return die("vcm_read_compare_map");
+            for (size_t p = 0; p < (size_t)resX * resY; p++) for (int k = 0; k < 3; k++) m3[p * 3 + k] = m4[p * 4 + k];
+            FILE *f = fopen(errorMap.c_str(), "wb");
+            if (!f) { fprintf(stderr, "vcm_render: cannot write %s\n", errorMap.c_str()); return 2; }
+            fprintf(f, "PF\n%d %d\n-1\n", resX, resY);
+            fwrite(m3.data(), sizeof(float), m3.size(), f);
+            fclose(f);
+        }
     }
     const int q = iterations / renderers, rem = iterations % renderers;
-    for (int g = 0; g < renderers && !haveTarget; g++) {
+    for (int g = 0; g < renderers && !haveTarget && refFile.empty(); g++) {
         const int lo = g * q + (g < rem ? g : rem), n = q + (g < rem ? 1 : 0);
         for (int it = lo; it < lo + n; it++)
             if (vcm_run_iteration(r[g], it, minLen, maxLen)) return die("vcm_run_iteration");
@@ -704,8 +812,16 @@ int main(int argc, char **argv)
         if (!partsOut.empty()) snprintf(partsJson, sizeof(partsJson), ", \"parts\": {\"iterations\": %d, \"pixels\": %lld, \"nonFinite\": %lld, \"luminance\": "
                                         "{\"emission\": %.17g, \"direct\": %.17g, \"connect\": %.17g, \"merge\": %.17g, \"lighttrace\": %.17g}}",
                                         ps.iterations, ps.pixels, ps.nonFinite, ps.luminance[0], ps.luminance[1], ps.luminance[2], ps.luminance[3], ps.luminance[4]);
-        char displayJson[480] = "";
-        if (disp.any) display_stats_json(ds, displayJson, sizeof(displayJson));
+        char displayJson[880] = "";
+        if (disp.any) display_stats_json(ds, displayJson, 480);
+        if (!refFile.empty()) {   // (a NaN or an infinity is no JSON number: null)
+            auto num = [](double v) { char b[40]; if (std::isfinite(v)) snprintf(b, sizeof(b), "%.17g", v); else snprintf(b, sizeof(b), "null"); return std::string(b); };
+            const size_t at = strlen(displayJson);
+            snprintf(displayJson + at, sizeof(displayJson) - at, ", \"compare\": {\"iterations\": %d, \"pixels\": %lld, \"nonFinite\": %lld, \"above\": %lld, "
+                     "\"ssimWindows\": %lld, \"maxPixel\": %lld, \"mse\": %s, \"relMse\": %s, \"mae\": %s, \"maxAbs\": %s, \"psnr\": %s, \"ssim\": %s}",
+                     cs.iterations, cs.pixels, cs.nonFinite, cs.above, cs.ssimWindows, cs.maxPixel, num(cs.mse).c_str(), num(cs.relMse).c_str(),
+                     num(cs.mae).c_str(), num(cs.maxAbs).c_str(), num(cs.psnr).c_str(), num(cs.ssim).c_str());
+        }
         std::string ms = "[";
         for (size_t i = 0; i < rankMs.size(); i++) { char b[32]; snprintf(b, sizeof(b), "%s%.3f", i ? ", " : "", rankMs[i]); ms += b; }
         ms += "]";

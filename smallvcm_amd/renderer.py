@@ -21,7 +21,7 @@ import os
 
 import numpy as np
 
-from ._abi import (CURVES, DISPLAY_SOURCES, DenoiseParams, DenoiseParams2, DisplayParams, DisplayStats, FEATURES, IMAGE_BGR8, TRANSFERS, NoiseStats, PART_NAMES, PARTS, PartsStats, ROBUST_DEFAULT_BUCKETS, RobustStats, SceneDesc, SceneDesc2, SceneDesc3, SceneDesc4, SceneDesc5, SceneDesc6, SceneDesc7, SceneDesc8, SceneDesc9, Stats, SCENE_CONFIGS, VCM_MERGE_RECORD_FLOATS, ALGO_LIGHT_TRACE, ALGO_PPM, ALGO_BPM,
+from ._abi import (CURVES, CompareParams, CompareStats, DISPLAY_SOURCES, DenoiseParams, DenoiseParams2, DisplayParams, DisplayStats, FEATURES, IMAGE_BGR8, TRANSFERS, NoiseStats, PART_NAMES, PARTS, PartsStats, ROBUST_DEFAULT_BUCKETS, RobustStats, SceneDesc, SceneDesc2, SceneDesc3, SceneDesc4, SceneDesc5, SceneDesc6, SceneDesc7, SceneDesc8, SceneDesc9, Stats, SCENE_CONFIGS, VCM_MERGE_RECORD_FLOATS, ALGO_LIGHT_TRACE, ALGO_PPM, ALGO_BPM,
                    ALGO_BPT, ALGO_VCM)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -173,6 +173,17 @@ def load_library(require_gpu=True):
         L.vcm_get_display_stats.argtypes = [vp, C.POINTER(DisplayStats)]
         L.vcm_display_buffers.argtypes = [C.c_int, C.c_int, C.c_int, vp, C.c_int, C.c_float, C.POINTER(DisplayParams), vp,
                                           C.POINTER(DisplayStats), vp]
+        L.vcm_compare_defaults.argtypes = [C.POINTER(CompareParams)]
+        L.vcm_compare_defaults.restype = None
+        L.vcm_set_reference.argtypes = [vp, fp]
+        L.vcm_set_reference_device.argtypes = [vp, vp]
+        L.vcm_compare.argtypes = [vp, C.c_int, C.c_float, C.POINTER(CompareParams), C.POINTER(CompareStats)]
+        L.vcm_compare_map_device.argtypes = [vp, C.POINTER(vp)]
+        L.vcm_read_compare_map.argtypes = [vp, fp]
+        L.vcm_compare_buffers.argtypes = [C.c_int, C.c_int, C.c_int, vp, C.c_int, C.c_float, vp, C.c_int, C.POINTER(CompareParams), vp,
+                                          C.POINTER(CompareStats), vp]
+        L.vcm_debug_compare_max_blocks.argtypes = [C.c_int]
+        L.vcm_debug_compare_max_blocks.restype = None
         L.vcm_debug_display_max_blocks.argtypes = [C.c_int]
         L.vcm_debug_display_max_blocks.restype = None
         L.vcm_debug_read_display_histogram.argtypes = [C.POINTER(C.c_ulonglong)]
@@ -259,6 +270,44 @@ def display_tensors(color, out=None, scale=1.0, **params):
     _check(L, L.vcm_display_buffers(dev, int(color.shape[1]), int(color.shape[0]), color.data_ptr(), int(color.shape[2]), float(scale),
                                     C.byref(p), out.data_ptr(), C.byref(st), torch.cuda.current_stream(dev).cuda_stream), "vcm_display_buffers")
     return out, st.asdict()
+
+
+def compare_params(**kw):
+    """vcm_compare_defaults with some members replaced: relEpsilon (0.01), peak (1), threshold (+Inf), ssim (1), writeMap (0)"""
+    L = load_library(require_gpu=False)
+    p = CompareParams()
+    L.vcm_compare_defaults(C.byref(p))
+    for k, v in kw.items():
+        if k not in [n for n, _ in CompareParams._fields_]:
+            raise TypeError("unknown compare parameter %r" % k)
+        setattr(p, k, v)
+    return p
+
+
+def compare_tensors(img, ref, map_out=None, scale=1.0, **params):
+    """vcm_compare_buffers over torch tensors: img * scale against ref, each [H, W, 3] or [H, W, 4] float32, contiguous, on
+    one GPU -> the dict of vcm_compare_stats.  map_out: a contiguous float32 tensor [H, W, 4] on that GPU that takes the
+    error map {relative squared error r, g, b; SSIM} (it switches writeMap on), or None.  Runs on torch's current stream
+    of that device and waits for it; params: see compare_params()"""
+    import torch
+    L = load_library()
+    for t in (img, ref):
+        if t.dtype != torch.float32 or not t.is_cuda or not t.is_contiguous() or t.dim() != 3 or t.shape[2] not in (3, 4):
+            raise ValueError("compare_tensors wants contiguous float32 GPU tensors [H, W, 3] or [H, W, 4]")
+    if tuple(img.shape[:2]) != tuple(ref.shape[:2]) or img.device != ref.device:
+        raise ValueError("compare_tensors wants two images of one size on one device")
+    if map_out is not None:
+        if (map_out.dtype != torch.float32 or not map_out.is_cuda or not map_out.is_contiguous() or map_out.device != img.device
+                or tuple(map_out.shape) != (img.shape[0], img.shape[1], 4)):
+            raise ValueError("compare_tensors wants map_out as a contiguous float32 GPU tensor [H, W, 4]")
+        params = dict(params, writeMap=1)
+    dev = img.device.index if img.device.index is not None else torch.cuda.current_device()
+    p = compare_params(**params)
+    st = CompareStats()
+    _check(L, L.vcm_compare_buffers(dev, int(img.shape[1]), int(img.shape[0]), img.data_ptr(), int(img.shape[2]), float(scale), ref.data_ptr(),
+                                    int(ref.shape[2]), C.byref(p), map_out.data_ptr() if map_out is not None else None, C.byref(st),
+                                    torch.cuda.current_stream(dev).cuda_stream), "vcm_compare_buffers")
+    return st.asdict()
 
 
 def denoise_tensors2(color, albedo, guide, mom, k, out=None, **params):
@@ -400,6 +449,24 @@ def render_until(renderer, noise, check_every=4, max_iterations=1024):
         if k >= 2 and (k % check_every == 0 or k == max_iterations):
             history.append(renderer.backend.noise_stats(noise))
             if history[-1]["mean"] <= noise:
+                break
+    return history
+
+
+def render_to_error(renderer, rel_mse, check_every=4, max_iterations=1024):
+    """Run iterations 0, 1, ... of `renderer` (RunIteration, mIterations, backend.compare: VertexCM with a reference set, or
+    a stand-in) until relMse against the reference is <= `rel_mse`: it is looked at after every `check_every` iterations
+    and after the last one, and rendering stops at the first look at or below the target or at `max_iterations`.  Returns
+    the looks, in order: vcm_compare_stats dicts (`above` counts the pixels over the target)."""
+    if check_every < 1 or max_iterations < 1:
+        raise ValueError("render_to_error wants check_every >= 1 and max_iterations >= 1")
+    history = []
+    while renderer.mIterations < max_iterations:
+        renderer.RunIteration(renderer.mIterations)
+        k = renderer.mIterations
+        if k % check_every == 0 or k == max_iterations:
+            history.append(renderer.backend.compare(threshold=rel_mse))
+            if history[-1]["relMse"] <= rel_mse:
                 break
     return history
 
@@ -697,6 +764,47 @@ class HipBackend:
         _check(self.L, self.L.vcm_read_display_image(self.ctx, fmt, out.ctypes.data_as(C.POINTER(C.c_ubyte))), "vcm_read_display_image")
         return out
 
+    # ---- the comparison with a reference image ----------------------------------
+    def set_reference(self, img):
+        """vcm_set_reference: the image [H, W, 3] (rows top first, linear RGB, finite) every compare() measures against;
+        None drops it"""
+        if img is None:
+            _check(self.L, self.L.vcm_set_reference(self.ctx, None), "vcm_set_reference")
+            return
+        img = np.ascontiguousarray(img, np.float32)
+        if img.shape != (self.resy, self.resx, 3):
+            raise ValueError("set_reference wants an image [%d, %d, 3]" % (self.resy, self.resx))
+        _check(self.L, self.L.vcm_set_reference(self.ctx, img.ctypes.data_as(C.POINTER(C.c_float))), "vcm_set_reference")
+
+    def set_reference_device(self, ptr):
+        """vcm_set_reference_device: a W * H float4 device image, copied on the context's stream"""
+        _check(self.L, self.L.vcm_set_reference_device(self.ctx, ptr), "vcm_set_reference_device")
+
+    def compare(self, source="framebuffer", scale=None, **params):
+        """vcm_compare: `source` ('framebuffer', 'denoised', 'robust') * scale against the reference -> the dict of
+        vcm_compare_stats {iterations, pixels, nonFinite, above, ssimWindows, maxPixel, mse, relMse, mae, maxAbs, psnr, ssim};
+        scale None: 1 / iterations for the framebuffer, 1 otherwise; params: see compare_params()"""
+        src = DISPLAY_SOURCES[source] if isinstance(source, str) else int(source)
+        if scale is None:
+            scale = 1.0 / self._fb_iterations if (src == DISPLAY_SOURCES["framebuffer"] and self._fb_iterations > 0) else 1.0
+        p = compare_params(**params)
+        st = CompareStats()
+        _check(self.L, self.L.vcm_compare(self.ctx, src, scale, C.byref(p), C.byref(st)), "vcm_compare")
+        return st.asdict()
+
+    def compare_map(self):
+        """vcm_read_compare_map: the error map [H, W, 4] of the last compare(writeMap=1) -- the relative squared error of
+        r, g, b and the SSIM of the window centred on the pixel (0 where it has none)"""
+        out = np.zeros((self.resy, self.resx, 4), np.float32)
+        _check(self.L, self.L.vcm_read_compare_map(self.ctx, out.ctypes.data_as(C.POINTER(C.c_float))), "vcm_read_compare_map")
+        return out
+
+    def compare_map_device(self):
+        """device pointer of the last compare(writeMap=1)'s float4 map"""
+        p = C.c_void_p()
+        _check(self.L, self.L.vcm_compare_map_device(self.ctx, C.byref(p)), "vcm_compare_map_device")
+        return p.value
+
     # ---- the technique breakdown ------------------------------------------------
     def track_parts(self, on=True):
         """keep the five kinds of addends of the framebuffer -- emission, direct, connect, merge, lighttrace -- in planes of
@@ -820,6 +928,11 @@ class VertexCM:
             raise RuntimeError("smallvcm_amd: render_until wants a renderer that has not run an iteration (variance tracking starts with the first)")
         self.backend.track_variance()
         return render_until(self, noise, check_every, max_iterations)
+
+    def render_to_error(self, reference, rel_mse, check_every=4, max_iterations=1024):
+        """render_to_error() of this module on this renderer, against the image `reference` [H, W, 3]"""
+        self.backend.set_reference(reference)
+        return render_to_error(self, rel_mse, check_every, max_iterations)
 
     def framebuffer_sum(self):
         return self.backend.framebuffer_sum()
